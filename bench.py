@@ -12,6 +12,13 @@ parity_path = the same workload at precision "bf16x3" (split-bf16, <= 1e-4 vs th
 reference_class_path = the same at precision "fp16" (10 mantissa bits = the TF32 arithmetic the reference itself computes in).
 cpu_baseline = the CPU oracle ("port" of the reference algorithm) on this box's host cores, bounded sample.
 
+A plain run measures the headline only: set-up, `--warmup` untimed steps, `--steps` timed steps (`ms_per_step` = milliseconds of
+one of them), the JSON line.  `--full` adds every other record: parity_path, reference_class_path, cpu_baseline, the MFMA ceiling,
+the other workloads, samplers, VAE, end-to-end and training records, and for N > 1 the all-gather timing, the cross-rank
+self-check and the strong-scaling leg.  `--dump-outputs DIR` writes what the timed path returned in its last step as
+DIR/<name>.npy (float32; at most 64 MB, larger outputs as a fixed seeded sample of rows); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (one process per
 GPU through torch.distributed.run, before this process touches a GPU); under an external launcher (the driver's
 `python -m torch.distributed.run ... bench.py --gpus N`) it runs as the rank it was started as.
@@ -294,9 +301,10 @@ def make_optimizer(params, lr, kind="native", max_grad_norm=None):
     return AdamW(params, lr=lr, max_grad_norm=max_grad_norm)
 
 
-def time_training(wl, precision, device, steps, warmup, dist_on, world, optimizer="native", graphed=False):
+def time_training(wl, precision, device, steps, warmup, dist_on, world, optimizer="native", graphed=False, outputs=None):
     """One step = Transport.training_losses forward + HIP backward + gradient all-reduce (N > 1) + fused AdamW on the per-GPU
-    batch of synthetic latents (standing in for frozen-VAE output).  Returns seconds for `steps` steps (max over ranks)."""
+    batch of synthetic latents (standing in for frozen-VAE output).  Returns seconds for `steps` steps (max over ranks).  A dict
+    passed as `outputs` receives the last step's loss and the parameters the steps left (for --dump-outputs)."""
     from scldm_amd.training import train_step
     from scldm_amd.transport import create_transport
     import gc
@@ -368,6 +376,9 @@ def time_training(wl, precision, device, steps, warmup, dist_on, world, optimize
         time_training.info["replicas_in_sync"] = bool(float(hi - lo) <= 1e-6 * max(1.0, abs(float(hi))))
         if not time_training.info["replicas_in_sync"]:
             raise SystemExit("bench.py: data-parallel replicas diverged (parameter checksums differ across ranks)")
+    if outputs is not None:
+        outputs["loss"] = torch.as_tensor(loss).detach().float().reshape(1)
+        outputs["parameters"] = torch.cat([p.detach().float().reshape(-1) for p in m.parameters()])
     return dt, float(loss)
 
 
@@ -1019,6 +1030,30 @@ def emit(result, rank):
         print(line, flush=True)  # the one JSON line
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one `path`/<name>.npy per array, float32 (float64 stays float64), 64 MB at most in all.  Arrays are written
+    smallest first; one that does not fit in what is left of the budget keeps a fixed, seeded sample of its rows (first axis), in
+    their original order - the same rows on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        a = t.detach()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        if a.dim() > 0 and a.numel() * a.element_size() > left:
+            row = a[0].numel() * a.element_size()
+            keep = left // row
+            idx = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a[idx.to(a.device)]
+            note(f"--dump-outputs: {name} cut to a seeded sample of {keep} of its {t.shape[0]} rows")
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1029,13 +1064,19 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
     ap.add_argument("--global-cells", type=int, default=0, help="override the GLOBAL cell count of the strong-scaling leg (N > 1)")
     ap.add_argument("--evals", type=int, default=0, help="override the number of CFG evaluations (profiling only; not a valid bench line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short extra-workload measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other record (other precisions, workloads, CPU baseline, ceilings, training, N > 1 checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra-workload measurements")
     args = ap.parse_args()
     fake = os.environ.get("BENCH_FAKE") == "1"   # CPU / gloo test of the launcher and harness (tests/test_bench_launcher.py)
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             # nothing in this process has touched a GPU yet (device_count() does not initialise one on this platform)
@@ -1059,6 +1100,9 @@ def main():
             raise SystemExit(f"rank {rank}: LOCAL_RANK {local_rank} but only {torch.cuda.device_count()} GPU(s) visible")
         torch.cuda.set_device(local_rank)
         device = torch.device("cuda", local_rank)
+    # the training step draws t, x0 and the label dropout from torch's default generators, whose start differs from process to
+    # process: seeded, so that the same arguments give the same inputs on every run (--dump-outputs compares builds on them)
+    torch.manual_seed(rank)
     if dist_on:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -1076,7 +1120,10 @@ def main():
         wl = dict(TRAIN_WORKLOADS[args.workload])
         if args.batch:
             wl["B"] = args.batch
-        dt, loss = time_training(wl, args.precision, device, args.steps, max(args.warmup, 1), dist_on, world)
+        outputs = {} if args.dump_outputs else None
+        dt, loss = time_training(wl, args.precision, device, args.steps, max(args.warmup, 1), dist_on, world, outputs=outputs)
+        if outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
         value = world * wl["B"] / (dt / args.steps)
         result = {"metric": "training cells/sec (flow-matching step: forward + backward + gradient all-reduce + AdamW)", "value": value,
                   "unit": "cells/s", "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": max(args.warmup, 1),
@@ -1102,6 +1149,8 @@ def main():
         wl["evals"] = args.evals
     m = make_model(wl, args.precision, device)
     dt, blocks, out, (z2, cond2, scales, B) = time_workload(m, wl, device, args.steps, args.warmup, dist_on, world, rank, time_blocks=True)
+    if args.dump_outputs and rank == 0:   # the final latents of the last timed step ([unconditional | guided] rows; N > 1: all ranks')
+        dump_outputs(args.dump_outputs, {"latents": out})
     ms_per_step = 1e3 * dt / args.steps
     strong = bool(wl.get("strong"))
     cells = wl["B"] if strong else world * B
@@ -1146,14 +1195,15 @@ def main():
             rl["traffic_ratio"] = (traffic / rl["algorithmic_hbm_bytes_per_launch"]) if traffic else None
             result["roofline"] = rl
     note(f"main workload done: {value:.0f} cells/s")
-    if rank == 0 and not fake and "roofline" in result and not args.no_extra:   # (--no-extra: profiling runs keep their kernel list clean)
+    full = args.full   # everything below this point but the JSON line is --full only
+    if full and rank == 0 and not fake and "roofline" in result and not args.no_extra:   # (--no-extra: profiling runs keep their kernel list clean)
         try:
             ceil = mfma_ceiling_record()
             result["mfma_sustained_ceiling"] = ceil
             result["roofline"]["frac_of_sustained_normal"] = result["roofline"]["achieved"] / ceil["normal_tflops"]
         except Exception as e:   # a measurement aid: never takes the headline line down
             result["mfma_sustained_ceiling"] = {"error": repr(e)}
-    if rank == 0 and not dist_on and not fake:
+    if full and rank == 0 and not dist_on and not fake:
         if not args.no_extra:
             if args.precision != "bf16x3":
                 result["parity_path"] = precision_path(wl, device, "bf16x3", args.steps, args.warmup)
@@ -1308,9 +1358,10 @@ def main():
             note("cpu baseline done")
     if dist_on:
         result["per_rank_ms_per_step"] = [1e3 * v / args.steps for v in getattr(time_workload, "per_rank_s", [])]
+    if full and dist_on:
         result["allgather_ms"] = 1e3 * time_allgather(out, B, device, world)
         result["cross_rank_check"] = cross_rank_check(m, wl, out, B, device, world, rank)
-    if dist_on and not args.no_extra and args.workload == "dentate_b4096_euler100":
+    if full and dist_on and not args.no_extra and args.workload == "dentate_b4096_euler100":
         # N > 1: the strong-scaling leg north_star names (parse1m, 8192 cells global = 8192 / N per GPU), every rank takes part
         w2 = dict(WORKLOADS["parse1m_b8192_euler100_strong"])
         if args.global_cells:

@@ -16,7 +16,7 @@ def _run(args, env_extra, timeout=300):
 
 
 def test_gpus_2_launches_two_ranks_and_gathers():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64"], {"BENCH_FAKE": "1"})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--full"], {"BENCH_FAKE": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -33,13 +33,13 @@ def test_gpus_2_launches_two_ranks_and_gathers():
 
 def test_cross_rank_check_catches_a_rank_that_ran_something_else():
     """BENCH_FAKE_CORRUPT_RANK=1: rank 1's stand-in sampler is perturbed - the self-check must fail the job loudly."""
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "16"], {"BENCH_FAKE": "1", "BENCH_FAKE_CORRUPT_RANK": "1"})
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "16", "--full"], {"BENCH_FAKE": "1", "BENCH_FAKE_CORRUPT_RANK": "1"})
     assert r.returncode != 0
     assert "cross-rank self-check FAILED" in (r.stderr + r.stdout)
 
 
 def test_strong_scaling_leg_splits_the_global_batch():
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"BENCH_FAKE": "1"})
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], {"BENCH_FAKE": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     s = j["strong_scaling"]
@@ -66,7 +66,7 @@ def test_world_size_mismatch_fails_loudly():
 
 
 def _strong(extra):
-    r = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--batch", "16", *extra], {"BENCH_FAKE": "1"}, timeout=600)
+    r = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--batch", "16", "--full", *extra], {"BENCH_FAKE": "1"}, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 8 and j["rccl_ranks"] == 8 and len(j["per_rank_ms_per_step"]) == 8 and j["allgather_ms"] >= 0
@@ -127,3 +127,74 @@ def test_rank_binds_its_device_before_anything_creates_a_handle(monkeypatch):
         raise AssertionError("expected SystemExit")
     except SystemExit as e:
         assert "LOCAL_RANK 9" in str(e) and not order
+
+
+def _bench_in_process(monkeypatch, argv):
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_FORCE_DIST", "BENCH_FAKE_CORRUPT_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("BENCH_FAKE", "1")
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench
+
+
+def test_steps_sets_the_number_of_timed_steps(monkeypatch, capsys):
+    """`--steps K --warmup W` runs exactly W + K sampling passes, and the line reports K and the milliseconds of one timed step."""
+    bench = _bench_in_process(monkeypatch, ["--steps", "4", "--warmup", "2", "--batch", "8"])
+    calls = []
+    solve = bench.FakeSampler.sample_ode_cfg
+    monkeypatch.setattr(bench.FakeSampler, "sample_ode_cfg", lambda self, *a: calls.append(1) or solve(self, *a))
+    bench.main()
+    j = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
+    assert len(calls) == 6
+    assert j["steps"] == 4 and j["warmup"] == 2 and j["ms_per_step"] > 0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in j
+
+
+def test_plain_multi_rank_run_leaves_the_full_records_out():
+    """Without --full the N > 1 extras (all-gather timing, cross-rank self-check, strong-scaling leg) are not run."""
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16"], {"BENCH_FAKE": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and len(j["per_rank_ms_per_step"]) == 2
+    assert not {"allgather_ms", "cross_rank_check", "strong_scaling"} & set(j)
+
+
+def test_dump_outputs_writes_the_last_steps_latents_the_same_on_every_run(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run(["--steps", "2", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d)], {"BENCH_FAKE": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(p.name for p in d.iterdir()) == ["latents.npy"]
+        runs.append(np.load(d / "latents.npy"))
+    assert runs[0].dtype == np.float32 and runs[0].shape == (16, 16, 16)
+    assert np.array_equal(runs[0], runs[1])
+    # what the stand-in sampler returns for bench's seeded inputs: the dump is the timed path's own result
+    wl = dict(bench.WORKLOADS["dentate_b4096_euler100"], B=8)
+    z2, cond2, _ = bench.make_inputs(wl, 8, "cpu", seed=1234)
+    assert np.array_equal(runs[0], (z2 * 2.0 + cond2["clusters"].float().view(-1, 1, 1)).numpy())
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_rows_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 + 10 * 16)   # the float64 loss, then 10 rows of 4 floats
+    big = torch.arange(400, dtype=torch.float32).reshape(100, 4)
+    got = []
+    for i in range(2):
+        bench.dump_outputs(str(tmp_path / str(i)), {"rows": big, "loss": torch.tensor([1.5], dtype=torch.float64)})
+        got.append(np.load(tmp_path / str(i) / "rows.npy"))
+        assert np.load(tmp_path / str(i) / "loss.npy").dtype == np.float64
+    a = got[0]
+    assert a.shape == (10, 4) and a.dtype == np.float32 and np.array_equal(a, got[1])
+    first = a[:, 0] / 4
+    assert np.all(np.diff(first) > 0) and np.array_equal(a, big.numpy()[first.astype(int)])

@@ -5,11 +5,11 @@ tag=${1:-r3}
 cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 mkdir -p gpurun_out
 o=gpurun_out/$tag
-timeout 1500 python bench.py --steps 20 --warmup 5 > ${o}_bench_default.json 2> ${o}_bench_default.err; tail -c 600 ${o}_bench_default.json; echo; cp profiles/bench_last.json ${o}_bench_default_details.json 2>/dev/null
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > ${o}_bench_default.json 2> ${o}_bench_default.err; tail -c 600 ${o}_bench_default.json; echo; cp profiles/bench_last.json ${o}_bench_default_details.json 2>/dev/null
 timeout 300 python bench.py --precision fp16 --steps 20 --warmup 5 --no-extra --no-cpu-baseline > ${o}_bench_fp16.json 2>/dev/null
 timeout 300 python bench.py --precision bf16x3 --steps 10 --warmup 2 --no-extra --no-cpu-baseline > ${o}_bench_bf16x3.json 2>/dev/null
 timeout 300 python bench.py --precision fp32 --steps 1 --no-extra --no-cpu-baseline > ${o}_bench_fp32.json 2>/dev/null
-BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 1 --no-extra --no-cpu-baseline > ${o}_bench_rccl_world1.json 2>/dev/null
+BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --steps 1 --no-extra --no-cpu-baseline > ${o}_bench_rccl_world1.json 2>/dev/null
 timeout 300 python bench.py --workload replogle_train_ditl_b1024 --steps 4 --warmup 2 > ${o}_bench_replogle_train_ditl_b1024.json 2>/dev/null
 ROCPROF_ROWS=12 bash tools/rocprof_stats.sh ${tag}_stats_bench bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra > ${o}_bench_kernel_stats.txt 2>&1
 ROCPROF_ROWS=12 bash tools/rocprof_stats.sh ${tag}_stats_bench_fp16 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra --precision fp16 > ${o}_bench_fp16_kernel_stats.txt 2>&1

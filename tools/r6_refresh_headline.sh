@@ -16,6 +16,6 @@ bash tools/rocprof_pmc.sh ${tag}_pmc4 "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" $K t
 python3 tools/pmc_summary.py $tag 8 > /dev/null 2>&1
 cp profiles/pmc_dit_forward_kernel.json gpurun_out/${tag}_pmc_dit_forward_kernel.json
 ROCPROF_ROWS=12 bash tools/rocprof_stats.sh ${tag}_stats_bench bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra > ${o}_bench_kernel_stats.txt 2>&1
-timeout 1500 python bench.py --steps 20 --warmup 5 > ${o}_bench_default.json 2> ${o}_bench_default.err; cp profiles/bench_last.json ${o}_bench_default_details.json
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > ${o}_bench_default.json 2> ${o}_bench_default.err; cp profiles/bench_last.json ${o}_bench_default_details.json
 timeout 300 python bench.py --precision fp16 --steps 20 --warmup 5 --no-extra --no-cpu-baseline > ${o}_bench_fp16.json 2>/dev/null
 tail -c 400 ${o}_bench_default.json
