@@ -89,6 +89,7 @@ extern "C" int scldm_dit_create(const scldm_dit_config* cfg, scldm_dit** out) {
     return SCLDM_OK;
   }
   // run-time knobs are read ONCE, here (they select kernel shapes and therefore which weight streams exist)
+  if (const char* e = getenv("SCLDM_FWD_MFMA")) h->fwd_m16 = atoi(e) != 32;
   if (const char* e = getenv("SCLDM_FT")) h->force_ft = atoi(e);
   if (const char* e = getenv("SCLDM_X3_FT")) h->force_x3_ft = atoi(e);
   if (const char* e = getenv("SCLDM_X3_NTT")) h->force_x3_ntt = atoi(e);
@@ -303,7 +304,8 @@ int scldm_build_pack_tables(scldm_dit* h, const scldm_dit_weights* w, hipStream_
         const int nc = h->n_chunks[f], hf = h->half[f];
         const long long npk = (long long)4 * units_per_layer(nc, hf) * 1024;
         train = (p == SCLDM_PREC_BF16 || p == SCLDM_PREC_FP16) && f == 1;   // (the training launch masks the precision it runs in)
-        add(kPackLayer, npk, {w->attn_w[i], w->proj_w[i], w->w1[i], w->w2[i], w->cproj[i]}, h->stream[p][f], {H, nc, hf, f + 1, p}, npk * i);
+        const int m16 = h->fwd_m16 && f == 1 && (p == SCLDM_PREC_BF16 || p == SCLDM_PREC_FP16);   // = the kernels' M16
+        add(kPackLayer, npk, {w->attn_w[i], w->proj_w[i], w->w1[i], w->w2[i], w->cproj[i]}, h->stream[p][f], {H, nc, hf, f + 1, p, m16}, npk * i);
         train = false;
       }
     if (h->bwd_stream) {
@@ -536,29 +538,35 @@ static int launch_adaln(scldm_dit* h, const float* silu_c, float* mod, int rows,
   return SCLDM_OK;
 }
 
-template <typename OP, int NTT, int FT>
+template <typename OP, int NTT, int FT, bool M16 = false>
 static int launch_fwd_t(const FwdArgs& a, hipStream_t st) {
   using L = FwdLayout<OP, NTT, FT>;
   static bool attr_set[64] = {};   // the attribute is per device
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    HIP_TRY(hipFuncSetAttribute((const void*)dit_forward_kernel<OP, NTT, FT>, hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void*)dit_forward_kernel<OP, NTT, FT, false, M16>, hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS_BYTES));
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
   const int tiles = cdiv((long long)a.n_fwd * 16, L::TM);
   const int grid = a.grid_tiles > 0 ? a.grid_tiles : tiles;
-  dit_forward_kernel<OP, NTT, FT><<<grid, L::NT, L::LDS_BYTES, st>>>(a);
+  dit_forward_kernel<OP, NTT, FT, false, M16><<<grid, L::NT, L::LDS_BYTES, st>>>(a);
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
 
-static int launch_fwd(int prec, int ntt, int ft, const FwdArgs& a, hipStream_t st) {
+// m16: the handle's fwd_m16 (the stream was packed for it); it selects the bf16 / fp16 FT=2 instantiations only
+static int launch_fwd(int prec, int ntt, int ft, bool m16, const FwdArgs& a, hipStream_t st) {
   if (prec == SCLDM_PREC_FP32) return launch_fwd_t<OpF32, 2, 2>(a, st);
   if (prec == SCLDM_PREC_BF16X3)
     return ft == 1 ? launch_fwd_t<OpBF16x3, 2, 1>(a, st) : ntt == 1 ? launch_fwd_t<OpBF16x3, 1, 2>(a, st) : launch_fwd_t<OpBF16x3, 2, 2>(a, st);
-  if (prec == SCLDM_PREC_FP16) return ft == 1 ? launch_fwd_t<OpFP16, 2, 1>(a, st) : ntt == 1 ? launch_fwd_t<OpFP16, 1, 2>(a, st) : launch_fwd_t<OpFP16, 2, 2>(a, st);
+  if (prec == SCLDM_PREC_FP16) {
+    if (ft == 1) return launch_fwd_t<OpFP16, 2, 1>(a, st);
+    if (m16) return ntt == 1 ? launch_fwd_t<OpFP16, 1, 2, true>(a, st) : launch_fwd_t<OpFP16, 2, 2, true>(a, st);
+    return ntt == 1 ? launch_fwd_t<OpFP16, 1, 2>(a, st) : launch_fwd_t<OpFP16, 2, 2>(a, st);
+  }
   if (ft == 1) return launch_fwd_t<OpBF16, 2, 1>(a, st);
+  if (m16) return ntt == 1 ? launch_fwd_t<OpBF16, 1, 2, true>(a, st) : launch_fwd_t<OpBF16, 2, 2, true>(a, st);
   return ntt == 1 ? launch_fwd_t<OpBF16, 1, 2>(a, st) : launch_fwd_t<OpBF16, 2, 2>(a, st);
 }
 
@@ -673,12 +681,12 @@ static int trunk(scldm_dit* h, const float* x, int n_direct, int rep, int n_fwd,
         HIP_TRY(hipStreamWaitEvent(h->side[0], h->fork_ev, 0));
         a.tile0 = 0;
         a.grid_tiles = n64;
-        rc = launch_fwd(prec, 2, ft, a, st);
+        rc = launch_fwd(prec, 2, ft, h->fwd_m16, a, st);
         s1 = h->side[0];
       }
       a.tile0 = 2 * n64;
       a.grid_tiles = n32;
-      if (rc == SCLDM_OK) rc = launch_fwd(prec, 1, ft, a, s1);
+      if (rc == SCLDM_OK) rc = launch_fwd(prec, 1, ft, h->fwd_m16, a, s1);
       if (n64 > 0) {
         HIP_TRY(hipEventRecord(h->join_ev[0], h->side[0]));
         HIP_TRY(hipStreamWaitEvent(st, h->join_ev[0], 0));
@@ -692,7 +700,7 @@ static int trunk(scldm_dit* h, const float* x, int n_direct, int rep, int n_fwd,
           a.tile0 = gt0[g];
           a.grid_tiles = gt0[g + 1] - gt0[g];
         }
-        rc = launch_fwd(prec, ntt, ft, a, sg);
+        rc = launch_fwd(prec, ntt, ft, h->fwd_m16, a, sg);
       }
     if (rc != SCLDM_OK) return rc;
     if (e1) HIP_TRY(hipEventRecord(e1, st));

@@ -91,6 +91,11 @@ struct OpBF16 {
   static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
+  // 16x16 tile over 32 k-values (the SwiGLU up-projection pass, dit_forward.hpp: gemm_pass_tile16):
+  //   A / B operand: lane l holds 8 k-values 8 (l >> 4)..+7 of row / col (l & 15);  C/D: lane l holds col (l & 15), rows 4 (l >> 4)..+3
+  static __device__ __forceinline__ f32x4 mma16(const Frag& a, const Frag& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
   // SwiGLU with the w1 rows packed times -log2(e) and the w2 rows times -1/log2(e) (kW1Scale / kW2Scale, applied by the weight
   // packer): the up-projection delivers a' = -log2(e) a and b' = -b / log2(e), so silu(a) b = a' b' / (1 + 2^a') - one multiply less
   static constexpr float kW1Scale = -1.4426950408889634f, kW2Scale = -0.6931471805599453f;
@@ -146,6 +151,9 @@ struct OpFP16 {
   static constexpr int kMmaOps = 1;          // MFMA instructions per mma()
   static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x4 mma16(const Frag& a, const Frag& b, f32x4 c) {   // layout: OpBF16::mma16
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
   // SwiGLU with the w1 rows packed times -log2(e) and the w2 rows times -1/log2(e) (kW1Scale / kW2Scale, applied by the weight
   // packer): the up-projection delivers a' = -log2(e) a and b' = -b / log2(e), so silu(a) b = a' b' / (1 + 2^a') - one multiply less

@@ -16,13 +16,16 @@ namespace scldm {
 //   chunk c, units 0-15: tile rows 0-15 = w1[hid], rows 16-31 = w2[hid], hid = c*128 + w*32 + ft*16 + (r&15)
 //   chunk c, units 16-23: mlp.c_proj rows w*64 + ft*32 + r, k = hidden index c*128 + ks*16 + ...
 // Hidden indices >= H are zero (exact padding of 684 -> 768).
+// m16 (FT=2, 16-bit policies; dit_forward.hpp: gemm_pass_tile16): the W12 units of a chunk (and of the trailing half chunk) are
+// 16-row x 32-k fragments instead - unit vv = k-step (vv & 7) of 32 of tile vv >> 3, fragment 0 = w1[hid], fragment 1 = w2[hid],
+// hid = c*128 + (w*2 + tile)*16 + (l&15), k = 32*(vv & 7) + (l>>4)*8 + j.  Same units, same bytes; every other unit is unchanged.
 // ------------------------------------------------------------------------------------------------
 // One element of a layer's packed stream (index documented above); FT = 32-row tiles per wave.
 // s1 / s2: factors applied to the w1 / w2 rows (OP::kW1Scale / kW2Scale of the stream's precision policy)
 __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, const float* __restrict__ Wproj,
                                                 const float* __restrict__ W1, const float* __restrict__ W2,
                                                 const float* __restrict__ Wcp, long long idx, int H, int n_chunks, int half, int FT,
-                                                float s1, float s2) {
+                                                float s1, float s2, bool m16 = false) {
   // FT = 32-row tiles per wave (2: four waves, 1: eight waves); a unit holds FT fragments of 512 elements
   const int UL = units_per_layer(n_chunks, half), unit_elems = 512 * FT;
   const int j = idx & 7, l = (idx >> 3) & 63, ft = (int)((idx >> 9) % FT);
@@ -44,7 +47,10 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
   } else if (u >= 64 + n_chunks * kUnitsPerChunk) {
     // trailing half chunk (FT=2): 64 hidden units, wave w owns 16 of them in ONE tile; then a K=64 c_proj pass
     const int vh = u - 64 - n_chunks * kUnitsPerChunk, hid0 = n_chunks * kHC;
-    if (vh < 8) {
+    if (vh < 8 && m16) {
+      const int hid = hid0 + w * 16 + (l & 15);
+      val = (hid < H) ? (ft == 0 ? W1 : W2)[(size_t)hid * 256 + vh * 32 + (l >> 4) * 8 + j] * (ft == 0 ? s1 : s2) : 0.f;
+    } else if (vh < 8) {
       const int ks = 2 * vh + ft, hid = hid0 + w * 16 + (r & 15);
       const float* src = (r < 16) ? W1 : W2;
       val = (hid < H) ? src[(size_t)hid * 256 + ks * 16 + k8] * ((r < 16) ? s1 : s2) : 0.f;
@@ -54,7 +60,10 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
     }
   } else {
     const int v = u - 64, c = v / kUnitsPerChunk, vv = v % kUnitsPerChunk;
-    if (vv < 16) {
+    if (vv < 16 && m16) {
+      const int hid = c * kHC + (w * 2 + (vv >> 3)) * 16 + (l & 15);
+      val = (hid < H) ? (ft == 0 ? W1 : W2)[(size_t)hid * 256 + (vv & 7) * 32 + (l >> 4) * 8 + j] * (ft == 0 ? s1 : s2) : 0.f;
+    } else if (vv < 16) {
       // FT=2: units 0-7 = tile 0, units 8-15 = tile 1, each unit = k-steps (2j, 2j+1) of that tile (gemm_pass_tile)
       // (SCLDM_W12_PAIR: unit vv = k-step vv of BOTH tiles, an ordinary two-tile gemm_pass)
       const int tile = (FT == 2 && !SCLDM_W12_PAIR) ? (vv >> 3) : ft;
@@ -192,7 +201,7 @@ struct PackJob {
   long long n;          // elements (pack_job_threads(kind, n, p) threads: layer streams take a lane fragment of 8 per thread)
   const float* s[5];    // sources (parameter tensors)
   void* d;              // destination
-  int p[6];             // kind-specific: copy -; transpose N,K,ldo,col0; layer H,n_chunks,half,FT,prec; final din,prec
+  int p[6];             // kind-specific: copy -; transpose N,K,ldo,col0; layer H,n_chunks,half,FT,prec,m16; final din,prec
   long long d_off;      // element offset added to the destination index (layer: start of the layer's stream)
 };
 // threads a job needs: the layer streams (forward and backward) handle one lane fragment = 8 consecutive elements per thread; a
@@ -265,7 +274,8 @@ __global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* __restric
         const float s1 = (j.p[4] == 1 || j.p[4] == 3) ? OpBF16::kW1Scale : 1.0f, s2 = (j.p[4] == 1 || j.p[4] == 3) ? OpBF16::kW2Scale : 1.0f;
         float v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = pack_layer_val(j.s[0], j.s[1], j.s[2], j.s[3], j.s[4], idx * 8 + e, j.p[0], j.p[1], j.p[2], j.p[3], s1, s2);
+        for (int e = 0; e < 8; ++e) v[e] = pack_layer_val(j.s[0], j.s[1], j.s[2], j.s[3], j.s[4], idx * 8 + e, j.p[0], j.p[1], j.p[2], j.p[3], s1, s2,
+                                                        j.p[3] == 2 && j.p[5] != 0);
         pack_store8(j.d, j.d_off / 8 + idx, v, j.p[4], fp16_stats);
       }
       break;

@@ -424,6 +424,62 @@ __device__ __forceinline__ void gemm_pass_tile(f32x16 (&acc)[NTT], WStream<OP, P
 #endif
 }
 
+// The same up-projection pass on 16x16 tiles (v_mfma_f32_16x16x32, the 16-bit policies' mma16): a unit is ONE 32-k step of the
+// tile, fragment 0 = its 16 w1 rows, fragment 1 = the 16 w2 rows of the same hidden units (pack_layer_val, m16), so a1[j] and b1[j]
+// hold a and b of the same (hidden unit, token) in the same lane and register: SwiGLU stays in-lane.  j = token tile of 16.
+// Same weight bytes, LDS fragment reads and MFMA cycles per pass as gemm_pass_tile; the chip holds a higher clock on this
+// shape under its power budget (profiles/r7_mfma_shape_probe.txt).
+template <typename OP, int NTT, int PF>
+__device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b1)[2 * NTT], WStream<OP, PF, 2>& ws,
+                                                 const typename OP::E* __restrict__ bsm, int ldb, int lane) {
+  using Frag = typename OP::Frag;
+  constexpr int UNITS = 8, NJ = 2 * NTT;
+  static_assert(UNITS % PF == 0, "8 units must be a multiple of the prefetch depth");
+  const typename OP::E* bbase = bsm + (lane & 15) * ldb + (lane >> 4) * 8;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  Frag bcur[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) bcur[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb);
+  // Per unit, token tile by token tile: the two MFMAs of tile j, then the read of tile j's fragment for the next unit into the
+  // registers they just consumed.  (All NJ reads ahead of the MFMAs, as gemm_pass does it, holds NJ more fragments live: 16 VGPRs,
+  // and the <OpBF16, 2, 2> kernel spills 20.)
+  auto unit = [&](int u, int s, bool first) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      a1[j] = OP::mma16(ws.ring[s][0], bcur[j], first ? zero : a1[j]);
+      b1[j] = OP::mma16(ws.ring[s][1], bcur[j], first ? zero : b1[j]);
+      // after the last unit: unit 0 again, never used (the read stays inside the row)
+      bcur[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb + ((u + 1) & (UNITS - 1)) * 32);
+    }
+#if !(SCLDM_PROXY & 1)
+    ws.ring[s][0] = ws.fetch(0);
+    ws.ring[s][1] = ws.fetch(1);
+#endif
+    ws.advance(2);
+    if (OP::kPin) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                  // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, OP::kFragLoads, 0);     // DS read
+      }
+      __builtin_amdgcn_sched_group_barrier(0x020, 2 * OP::kFragLoads, 0);   // VMEM read
+    }
+  };
+#if SCLDM_SETPRIO
+  __builtin_amdgcn_s_setprio(SCLDM_SETPRIO);
+#endif
+#pragma unroll
+  for (int s = 0; s < PF; ++s) unit(s, s, s == 0);
+#pragma unroll 1
+  for (int u0 = PF; u0 < UNITS; u0 += PF) {
+#pragma unroll
+    for (int s = 0; s < PF; ++s) unit(u0 + s, s, false);
+  }
+#if SCLDM_SETPRIO
+  __builtin_amdgcn_s_setprio(0);
+#endif
+}
+
 #ifdef SCLDM_PHASE_TIMING
 #define SCLDM_LN_STAMP(i)                                                                              \
   do {                                                                                                 \
@@ -578,8 +634,11 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
 #ifndef SCLDM_FWD_ONE_WG
 #define SCLDM_FWD_ONE_WG 0    // experiment builds: 1 = compile every instantiation for ONE wave per SIMD (up to 512 registers: room for -DSCLDM_PF=8 -DSCLDM_W12_PAIR=1)
 #endif
-template <typename OP, int NTT, int FT, bool REC = false>
+// M16 (16-bit policies, FT = 2): the SwiGLU up-projection runs on 16x16 tiles (gemm_pass_tile16) from a stream packed for it
+// (pack_layer_val, m16); every other pass, the residual and the record stay on 32x32 tiles.  SCLDM_FWD_MFMA=32 selects M16 = false.
+template <typename OP, int NTT, int FT, bool REC = false, bool M16 = false>
 __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG && NTT <= 2) || NTT == 1)) ? 2 : 1) void dit_forward_kernel(const FwdArgs a) {
+  static_assert(!M16 || (FT == 2 && sizeof(typename OP::E) == 2 && sizeof(typename OP::Frag) == 16), "M16: 16-bit policies, FT = 2");
   using L = FwdLayout<OP, NTT, FT>;
   using E = typename OP::E;
   using Frag = typename OP::Frag;
@@ -1104,7 +1163,20 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
           out[tt][q] = OP::pack4(h[0], h[1], h[2], h[3]);
         }
     };
-    if constexpr (FT == 2) {
+    // M16: the SwiGLU output of 16-token tile j, 4 hidden units per lane (see the store below)
+    Quad hq16[M16 ? TILES : 1][M16 ? 2 * NTT : 1];
+    if constexpr (M16) {
+      static_assert(HALF || !kPair, "M16: one-tile up-projection passes");
+#pragma unroll
+      for (int ft = 0; ft < TILES; ++ft) {
+        f32x4 a1[2 * NTT], b1[2 * NTT];
+        gemm_pass_tile16<OP, NTT, PF>(a1, b1, ws, XA, L::XA_LD, lane);
+#pragma unroll
+        for (int j = 0; j < 2 * NTT; ++j)
+          hq16[ft][j] = OP::pack4(OP::swiglu(a1[j][0], b1[j][0]), OP::swiglu(a1[j][1], b1[j][1]), OP::swiglu(a1[j][2], b1[j][2]),
+                                  OP::swiglu(a1[j][3], b1[j][3]));
+      }
+    } else if constexpr (FT == 2) {
       if constexpr (HALF || !kPair) {
 #pragma unroll
         for (int ft = 0; ft < TILES; ++ft) {
@@ -1127,6 +1199,13 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
 #pragma unroll
     for (int ft = 0; ft < TILES; ++ft) {
       const int col0 = HALF ? wave * 16 : (wave * FT + ft) * 16;
+      if constexpr (M16) {
+        // lane l: token 16 j + (l & 15), hidden units col0 + 4 (l >> 4)..+3 - one 8-byte store; a 16-lane group covers 16 rows
+        // at the same column (row stride 68 dwords: banks 4i..4i+1, +2 for the next group), conflict-free
+#pragma unroll
+        for (int j = 0; j < 2 * NTT; ++j) OP::store_quad(HBc + (j * 16 + (lane & 15)) * L::HB_LD, col0 + (lane >> 4) * 4, hq16[ft][j]);
+        continue;
+      }
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) {
 #if SCLDM_PAIR_STORE

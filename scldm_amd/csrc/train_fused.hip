@@ -733,15 +733,21 @@ int forward(scldm_dit* h, const float* x, const float* mod, int n, float* out, c
   static const bool small_ok = [] { const char* e = getenv("SCLDM_TRAIN_SMALL_NTT"); return !(e && e[0] == '0'); }();
   const int tiles64 = pad4(n) / 4;
   const bool small = small_ok && tiles64 <= 128;
-  void (*kern)(const FwdArgs) = small ? (f16 ? dit_forward_kernel<OpFP16, 1, 2, true> : dit_forward_kernel<OpBF16, 1, 2, true>)
-                                      : (f16 ? dit_forward_kernel<OpFP16, 2, 2, true> : dit_forward_kernel<OpBF16, 2, 2, true>);
+  // the recording instantiations read the same packed stream as the inference ones: the same M16 (h->fwd_m16; the record itself -
+  // residual and branch outputs - is written in the 32x32 layout either way)
+  const bool m16 = h->fwd_m16;
+  void (*kern)(const FwdArgs) =
+      m16 ? (small ? (f16 ? dit_forward_kernel<OpFP16, 1, 2, true, true> : dit_forward_kernel<OpBF16, 1, 2, true, true>)
+                   : (f16 ? dit_forward_kernel<OpFP16, 2, 2, true, true> : dit_forward_kernel<OpBF16, 2, 2, true, true>))
+          : (small ? (f16 ? dit_forward_kernel<OpFP16, 1, 2, true> : dit_forward_kernel<OpBF16, 1, 2, true>)
+                   : (f16 ? dit_forward_kernel<OpFP16, 2, 2, true> : dit_forward_kernel<OpBF16, 2, 2, true>));
   const int lds_bytes = small ? L1::LDS_BYTES : L::LDS_BYTES;
-  static bool attr_set[2][2][64] = {};
+  static bool attr_set[2][2][2][64] = {};
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[small][f16][dev]) {
+  if (dev < 0 || dev >= 64 || !attr_set[m16][small][f16][dev]) {
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    if (dev >= 0 && dev < 64) attr_set[small][f16][dev] = true;
+    if (dev >= 0 && dev < 64) attr_set[m16][small][f16][dev] = true;
   }
   const scldm_dit_config& c = h->cfg;
   if (h->iota_n < n) {   // identity row index, kept on the handle (grown on demand)
