@@ -510,7 +510,7 @@ int scldm_nb_sample(const float* mu, const float* theta, float* out, size_t n, u
 /* ------------------------------------------------------------------------------------------------
  * TransformerVAE TRAINING step (BASELINE configs[0]; the reference trains through torch autograd over
  * TransformerVAE.forward, src/scldm/vae.py:29-56, inside VAE.training_step, src/scldm/models.py:249-290, with the loss
- * -log_nb_positive(counts, mu, theta), models.py:243, src/scldm/distributions.py:6-42).  fp32.
+ * -log_nb_positive(counts, mu, theta), models.py:243, src/scldm/distributions.py:6-42).  fp32 (fp16 operands: the _ex forms below).
  *   forward : (mu, theta, z) = TransformerVAE.forward(counts, genes, library_size, counts_subset, genes_subset) - the inference
  *             kernels - and leaves in `saved` what the backward cannot recompute cheaply (the pooling's attention output and
  *             log-sum-exp) or should not wait for (the decoder's per-cell K | V); `ws` need not survive the call; uses the packed weights of the last scldm_vae_load_weights (call it after every optimiser step).
@@ -528,6 +528,24 @@ int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scl
                              const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
                              const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta, const float* dz,
                              void* saved, void* ws, void* stream);
+
+/* The same step with an operand policy (`precision`): SCLDM_PREC_FP32 = the two calls above; SCLDM_PREC_FP16 = the reference's TF32
+ * class (set_float32_matmul_precision("high")): fp16 operands rounded to nearest even, fp32 accumulation, in the encoder pooling and
+ * the per-gene decoder forward and in every contraction of the per-gene chain backward; the two 16-token trunks, the pooling backward,
+ * LayerNorms, softmax, the SwiGLU gradient and the NB head stay fp32.  Forward and backward of one step take the same value; any
+ * other value returns SCLDM_ERR_SHAPE.  fp16 needs the default kernel generations (SCLDM_ERR_STATE if SCLDM_VAE_GENE_MFMA,
+ * SCLDM_VAE_GENE_WIDE or SCLDM_VAE_CELL_WIDE selects an earlier one).  The fp16 backward scales each cell's logit gradient by a power of
+ * two (max |2^e dlogit| in [1024, 2048)) before rounding and its results back by 2^-e (exact), and - if the caller registered one with
+ * scldm_vae_train_set_found_inf - sets a device float to 1.0 when the per-gene backward produced a non-finite gradient (reset to 0.0
+ * at the start of every fp16 backward): an optimizer that takes GradScaler's `found_inf` skips the step on device. */
+int scldm_vae_train_forward_ex(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S, const int64_t* genes,
+                               const float* library_size, int G, float* mu, float* theta, float* z, void* saved, void* ws, int precision,
+                               void* stream);
+int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
+                                const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
+                                const float* dz, void* saved, void* ws, int precision, void* stream);
+int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf /* device, caller-owned, may be NULL */);
 
 /* log_nb_positive (src/scldm/distributions.py:6-42) elementwise over n values, and its gradient w.r.t. mu and theta given the
  * upstream gradient of the log-likelihood (either output may be NULL):

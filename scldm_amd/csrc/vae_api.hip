@@ -267,11 +267,14 @@ extern "C" size_t scldm_vae_workspace_bytes(const scldm_vae* h, int B, int G) {
 }
 
 int scldm_vae_encode_ex(scldm_vae* h, const float* counts, const int64_t* genes, int B, int S, float* z, int precision, float* pooled,
-                        float* lse2, hipStream_t st) {
+                        float* lse2, hipStream_t st, int cell_precision) {
   int rc = vae_ready(h);
   if (rc) return rc;
   if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_BF16 && precision != SCLDM_PREC_FP16)
     return fail(SCLDM_ERR_SHAPE, "unsupported MCAB precision %d (fp32, bf16, fp16)", precision);
+  const int cprec = cell_precision < 0 ? precision : cell_precision;
+  if (cprec != SCLDM_PREC_FP32 && cprec != SCLDM_PREC_BF16 && cprec != SCLDM_PREC_FP16)
+    return fail(SCLDM_ERR_SHAPE, "unsupported trunk precision %d (fp32, bf16, fp16)", cprec);
   if (B <= 0 || S <= 0 || !counts || !genes || !z || !pooled) return fail(SCLDM_ERR_SHAPE, "bad argument");
   const scldm_vae_config& c = h->cfg;
   EncPoolArgs p;
@@ -302,8 +305,8 @@ int scldm_vae_encode_ex(scldm_vae* h, const float* counts, const int64_t* genes,
   e.B = B; e.n_lat = c.n_embed_latent; e.n_layer = c.n_layer; e.eps = c.layernorm_eps;
   {
     KernelTimer kt(h, SCLDM_VAE_K_ENC_CELL, st);
-    if (precision == SCLDM_PREC_FP16) enc_cell_kernel<OpFP16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(e);
-    else if (precision == SCLDM_PREC_BF16) enc_cell_kernel<OpBF16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(e);
+    if (cprec == SCLDM_PREC_FP16) enc_cell_kernel<OpFP16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(e);
+    else if (cprec == SCLDM_PREC_BF16) enc_cell_kernel<OpBF16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(e);
     else enc_cell_kernel<OpF32><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(e);
   }
   LAUNCH_CHECK();
@@ -317,8 +320,30 @@ extern "C" int scldm_vae_encode(scldm_vae* h, const float* counts, const int64_t
   return scldm_vae_encode_ex(h, counts, genes, B, S, z, precision, (float*)ws_, nullptr, (hipStream_t)stream_);
 }
 
+// plain (B, 16, 64) K | V -> the MFMA A-operand fragments that dec_cell_kernel writes for the 16-bit policies (same element order)
+__global__ __launch_bounds__(64) void dec_kv_frag_kernel(const float* __restrict__ plain, float* __restrict__ frag) {
+  const int lane = threadIdx.x, row = lane & 31, hh = lane >> 5;
+  const float* Sc = plain + (size_t)blockIdx.x * (kNI * 64);
+  float* out = frag + (size_t)blockIdx.x * 48 * 64;
+  for (int t = 0; t < 2; ++t)
+    for (int jj = 0; jj < 8; ++jj) {
+      const int hl = row >> 4, key = row & 15, k = acc_row(8 * t + jj, hh);
+      const int j = t * 8 + jj;
+      out[((j >> 2) * 64 + lane) * 4 + (j & 3)] = ((k >> 3) == 2 * t + hl) ? Sc[key * 64 + k] : 0.f;
+    }
+  for (int t = 0; t < 2; ++t)
+    for (int r = 0; r < 16; ++r) {
+      const int rr = acc_row(r, hh), hl = rr >> 4, key = rr & 15;
+      const int j = 16 + t * 16 + r;
+      out[((j >> 2) * 64 + lane) * 4 + (j & 3)] = ((row >> 3) == 2 * t + hl) ? Sc[key * 64 + 32 + row] : 0.f;
+    }
+}
+
+// kv_plain != nullptr (fp16 training forward): the cell pair kernel runs exact fp32 and writes plain K | V there; the fragments of the
+// 16-bit per-gene kernel are packed from it
 static int vae_decode_impl(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G, float* mu,
-                           float* theta, bool draw, unsigned long long seed, int precision, void* ws_, void* stream_) {
+                           float* theta, bool draw, unsigned long long seed, int precision, void* ws_, void* stream_,
+                           float* kv_plain = nullptr) {
   int rc = vae_ready(h);
   if (rc) return rc;
   if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_BF16 && precision != SCLDM_PREC_FP16)
@@ -332,7 +357,16 @@ static int vae_decode_impl(scldm_vae* h, const float* z, const int64_t* genes, c
   d.z = z; d.lat_frag = h->frag_cell + F_DEC_LAT; d.trunk = h->dec_trunk;
   d.ca_ln1_w = h->small + S_DEC_LN1W; d.ca_ln1_b = h->small + S_DEC_LN1B; d.kv_frag = h->frag_cell + F_DEC_KV;
   d.kvfrag = kv; d.B = B; d.n_lat = c.n_embed_latent; d.n_layer = c.n_layer; d.eps = c.layernorm_eps;
-  {
+  if (kv_plain) {
+    if (precision == SCLDM_PREC_FP32) return fail(SCLDM_ERR_SHAPE, "plain K | V output is for the 16-bit per-gene policies");
+    d.kvfrag = kv_plain;
+    {
+      KernelTimer kt(h, SCLDM_VAE_K_DEC_CELL, st);
+      dec_cell_kernel<OpF32><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
+    }
+    LAUNCH_CHECK();
+    dec_kv_frag_kernel<<<B, 64, 0, st>>>(kv_plain, kv);
+  } else {
     KernelTimer kt(h, SCLDM_VAE_K_DEC_CELL, st);
     if (precision == SCLDM_PREC_FP16) dec_cell_kernel<OpFP16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
     else if (precision == SCLDM_PREC_BF16) dec_cell_kernel<OpBF16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
@@ -368,6 +402,12 @@ static int vae_decode_impl(scldm_vae* h, const float* z, const int64_t* genes, c
 extern "C" int scldm_vae_decode(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G,
                                 float* mu, float* theta, int precision, void* ws_, void* stream_) {
   return vae_decode_impl(h, z, genes, library_size, B, G, mu, theta, false, 0ull, precision, ws_, stream_);
+}
+
+int scldm_vae_decode_train_fp16(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G, float* mu,
+                                float* theta, float* kv_plain, void* ws, hipStream_t st) {
+  if (!kv_plain) return fail(SCLDM_ERR_SHAPE, "bad argument");
+  return vae_decode_impl(h, z, genes, library_size, B, G, mu, theta, false, 0ull, SCLDM_PREC_FP16, ws, st, kv_plain);
 }
 
 extern "C" int scldm_vae_decode_sample(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G,

@@ -33,6 +33,8 @@ struct scldm_vae {
   // beside the per-gene backward (created on first use by scldm_vae_train_backward)
   hipStream_t side;
   hipEvent_t ev_fork, ev_gene, ev_join;
+  // fp16 training backward: caller-owned device float set to 1 on a non-finite per-gene gradient (scldm_vae_train_set_found_inf)
+  float* found_inf;
   // measurement hook (scldm_vae_kernel_timing_enable): HIP event pairs around each MCAB kernel launch, per kernel kind
   bool timing;
   hipEvent_t tev[SCLDM_VAE_KERNEL_KINDS][2 * 64];
@@ -42,5 +44,10 @@ struct scldm_vae {
 // vae_api.hip internals used by the training entry points: TransformerVAE.encode that also leaves the pooling's attention output
 // (B, 16, 32) and the log2-domain log-sum-exp of its scaled scores (B, 4, 16) in caller-provided buffers (either may be NULL)
 int scldm_vae_refresh(scldm_vae* h, bool force, hipStream_t st);
+// cell_precision: operand policy of the 16-token trunk kernel (-1 = `precision`; the fp16 training forward runs the trunks exact)
 int scldm_vae_encode_ex(scldm_vae* h, const float* counts, const int64_t* genes, int B, int S, float* z, int precision, float* pooled,
-                        float* lse2, hipStream_t st);
+                        float* lse2, hipStream_t st, int cell_precision = -1);
+// fp16 training forward of the decoder: the cell pair kernel in exact fp32 writes the cells' plain K | V (B, 16, 64) to kv_plain,
+// which is then packed into the MFMA fragments of the fp16-operand per-gene kernel (in the workspace) - mu / theta as scldm_vae_decode
+int scldm_vae_decode_train_fp16(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G, float* mu,
+                                float* theta, float* kv_plain, void* ws, hipStream_t st);

@@ -248,11 +248,20 @@ __global__ __launch_bounds__(64) void enc_q_bwd_kernel(const float* __restrict__
 //   dlogit_g = mu_g (dmu_g - sum_j dmu_j mu_j / lib) / T ;  dTheta[gene] += dtheta theta (atomic scatter)
 // One workgroup (256 threads) per cell.  dlogit overwrites `dl`; bsum[cell] = sum_g dlogit_g (the head bias gradient's partial).
 // =================================================================================================================================
+// SCALE (fp16 training backward): also records the cell's power of two 2^e with max |2^e dl| in [2^kDlScaleLog2, 2^(kDlScaleLog2 + 1))
+// (1 for an all-zero row) in dl_scale[cell]; the fp16-operand per-gene kernel multiplies dl by it before rounding, and its fp32 outputs
+// by 2^-e.  The gradient operands of the chain are dl times weight-sized factors (d a = dl (Wc^T w_head)_u b sigma'(a), ...: 1e-3 dl
+// at the reference's initialisation), and most genes' dl lie orders of magnitude below the cell's maximum: at [8, 16) they fell into
+// fp16's subnormal range (gradient error 1.7 x the TF32-operand oracle's on vae_train_small); [1024, 2048) keeps them normal and
+// leaves 32 x headroom for d y = dl w_head + ... (|w_head| < 1).  An overflow still sets the found-inf flag.
+constexpr int kDlScaleLog2 = 10;
+template <bool SCALE>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ theta, const float* __restrict__ dmu,
                                                        const float* __restrict__ dtheta, const float* __restrict__ lib,
                                                        const int64_t* __restrict__ genes, int G, float inv_temp, float* __restrict__ dl,
-                                                       float* __restrict__ g_theta, float* __restrict__ bsum) {
+                                                       float* __restrict__ g_theta, float* __restrict__ bsum, float* __restrict__ dl_scale) {
   __shared__ float red[4];
+  __shared__ float amax[4];
   const int cell = blockIdx.x, tid = threadIdx.x;
   const size_t base = (size_t)cell * G;
   float s = 0.f;
@@ -262,11 +271,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   __syncthreads();
   const float sc = (red[0] + red[1] + red[2] + red[3]) / lib[cell];
   __syncthreads();
-  float b = 0.f;
+  float b = 0.f, m = 0.f;
   for (int g = tid; g < G; g += 256) {
     const float d = dmu ? mu[base + g] * (dmu[base + g] - sc) * inv_temp : 0.f;
     dl[base + g] = d;
     b += d;
+    if constexpr (SCALE) m = fmaxf(m, fabsf(d));
     if (dtheta) {
       const float dt = dtheta[base + g] * theta[base + g];
       if (dt != 0.f) atomicAdd(g_theta + genes[base + g], dt);
@@ -274,8 +284,25 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   }
   b = wave_sum(b);
   if ((tid & 63) == 0) red[tid >> 6] = b;
+  if constexpr (SCALE) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) amax[tid >> 6] = m;
+  }
   __syncthreads();
   if (tid == 0) bsum[cell] = red[0] + red[1] + red[2] + red[3];
+  if constexpr (SCALE) {
+    if (tid == 0) {
+      const float mx = fmaxf(fmaxf(amax[0], amax[1]), fmaxf(amax[2], amax[3]));
+      int e = 0;
+      if (mx > 0.f && mx <= 3.4e38f) {      // (a non-finite row keeps 2^0: the gene kernel's outputs then raise the flag)
+        int ex;
+        (void)frexpf(mx, &ex);             // mx = f 2^ex, f in [0.5, 1)  ->  mx 2^(kDlScaleLog2 + 1 - ex) in [2^kDlScaleLog2, 2^(kDlScaleLog2 + 1))
+        e = min(max(kDlScaleLog2 + 1 - ex, -126), 126);
+      }
+      dl_scale[cell] = ldexpf(1.0f, e);
+    }
+  }
 }
 
 // =================================================================================================================================
@@ -299,6 +326,10 @@ struct DecBwdArgs {
   float* dkv_part;         // (B * chunks, 16, 64)
   int G, tiles;
   float eps;
+  // fp16-operand per-gene kernel only (dec_gene_bwd_mfma2_kernel<true>): per-cell power-of-two scale of dl (head_bwd_kernel<true>) and
+  // the caller's found-inf flag (may be null)
+  const float* dl_scale;
+  float* found_inf;
 };
 __global__ __launch_bounds__(64) void dec_gene_bwd_kernel(const DecBwdArgs a) {
   __shared__ __attribute__((aligned(16))) float SA[64 * kSL], SB[64 * kSL], SC[3 * 64 * kSL];

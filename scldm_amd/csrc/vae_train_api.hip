@@ -55,8 +55,26 @@ bool gene_wide() {
   return on;
 }
 
+// SCLDM_VAE_GENE_MFMA: 2 (default): every contraction of the per-gene chain on the matrix pipe; 1: the MLP and the weight gradients
+// only; 0: the VALU form
+int gene_mfma() {
+  static const int v = [] { const char* e = getenv("SCLDM_VAE_GENE_MFMA"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2; }();
+  return v;
+}
+
+// precision of a training step: fp32 (exact), or fp16 (fp16 operands of the per-gene MCAB contractions, forward and backward), which
+// exists for the default kernel generations only
+int check_train_precision(int precision) {
+  if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_FP16)
+    return fail(SCLDM_ERR_SHAPE, "unsupported VAE training precision %d (SCLDM_PREC_FP32 or SCLDM_PREC_FP16)", precision);
+  if (precision == SCLDM_PREC_FP16 && (gene_mfma() != 2 || !gene_wide() || !cell_wide()))
+    return fail(SCLDM_ERR_STATE, "fp16 VAE training needs the default kernel generations: unset SCLDM_VAE_GENE_MFMA, SCLDM_VAE_GENE_WIDE "
+                                 "and SCLDM_VAE_CELL_WIDE (they select earlier fp32-only kernels)");
+  return SCLDM_OK;
+}
+
 struct Ws {
-  float *wct, *Q, *dQ, *xs_enc, *xs_dec, *ysave, *kv, *dl, *dz_dec, *dao, *dgq, *bsum, *p_gene, *p_dkv, *p_dcell, *p_ecell, *p_pool;
+  float *wct, *Q, *dQ, *xs_enc, *xs_dec, *ysave, *kv, *dl, *dz_dec, *dao, *dgq, *bsum, *p_gene, *p_dkv, *p_dcell, *p_ecell, *p_pool, *dl_scale;
   int tilesD, chunksD, tilesE, chunksE, quads, cparts;
   size_t bytes;
 };
@@ -91,6 +109,7 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   w.p_dcell = k.take((size_t)w.cparts * dc_size(L));
   w.p_ecell = k.take((size_t)w.cparts * ec_size(L));
   w.p_pool = k.take((size_t)B * w.chunksE * EP_SIZE);
+  w.dl_scale = k.take((size_t)B);      // fp16: per-cell power of two of dl (head_bwd_kernel<true>)
   w.bytes = k.off;
   return w;
 }
@@ -162,9 +181,17 @@ extern "C" size_t scldm_vae_train_workspace_bytes(const scldm_vae* h, int B, int
   return std::max(carve_ws(h, B, S, G, nullptr).bytes, scldm_vae_workspace_bytes(h, B, G));
 }
 
-extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S,
-                                       const int64_t* genes, const float* library_size, int G, float* mu, float* theta, float* z,
-                                       void* saved_, void* ws, void* stream_) {
+extern "C" int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf) {
+  if (!h) return fail(SCLDM_ERR_SHAPE, "scldm_vae_train_set_found_inf: null handle");
+  h->found_inf = found_inf;
+  return SCLDM_OK;
+}
+
+extern "C" int scldm_vae_train_forward_ex(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S,
+                                          const int64_t* genes, const float* library_size, int G, float* mu, float* theta, float* z,
+                                          void* saved_, void* ws, int precision, void* stream_) {
+  int rc = check_train_precision(precision);
+  if (rc) return rc;
   if (!h || !counts_subset || !genes_subset || !genes || !library_size || !mu || !theta || !z || !saved_ || !ws)
     return fail(SCLDM_ERR_SHAPE, "null argument");
   if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1");
@@ -172,7 +199,14 @@ extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset,
     return fail(SCLDM_ERR_STATE, "the training backward is built for the shared-theta NB head (vae_base.yaml:62); the unshared head decodes only");
   hipStream_t st = (hipStream_t)stream_;
   Saved s = carve_saved(B, saved_);
-  int rc = scldm_vae_encode_ex(h, counts_subset, genes_subset, B, S, z, SCLDM_PREC_FP32, s.pooled, s.lse2, st);
+  if (precision == SCLDM_PREC_FP16) {
+    // fp16 operands in the per-token / per-gene MCAB kernels (pooling, per-gene decoder); the two 16-token trunks stay exact fp32, so
+    // the backward's fp32 recompute of them reproduces the forward.  `saved` receives the cells' plain K | V directly.
+    rc = scldm_vae_encode_ex(h, counts_subset, genes_subset, B, S, z, SCLDM_PREC_FP16, s.pooled, s.lse2, st, SCLDM_PREC_FP32);
+    if (rc) return rc;
+    return scldm_vae_decode_train_fp16(h, z, genes, library_size, B, G, mu, theta, s.kv, ws, st);
+  }
+  rc = scldm_vae_encode_ex(h, counts_subset, genes_subset, B, S, z, SCLDM_PREC_FP32, s.pooled, s.lse2, st);
   if (rc) return rc;
   rc = scldm_vae_decode(h, z, genes, library_size, B, G, mu, theta, SCLDM_PREC_FP32, ws, stream_);
   if (rc) return rc;
@@ -182,12 +216,22 @@ extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset,
   return SCLDM_OK;
 }
 
-extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
-                                        const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
-                                        const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
-                                        const float* dz, void* saved_, void* ws_, void* stream_) {
-  int rc = check_train(h, w, B, S, G);
+extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S,
+                                       const int64_t* genes, const float* library_size, int G, float* mu, float* theta, float* z,
+                                       void* saved_, void* ws, void* stream_) {
+  return scldm_vae_train_forward_ex(h, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, saved_, ws,
+                                    SCLDM_PREC_FP32, stream_);
+}
+
+extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                           const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
+                                           const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
+                                           const float* dz, void* saved_, void* ws_, int precision, void* stream_) {
+  int rc = check_train_precision(precision);
   if (rc) return rc;
+  rc = check_train(h, w, B, S, G);
+  if (rc) return rc;
+  const bool f16 = precision == SCLDM_PREC_FP16;
   if (!g || !counts_subset || !genes_subset || !genes || !library_size || !mu || !theta || !z || !saved_ || !ws_)
     return fail(SCLDM_ERR_SHAPE, "null argument");
   if (!g->gene_embedding || !g->theta) return fail(SCLDM_ERR_SHAPE, "the gene_embedding and theta gradient tables are required");
@@ -201,6 +245,7 @@ extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w
   float* g_theta = const_cast<float*>(g->theta);
   HIP_TRY(hipMemsetAsync(g_emb, 0, (size_t)(c.n_genes + 1) * 32 * 4, st));
   HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
+  if (f16 && h->found_inf) HIP_TRY(hipMemsetAsync(h->found_inf, 0, sizeof(float), st));
 
   // ---- transposed c_proj copies (the streaming SwiGLU reads columns of c_proj as rows): enc cross, dec cross, enc layers, dec layers
   auto wct = [&](int i) { return k.wct + (size_t)i * kHP * 32; };
@@ -234,7 +279,8 @@ extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w
       HIP_TRY(hipFuncSetAttribute((const void*)wide::enc_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::PB_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::G_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
     }
   }
@@ -277,7 +323,8 @@ extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w
   LAUNCH_CHECK();
   if (overlap) HIP_TRY(hipEventRecord(h->ev_join, s2));
   // ---- NB head, then the per-gene decoder chain
-  head_bwd_kernel<<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum);
+  if (f16) head_bwd_kernel<true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, k.dl_scale);
+  else head_bwd_kernel<false><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, nullptr);
   LAUNCH_CHECK();
   DecBwdArgs ga{};
   ga.genes = genes; ga.emb = w->gene_embedding; ga.dl = k.dl; ga.kv = overlap ? sv.kv : k.kv;
@@ -285,9 +332,12 @@ extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w
   ga.ln2_w = w->dec_cross.ln2_w; ga.ln2_b = w->dec_cross.ln2_b; ga.head_w = w->head_w;
   ga.mlp = mlp_of(w->dec_cross.w1, w->dec_cross.w2, wct(1), H);
   ga.g_emb = g_emb; ga.part = k.p_gene; ga.dkv_part = k.p_dkv; ga.G = G; ga.tiles = k.tilesD; ga.eps = eps;
-  // 2 (default): every contraction of the per-gene chain on the matrix pipe; 1: the MLP and the weight gradients only; 0: the VALU form
-  static const int gene_mfma = [] { const char* e = getenv("SCLDM_VAE_GENE_MFMA"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2; }();
-  if (gene_wide() && gene_mfma == 2) wide::dec_gene_bwd_mfma2_kernel<<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+  const int gene_mfma = ::gene_mfma();
+  if (f16) {    // (check_train_precision: the default generations)
+    ga.dl_scale = k.dl_scale;
+    ga.found_inf = h->found_inf;
+    wide::dec_gene_bwd_mfma2_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+  } else if (gene_wide() && gene_mfma == 2) wide::dec_gene_bwd_mfma2_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
   else if (gene_wide() && gene_mfma) wide::dec_gene_bwd_mfma_kernel<<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
   else if (gene_wide()) wide::dec_gene_bwd_kernel<<<dim3(k.chunksD, B), wide::kThreads, wide::G_BYTES, st>>>(ga);
   else dec_gene_bwd_kernel<<<dim3(k.chunksD, B), 64, 0, st>>>(ga);
@@ -373,6 +423,14 @@ extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w
     LAUNCH_CHECK();
   }
   return SCLDM_OK;   // (join_side: `st` waits for the second stream)
+}
+
+extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                        const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
+                                        const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
+                                        const float* dz, void* saved_, void* ws_, void* stream_) {
+  return scldm_vae_train_backward_ex(h, w, g, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, dmu, dtheta, dz,
+                                     saved_, ws_, SCLDM_PREC_FP32, stream_);
 }
 
 extern "C" int scldm_nb_loglik(const float* x, const float* mu, const float* theta, float eps, float* out, size_t n, void* stream_) {

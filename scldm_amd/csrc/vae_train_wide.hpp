@@ -1509,6 +1509,15 @@ __device__ __forceinline__ float row16_max(float v) {   // max over the 16 lanes
 typedef const volatile __attribute__((address_space(3))) f32x2 lds_f32x2;
 __device__ __forceinline__ lds_f32x2* v2(const float* p) { return (lds_f32x2*)p; }
 
+// fp16-operand form (F16, precision "fp16" in training): the k values a lane holds for n consecutive 16 x 16 x 4 fp32 steps of one
+// accumulator are the n consecutive k of ONE 16 x 16 x 16 (n = 4) or 16 x 16 x 32 (n = 8) f16 MFMA - lane (row, g4) holds A[row][n g4 + i]
+// and B[n g4 + i][col] in both - so the same LDS reads feed it, rounded to nearest even in registers (a finite fp32 beyond the fp16
+// range becomes inf: no saturation, the found-inf flag sees it).  Products of two k = 8 head-dim steps pad the f16 operand with zeros.
+__device__ __forceinline__ f16x4 h4(float a, float b, float c, float d) { return f16x4{(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d}; }
+__device__ __forceinline__ f32x4 mfma16h(f16x4 x, f16x4 y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(x, y, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma32h(f16x8 x, f16x8 y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); }
+
+template <bool F16>
 __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const DecBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int tid = threadIdx.x, tok = tid >> 4, j = tid & 15, chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
@@ -1544,10 +1553,14 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
     const float* W = S + w_rows + (16 * half + li) * kP + 16 * kh + 2 * g4;
     const f32x2 x0 = *v2(X), x1 = *v2(X + 8), w0 = *v2(W), w1 = *v2(W + 8);
     f32x4 acc = z4();
-    acc = mfma16(x0[0], w0[0], acc);
-    acc = mfma16(x0[1], w0[1], acc);
-    acc = mfma16(x1[0], w1[0], acc);
-    acc = mfma16(x1[1], w1[1], acc);
+    if constexpr (F16) {
+      acc = mfma16h(h4(x0[0], x0[1], x1[0], x1[1]), h4(w0[0], w0[1], w1[0], w1[1]), acc);
+    } else {
+      acc = mfma16(x0[0], w0[0], acc);
+      acc = mfma16(x0[1], w0[1], acc);
+      acc = mfma16(x1[0], w1[0], acc);
+      acc = mfma16(x1[1], w1[1], acc);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) S[dst_rows + (4 * g4 + r) * kP + 16 * half + li] = acc[r];
   };
@@ -1555,10 +1568,14 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
   auto lin_t_partial = [&](int dy_rows, int w_rows, int it, int kq, f32x4& acc) {
     const f32x4 d = *v4(S + dy_rows + li * kP + 16 * kq + 4 * g4);
     const float* W = S + w_rows + (16 * kq + 4 * g4) * kP + 16 * it + li;
-    acc = mfma16(d[0], W[0], acc);
-    acc = mfma16(d[1], W[kP], acc);
-    acc = mfma16(d[2], W[2 * kP], acc);
-    acc = mfma16(d[3], W[3 * kP], acc);
+    if constexpr (F16) {
+      acc = mfma16h(h4(d[0], d[1], d[2], d[3]), h4(W[0], W[kP], W[2 * kP], W[3 * kP]), acc);
+    } else {
+      acc = mfma16(d[0], W[0], acc);
+      acc = mfma16(d[1], W[kP], acc);
+      acc = mfma16(d[2], W[2 * kP], acc);
+      acc = mfma16(d[3], W[3 * kP], acc);
+    }
   };
   const int begin = chunk * a.tiles * 64, end = min(a.G, begin + a.tiles * 64);
 #if SCLDM_VAE_PHASE_CLOCKS
@@ -1578,11 +1595,16 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
   auto first_gene = [&](int step) { return begin + 16 * ((step + rot) % nsteps); };
   long long gene_nx = 0, gene_n2 = 0;
   float dl_nx = 0.f, e0_nx = 0.f, e1_nx = 0.f;
+  // F16: dl enters scaled by the cell's 2^e (so that the gradient operands sit in the fp16 range); every output leaves times 2^-e
+  float dl_sc = 1.f;
+  bool bad = false;     // F16: a non-finite value in this workgroup's outputs
+  if constexpr (F16) dl_sc = a.dl_scale[cell];
   if (nsteps > 0) {
     const int ga = first_gene(0);
     gene_nx = a.genes[slot(ga)];
     gene_n2 = a.genes[slot(first_gene(1))];
     dl_nx = ga + tok < end ? a.dl[slot(ga)] : 0.f;
+    if constexpr (F16) dl_nx *= dl_sc;
     e0_nx = a.emb[(size_t)gene_nx * 32 + j];
     e1_nx = a.emb[(size_t)gene_nx * 32 + j + 16];
   }
@@ -1596,6 +1618,7 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
     e0_nx = a.emb[(size_t)gene_nx * 32 + j];
     e1_nx = a.emb[(size_t)gene_nx * 32 + j + 16];
     dl_nx = g1 + tok < end ? a.dl[slot(g1)] : 0.f;
+    if constexpr (F16) dl_nx *= dl_sc;
     gene_n2 = a.genes[slot(first_gene(step + 2))];
     if (j == 0) S[M_DL + tok] = dlog;
     const Ln n1 = ln_own(q00, q01, a.eps);
@@ -1615,8 +1638,12 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       const f32x2 q2 = *v2(S + G_QQ + li * kP + 8 * wave + 2 * g4) + *v2(S + G_TX + li * kP + 8 * wave + 2 * g4);
       const f32x2 k2 = *v2(S + G_KV + li * kP64 + 8 * wave + 2 * g4);
       f32x4 sc = z4();
-      sc = mfma16(q2[0], k2[0], sc);
-      sc = mfma16(q2[1], k2[1], sc);
+      if constexpr (F16) {
+        sc = mfma16h(h4(q2[0], q2[1], 0.f, 0.f), h4(k2[0], k2[1], 0.f, 0.f), sc);
+      } else {
+        sc = mfma16(q2[0], k2[0], sc);
+        sc = mfma16(q2[1], k2[1], sc);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float v = sc[r] * kScale, e = __expf(v - row16_max(v));
@@ -1625,12 +1652,18 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       }
       tsync();     // (this wave wrote the PP columns it reads)
       f32x4 ao = z4();
+      if constexpr (F16) {
+        const f32x2 p0 = *v2(S + G_PP + li * kP64 + 16 * wave + 2 * g4), p1 = *v2(S + G_PP + li * kP64 + 16 * wave + 8 + 2 * g4);
+        const float* V = S + G_KV + (2 * g4) * kP64 + 32 + 8 * wave + (li & 7);
+        ao = mfma16h(h4(p0[0], p0[1], p1[0], p1[1]), h4(V[0], V[kP64], V[8 * kP64], V[9 * kP64]), ao);
+      } else {
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const f32x2 p2 = *v2(S + G_PP + li * kP64 + 16 * wave + 8 * m + 2 * g4);
-        const float* V = S + G_KV + (8 * m + 2 * g4) * kP64 + 32 + 8 * wave + (li & 7);   // (lanes li, li + 8 share an address: no conflict)
-        ao = mfma16(p2[0], V[0], ao);
-        ao = mfma16(p2[1], V[kP64], ao);
+        for (int m = 0; m < 2; ++m) {
+          const f32x2 p2 = *v2(S + G_PP + li * kP64 + 16 * wave + 8 * m + 2 * g4);
+          const float* V = S + G_KV + (8 * m + 2 * g4) * kP64 + 32 + 8 * wave + (li & 7);   // (lanes li, li + 8 share an address: no conflict)
+          ao = mfma16(p2[0], V[0], ao);
+          ao = mfma16(p2[1], V[kP64], ao);
+        }
       }
       if (li < 8) {
 #pragma unroll
@@ -1663,13 +1696,26 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
         const int ot = wave + 4 * q;
         if (ot < 6) {
           f32x4 aa = z4(), bb = z4();
+          if constexpr (F16) {
+            f16x8 xh, xa, xb;
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            const f32x2 wa = *v2(S + G_W1 + (16 * ot + li) * kP + 8 * s + 2 * g4), wb = *v2(S + G_W2 + (16 * ot + li) * kP + 8 * s + 2 * g4);
-            aa = mfma16(hk[s][0], wa[0], aa);
-            bb = mfma16(hk[s][0], wb[0], bb);
-            aa = mfma16(hk[s][1], wa[1], aa);
-            bb = mfma16(hk[s][1], wb[1], bb);
+            for (int s = 0; s < 4; ++s) {
+              const f32x2 wa = *v2(S + G_W1 + (16 * ot + li) * kP + 8 * s + 2 * g4), wb = *v2(S + G_W2 + (16 * ot + li) * kP + 8 * s + 2 * g4);
+              xh[2 * s] = (_Float16)hk[s][0]; xh[2 * s + 1] = (_Float16)hk[s][1];
+              xa[2 * s] = (_Float16)wa[0]; xa[2 * s + 1] = (_Float16)wa[1];
+              xb[2 * s] = (_Float16)wb[0]; xb[2 * s + 1] = (_Float16)wb[1];
+            }
+            aa = mfma32h(xh, xa, aa);
+            bb = mfma32h(xh, xb, bb);
+          } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              const f32x2 wa = *v2(S + G_W1 + (16 * ot + li) * kP + 8 * s + 2 * g4), wb = *v2(S + G_W2 + (16 * ot + li) * kP + 8 * s + 2 * g4);
+              aa = mfma16(hk[s][0], wa[0], aa);
+              bb = mfma16(hk[s][0], wb[0], bb);
+              aa = mfma16(hk[s][1], wa[1], aa);
+              bb = mfma16(hk[s][1], wb[1], bb);
+            }
           }
           const float c0u = S[M_C0 + 16 * ot + li];
 #pragma unroll
@@ -1690,16 +1736,35 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       const float* Wm = S + (kh ? G_W2 : G_W1);
       const float* Dm = S + (kh ? G_DB : G_DA);
       f32x4 acc = z4(), acc2 = z4();
+      if constexpr (F16) {
 #pragma unroll
-      for (int sq = 0; sq < 6; ++sq) {
-        const f32x4 d = *v4(Dm + li * kQ + 16 * sq + 4 * g4);
-        const float* W = Wm + (16 * sq + 4 * g4) * kP + 16 * half + li;
-        acc = mfma16(d[0], W[0], acc);
-        acc2 = mfma16(d[1], W[kP], acc2);
-        acc = mfma16(d[2], W[2 * kP], acc);
-        acc2 = mfma16(d[3], W[3 * kP], acc2);
+        for (int sp = 0; sp < 3; ++sp) {     // two 16-unit k slices per 16 x 16 x 32 MFMA
+          f16x8 xd, xw;
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int sq = 2 * sp + u;
+            const f32x4 d = *v4(Dm + li * kQ + 16 * sq + 4 * g4);
+            const float* W = Wm + (16 * sq + 4 * g4) * kP + 16 * half + li;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              xd[4 * u + i] = (_Float16)d[i];
+              xw[4 * u + i] = (_Float16)W[i * kP];
+            }
+          }
+          acc = mfma32h(xd, xw, acc);
+        }
+      } else {
+#pragma unroll
+        for (int sq = 0; sq < 6; ++sq) {
+          const f32x4 d = *v4(Dm + li * kQ + 16 * sq + 4 * g4);
+          const float* W = Wm + (16 * sq + 4 * g4) * kP + 16 * half + li;
+          acc = mfma16(d[0], W[0], acc);
+          acc2 = mfma16(d[1], W[kP], acc2);
+          acc = mfma16(d[2], W[2 * kP], acc);
+          acc2 = mfma16(d[3], W[3 * kP], acc2);
+        }
+        acc += acc2;
       }
-      acc += acc2;
       float* Pt = S + (kh ? G_DQQ : G_TX);
 #pragma unroll
       for (int r = 0; r < 4; ++r) Pt[(4 * g4 + r) * kP + 16 * half + li] = acc[r];
@@ -1738,8 +1803,12 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       const f32x2 a2 = *v2(S + G_DAO + li * kP + 8 * wave + 2 * g4);
       const f32x2 v2v = *v2(S + G_KV + li * kP64 + 32 + 8 * wave + 2 * g4);
       f32x4 dp = z4();
-      dp = mfma16(a2[0], v2v[0], dp);
-      dp = mfma16(a2[1], v2v[1], dp);
+      if constexpr (F16) {
+        dp = mfma16h(h4(a2[0], a2[1], 0.f, 0.f), h4(v2v[0], v2v[1], 0.f, 0.f), dp);
+      } else {
+        dp = mfma16(a2[0], v2v[0], dp);
+        dp = mfma16(a2[1], v2v[1], dp);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float dg = row16_sum(p[r] * dp[r]);
@@ -1747,12 +1816,18 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       }
       tsync();
       f32x4 dq = z4();
+      if constexpr (F16) {
+        const f32x2 d0 = *v2(S + G_DS + li * kP64 + 16 * wave + 2 * g4), d1 = *v2(S + G_DS + li * kP64 + 16 * wave + 8 + 2 * g4);
+        const float* K = S + G_KV + (2 * g4) * kP64 + 8 * wave + (li & 7);
+        dq = mfma16h(h4(d0[0], d0[1], d1[0], d1[1]), h4(K[0], K[kP64], K[8 * kP64], K[9 * kP64]), dq);
+      } else {
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const f32x2 d2 = *v2(S + G_DS + li * kP64 + 16 * wave + 8 * m + 2 * g4);
-        const float* K = S + G_KV + (8 * m + 2 * g4) * kP64 + 8 * wave + (li & 7);
-        dq = mfma16(d2[0], K[0], dq);
-        dq = mfma16(d2[1], K[kP64], dq);
+        for (int m = 0; m < 2; ++m) {
+          const f32x2 d2 = *v2(S + G_DS + li * kP64 + 16 * wave + 8 * m + 2 * g4);
+          const float* K = S + G_KV + (8 * m + 2 * g4) * kP64 + 8 * wave + (li & 7);
+          dq = mfma16(d2[0], K[0], dq);
+          dq = mfma16(d2[1], K[kP64], dq);
+        }
       }
       if (li < 8) {
 #pragma unroll
@@ -1772,7 +1847,24 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
     }
     // ---- phase C: weight gradients, D[out 16 ot + 4 g4 + r][in 16 it + li] += sum_genes dy[gene][out] x[gene][in]
     // (d W1 | d W2 could run in phase B already - measured: B + 1 270 cycles, C - 890: the matrix pipe is shared with the CU's other workgroup)
-    {
+    if constexpr (F16) {   // (the four genes 4 g4 .. + 3 of a lane are the k of one 16 x 16 x 16 MFMA)
+      auto col4 = [&](int base, int ld) {
+        const float* p = S + base + 4 * g4 * ld;
+        return h4(p[0], p[ld], p[2 * ld], p[3 * ld]);
+      };
+#pragma unroll
+      for (int n = 0; n < 3; ++n) {
+        const int idx = wave + 4 * n, ot = idx >> 1, it = idx & 1;
+        const f16x4 x = col4(G_H2 + 16 * it + li, kP);
+        gw1[n] = mfma16h(col4(G_DA + 16 * ot + li, kQ), x, gw1[n]);
+        gw2[n] = mfma16h(col4(G_DB + 16 * ot + li, kQ), x, gw2[n]);
+      }
+      const int ot = wave >> 1, it = wave & 1;
+      gq = mfma16h(col4(G_DQQ + 16 * ot + li, kP), col4(G_QN + 16 * it + li, kP), gq);
+      gp = mfma16h(col4(G_DY + 16 * ot + li, kP), col4(G_AO + 16 * it + li, kP), gp);
+      gk = mfma16h(col4(G_DS + wave * 16 + li, kP64), col4(G_QQ + 16 * (wave >> 1) + li, kP), gk);
+      gv = mfma16h(col4(G_PP + wave * 16 + li, kP64), col4(G_DAO + 16 * (wave >> 1) + li, kP), gv);
+    } else {
 #pragma unroll
       for (int n = 0; n < 3; ++n) {
         const int idx = wave + 4 * n, ot = idx >> 1, it = idx & 1;
@@ -1805,8 +1897,14 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       ln_back(n1, t0 * l1w0, t1 * l1w1, o0, o1);
       if (valid && dlog != 0.f) {
         float* ge = a.g_emb + (size_t)gene * 32;
-        atomicAdd(ge + j, d0 + o0);
-        atomicAdd(ge + j + 16, d1 + o1);
+        float v0 = d0 + o0, v1 = d1 + o1;
+        if constexpr (F16) {
+          v0 *= 1.0f / dl_sc;
+          v1 *= 1.0f / dl_sc;
+          bad |= !(__builtin_isfinite(v0) && __builtin_isfinite(v1));
+        }
+        atomicAdd(ge + j, v0);
+        atomicAdd(ge + j + 16, v1);
       }
     }
     PHASE_MARK(11);
@@ -1818,6 +1916,23 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
 #endif
 #undef PHASE_MARK
   __syncthreads();
+  if constexpr (F16) {     // back to the unscaled gradient (exact: a power of two), and the overflow check of what leaves
+    const float inv = 1.0f / dl_sc;
+    auto fix = [&](f32x4& v) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] *= inv;
+        bad |= !__builtin_isfinite(v[r]);
+      }
+    };
+#pragma unroll
+    for (int n = 0; n < 3; ++n) { fix(gw1[n]); fix(gw2[n]); }
+    fix(gq); fix(gp); fix(gk); fix(gv);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) vs[i] *= inv;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) cacc[q] *= inv;
+  }
   // ---- one partial per workgroup (as dec_gene_bwd_mfma_kernel)
   float* P = a.part + (size_t)(cell * nch + chunk) * DP_SIZE;
   {
@@ -1858,6 +1973,10 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
   }
   float cu = 0.f;
   if (tid < 96) cu = (RC[tid] + RC[96 + tid]) + (RC[192 + tid] + RC[288 + tid]);
+  if constexpr (F16) {
+    bad |= !(__builtin_isfinite(sum) && __builtin_isfinite(cu));
+    if (bad && a.found_inf) *a.found_inf = 1.0f;
+  }
   __syncthreads();
   float* C = S;            // c[u]
   float* HD = S + 128;     // sum dlogit * y

@@ -17,7 +17,8 @@ class _VAETrainFn(torch.autograd.Function):
     """TransformerVAE.forward with a HIP backward (scldm_vae_train_forward / _backward, include/scldm_hip.h): replaces torch
     autograd over the reference's module tree (vae.py:29-56) inside VAE.training_step (models.py:249-290).  Outputs mu, theta
     (B, G) and z (B, 16, n_lat) are ordinary differentiable tensors: the reference's own `-log_nb_positive(counts, mu, theta)`
-    (models.py:243) - or scldm_amd.distributions.log_nb_positive, the fused form - sits on top of them unchanged."""
+    (models.py:243) - or scldm_amd.distributions.log_nb_positive, the fused form - sits on top of them unchanged.  The operand policy
+    (`module.precision`, "fp32" or "fp16") is read at the forward and used by the backward of the same step."""
 
     @staticmethod
     def forward(ctx, module, counts_subset, genes_subset, genes, lib, *params):
@@ -30,11 +31,15 @@ class _VAETrainFn(torch.autograd.Function):
         z = torch.empty(B, module.encoder.latent_dim, module.encoder.latent_embedding, device=dev, dtype=torch.float32)
         saved = torch.empty(L.scldm_vae_train_saved_bytes(h, B), dtype=torch.uint8, device=dev)
         ws = torch.empty(L.scldm_vae_train_workspace_bytes(h, B, S, G), dtype=torch.uint8, device=dev)
+        prec = _lib.PRECISIONS[module.precision]
+        if prec == _lib.PREC_FP16:
+            module.found_inf_flag()     # (registers the flag with the handle: the fp16 backward resets and sets it)
         with torch.cuda.device(dev):
-            _lib.check(L.scldm_vae_train_forward(h, counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(), lib.data_ptr(), G,
-                                                 mu.data_ptr(), theta.data_ptr(), z.data_ptr(), saved.data_ptr(), ws.data_ptr(), _stream_ptr()),
-                       "scldm_vae_train_forward")
-        ctx.module, ctx.saved, ctx.ws = module, saved, ws
+            _lib.check(L.scldm_vae_train_forward_ex(h, counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(), lib.data_ptr(),
+                                                    G, mu.data_ptr(), theta.data_ptr(), z.data_ptr(), saved.data_ptr(), ws.data_ptr(), prec,
+                                                    _stream_ptr()),
+                       "scldm_vae_train_forward_ex")
+        ctx.module, ctx.saved, ctx.ws, ctx.prec = module, saved, ws, prec
         ctx.inputs = (counts_subset, genes_subset, genes, lib)
         ctx.outs = (mu, theta, z)
         ctx.params = params
@@ -76,10 +81,11 @@ class _VAETrainFn(torch.autograd.Function):
         g, keep_g = cache["g"]
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
-            _lib.check(L.scldm_vae_train_backward(h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S,
-                                                  genes.data_ptr(), lib.data_ptr(), G, mu.data_ptr(), theta.data_ptr(), z.data_ptr(),
-                                                  ptr(dmu), ptr(dtheta), ptr(dz), ctx.saved.data_ptr(), ctx.ws.data_ptr(), _stream_ptr()),
-                       "scldm_vae_train_backward")
+            _lib.check(L.scldm_vae_train_backward_ex(h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S,
+                                                     genes.data_ptr(), lib.data_ptr(), G, mu.data_ptr(), theta.data_ptr(), z.data_ptr(),
+                                                     ptr(dmu), ptr(dtheta), ptr(dz), ctx.saved.data_ptr(), ctx.ws.data_ptr(), ctx.prec,
+                                                     _stream_ptr()),
+                       "scldm_vae_train_backward_ex")
         ctx.saved = ctx.ws = None
         views = _unflatten_dense_tensors(flat, params)      # one C++ call instead of 175 slices + views
         out = [v if ctx.needs_input_grad[5 + i] else None for i, v in enumerate(views)]
@@ -98,7 +104,9 @@ class TransformerVAE(nn.Module):
         # operand policy of the contractions of encode / decode / decode_sample - the per-gene MCAB / SwiGLU products and the Linears of
         # the 16-token trunks (LayerNorms, softmax, the trunks' 16 x 16 attention and the NB head are fp32 in every policy): "fp32" =
         # exact (parity path); "fp16" = TF32's mantissa, the arithmetic class the reference itself runs the VAE in
-        # (set_float32_matmul_precision("high"), experiments/scripts/inference.py:26); "bf16" = 8 bits
+        # (set_float32_matmul_precision("high"), experiments/scripts/inference.py:26); "bf16" = 8 bits.  Training (forward under
+        # autograd) takes "fp32" or "fp16": the TF32 class of the reference's trainer (experiments/scripts/train.py:18) - fp16 operands in
+        # the pooling, the per-gene decoder and every contraction of the per-gene backward, the 16-token trunks exact; see found_inf_flag()
         self.precision = "fp32"
         self._weights_key = None
         self._weights_fp = None
@@ -147,13 +155,30 @@ class TransformerVAE(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _weights_fp=None, _ws=None, _keep=None)
-        state.pop("_train_cache", None)
+        for k in ("_train_cache", "_found_inf", "_found_inf_handle"):    # (the flag is registered with the handle that does not travel)
+            state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         super().__setstate__(state)
         for k in ("_handle", "_weights_key", "_weights_fp", "_ws", "_keep"):
             self.__dict__.setdefault(k, None)
+
+    def found_inf_flag(self) -> torch.Tensor:
+        """Device float the fp16 training backward sets to 1.0 when the per-gene backward produced a non-finite gradient (reset to 0.0
+        at the start of every fp16 backward): hand it to an optimizer that understands GradScaler's `found_inf`
+        (`scldm_amd.optim.AdamW`: `optimizer.found_inf = vae.found_inf_flag()`), which then skips the step on device, no host read.
+        The contract of DiT.found_inf_flag()."""
+        L, h = (_lib.lib(), self._handle) if self._handle is not None else self._native()
+        dev = self.input_layer.gene_embedding.weight.device
+        flag = self.__dict__.get("_found_inf")
+        if flag is None or flag.device != dev:
+            flag = self.__dict__["_found_inf"] = torch.zeros((), dtype=torch.float32, device=dev)
+            self.__dict__["_found_inf_handle"] = None
+        if self.__dict__.get("_found_inf_handle") != h.value:     # (re-)register with THIS handle (a copy starts with none)
+            _lib.check(L.scldm_vae_train_set_found_inf(h, flag.data_ptr()), "scldm_vae_train_set_found_inf")
+            self.__dict__["_found_inf_handle"] = h.value
+        return flag
 
     def _weights_struct(self, dp):
         """scldm_vae_weights filled with dp(parameter) -> device pointer (the same struct, with writable pointers, receives the
@@ -289,7 +314,8 @@ class TransformerVAE(nn.Module):
 
     def forward(self, counts, genes, library_size, counts_subset=None, genes_subset=None):
         """(params, z) with params = {"mu", "theta"} (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
-        are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), fp32.  As in the
+        are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
+        (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if counts_subset is None or genes_subset is None:
@@ -303,11 +329,11 @@ class TransformerVAE(nn.Module):
             if cs.dim() != 2 or gs.shape != cs.shape or g.dim() != 2 or g.shape[0] != cs.shape[0] or lib.shape[0] != cs.shape[0]:
                 raise ValueError(f"expected counts_subset / genes_subset (B,S), genes (B,G), library_size (B,1); got {tuple(cs.shape)}, "
                                  f"{tuple(gs.shape)}, {tuple(g.shape)}, {tuple(library_size.shape)}")
-            if self.precision != "fp32":
-                raise NotImplementedError("TransformerVAE training runs in fp32 (precision='fp32')")
             if self.decoder_head.theta is None:
                 raise NotImplementedError("the HIP training backward is built for the shared-theta NB head (vae_base.yaml:62); "
                                           "the unshared-theta head (stochastic_layers.py:94-96) decodes only")
+            if self.precision not in ("fp32", "fp16"):
+                raise NotImplementedError(f"TransformerVAE training runs in fp32 or fp16 (precision={self.precision!r})")
             params = tuple(self.parameters())
             mu, theta, z = _VAETrainFn.apply(self, cs, gs, g, lib, *params)
             return {"mu": mu, "theta": theta}, z
