@@ -533,8 +533,7 @@ int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scl
  * class (set_float32_matmul_precision("high")): fp16 operands rounded to nearest even, fp32 accumulation, in the encoder pooling and
  * the per-gene decoder forward and in every contraction of the per-gene chain backward; the two 16-token trunks, the pooling backward,
  * LayerNorms, softmax, the SwiGLU gradient and the NB head stay fp32.  Forward and backward of one step take the same value; any
- * other value returns SCLDM_ERR_SHAPE.  fp16 needs the default kernel generations (SCLDM_ERR_STATE if SCLDM_VAE_GENE_MFMA,
- * SCLDM_VAE_GENE_WIDE or SCLDM_VAE_CELL_WIDE selects an earlier one).  The fp16 backward scales each cell's logit gradient by a power of
+ * other value returns SCLDM_ERR_SHAPE.  The fp16 backward scales each cell's logit gradient by a power of
  * two (max |2^e dlogit| in [1024, 2048)) before rounding and its results back by 2^-e (exact), and - if the caller registered one with
  * scldm_vae_train_set_found_inf - sets a device float to 1.0 when the per-gene backward produced a non-finite gradient (reset to 0.0
  * at the start of every fp16 backward): an optimizer that takes GradScaler's `found_inf` skips the step on device. */

@@ -213,8 +213,7 @@ __host__ __device__ inline long long pack_job_threads(int kind, long long n, con
   return n;
 }
 // prec_mask: bit p set = pack the streams of precision p (kPackLayer / kPackFinal jobs of other precisions are skipped - the
-// training step re-packs only what it reads); kPackLayerBwd jobs run when bit 8 is set (bit 9: as fp16 instead of bf16); bit 10: ONLY
-// the kPackLayerBwd jobs (the training step's second launch: the backward stream is packed beside the forward, not ahead of it).
+// training step re-packs only what it reads); kPackLayerBwd jobs run when bit 8 is set (bit 9: as fp16 instead of bf16).
 __global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* __restrict__ jobs, int n_jobs, const int* __restrict__ dirty,
                                                         unsigned prec_mask, int* __restrict__ fp16_stats = nullptr) {
   if (dirty && *dirty == 0) return;
@@ -225,7 +224,6 @@ __global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* __restric
   }
   const PackJob& j = jobs[lo];
   const long long idx = (long long)((int)blockIdx.x - j.first_block) * 256 + threadIdx.x;
-  if ((prec_mask & 0x400u) && j.kind != kPackLayerBwd) return;
   if (j.kind == kPackTranspose && pack_transpose_tiled(j.p)) {   // out[k*ldo + col0 + n] = W[n*K + k], a 32 x 32 tile per block
     __shared__ float tile[32][33];
     const int N = j.p[0], K = j.p[1], ldo = j.p[2], col0 = j.p[3];

@@ -52,7 +52,6 @@ struct scldm_dit {
   unsigned long long* d_fp_state;  // [0] running accumulator, [1] fingerprint of the packed weights
   int* d_dirty;    // [0] re-pack flag written by the compare kernel, [1] force flag
   hipStream_t side[3];     // secondary streams for tile-group launches (created on first use)
-  bool wgrad_reduce_on_side = false;   // fused training backward: the deferred weight-gradient reduction is in flight on side[2] (joined by scldm_dit_train_backward)
   hipEvent_t fork_ev, join_ev[3];
   hipEvent_t wg_ev[2] = {nullptr, nullptr};   // fused training, small batches: layer l's weight-gradient launches (side stream) are done with operand-pair set l & 1
   hipEvent_t bwd_pack_ev = nullptr;   // the training step's backward weight stream is packed (second pack launch of fused::prepare)
@@ -86,8 +85,6 @@ struct scldm_dit {
   size_t w16_layer_elems;
   void* wt16;               // the same matrices transposed ([in][out], rows padded to a multiple of 8): k-contiguous operands of the data gradients
   size_t wt16_layer_elems;
-  int n_cast_first;         // cast jobs that run ahead of the forward (adaLN + the first layers); the rest runs beside it
-  bool cast_side_busy;      // the side-stream cast of this step has not been joined yet
   bool wt16_live;           // the current step's forward refreshed the transposed copies (large batches only)
   void* ada16;              // [mod_w][D] bf16: every adaLN Linear's weight stacked (one GEMM for all layers' modulation vectors)
   float* ada_ball;          // [mod_w] fp32: their biases, stacked

@@ -10,10 +10,8 @@
 #include "train.hpp"
 #include "bgemm.hpp"
 #include "bgemm8.hpp"
-#include "bgemm4.hpp"
 #include "attn_mfma.hpp"
 #include "train_fused.hpp"
-#include "cond_bwd.hpp"
 
 using namespace scldm;
 using namespace scldm::train;
@@ -209,7 +207,6 @@ const bool g_epi_lds = [] { const char* e = getenv("SCLDM_EPI_LDS"); return !e |
 const int g_min_tiles256 = [] { const char* e = getenv("SCLDM_MIN_TILES256"); return e ? atoi(e) : 96; }();
 const bool g_bgemm8 = [] { const char* e = getenv("SCLDM_BGEMM8"); return !e || atoi(e) != 0; }();   // LDS-DMA phase-split kernel for (KC, KC) (A/B switch)
 const bool g_bgemm8_wgrad = [] { const char* e = getenv("SCLDM_BGEMM8_WGRAD"); return !e || atoi(e) != 0; }();   // A/B switch (read at load)
-const bool g_bgemm_persist = [] { const char* e = getenv("SCLDM_BGEMM_PERSIST"); return e && atoi(e) != 0; }();   // A/B switch (read at load)
 
 template <bool BIG, bool A_KC, bool B_KC>
 int launch_bgemm(const BGemmArgs& g, int blocks, hipStream_t st) {
@@ -268,35 +265,6 @@ int launch_bgemm8_mc(const BGemmArgs& g, int blocks, hipStream_t st) {   // both
   return SCLDM_OK;
 }
 
-// 128 x 128 LDS-DMA kernel (bgemm4.hpp) for (KC, KC) products that do not fill the chip with 256-tiles
-// SCLDM_BGEMM4: 0 = never (default), 1 = every (KC, KC) product of the small-tile class, 2 = the forward's only (read at load).
-// Opt-in: stand-alone the kernel is bit-identical to bgemm_kernel and 5-35 % faster per product (profiles/r3_gemm_probe_small.txt), inside
-// the training step it measured +-0 (forward only) to -3 % (everywhere): DiT-L at 256 cells 19.4 / 19.8 against 19.25 ms, 512 x 12 at
-// 512 cells 8.1 / 8.5 against 8.16 (profiles/r3_train_bgemm4_modes.txt) - its one-stage prefetch suffers next to the kernels it shares
-// the chip with, where bgemm_kernel keeps two register stages in flight.
-const int g_bgemm4 = [] { const char* e = getenv("SCLDM_BGEMM4"); return e ? atoi(e) : 0; }();
-thread_local bool t_in_backward = false;   // set by scldm_dit_train_backward around its launches
-template <int EPI>
-int launch_bgemm4_t(const BGemmArgs& g, int blocks, hipStream_t st) {
-  static std::atomic<bool> attr_set[kMaxDevices];
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= kMaxDevices || !attr_set[dev].load(std::memory_order_acquire)) {
-    HIP_TRY(hipFuncSetAttribute((const void*)bgemm4_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, kBGemm4Lds));
-    if (dev >= 0 && dev < kMaxDevices) attr_set[dev].store(true, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(bgemm4_kernel<EPI>, dim3(blocks), dim3(256), kBGemm4Lds, st, g);
-  LAUNCH_CHECK();
-  return SCLDM_OK;
-}
-int launch_bgemm4(const BGemmArgs& g, int blocks, hipStream_t st) {
-  // results through LDS need whole 16-byte pieces per row: fp32 - N, ldc multiples of 4 and a 16-byte aligned base; bf16 - N % 4 == 0
-  // (rows of N % 8 == 4 elements are 8-byte aligned: global 16-byte stores need dword alignment only)
-  const bool lds_ok = g.C16 ? (g.N % 4 == 0 && (reinterpret_cast<uintptr_t>(g.C16) & 15) == 0)
-                            : (g.N % 4 == 0 && g.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
-  return lds_ok ? launch_bgemm4_t<0>(g, blocks, st) : launch_bgemm4_t<1>(g, blocks, st);
-}
-
 // C[M,N] (ldc) (+)= A(m,k) B(n,k) (+ bias[n]); *_kc: the operand is contiguous along k (else along m / n).  Operand
 // orientations in use: (KC, KC) forward, (KC, MC) data gradient, (MC, MC) weight gradient.
 int bgemm(hipStream_t st, const __bf16* A, int lda, bool a_kc, const __bf16* B, int ldb, bool b_kc, float* C, long ldc, int M, int N,
@@ -338,7 +306,7 @@ int bgemm(hipStream_t st, const __bf16* A, int lda, bool a_kc, const __bf16* B, 
   g.accumulate = accumulate ? 1 : 0;
   g.rowsum = rowsum_out;
   g.per_xcd = (int)cdiv(tiles, 8);
-  int blocks = splits > 1 ? (int)tiles * splits : 8 * g.per_xcd;
+  const int blocks = splits > 1 ? (int)tiles * splits : 8 * g.per_xcd;
   if (splits > 1) {
     g.C = part;
     g.ldc = N;
@@ -349,10 +317,6 @@ int bgemm(hipStream_t st, const __bf16* A, int lda, bool a_kc, const __bf16* B, 
   int rc;
   // (bf16 results of the LDS-DMA kernel are stored in pairs at least: rows of an even number of elements)
   const bool use8 = big && a_kc == b_kc && splits == 1 && g_bgemm8 && (a_kc || g_bgemm8_wgrad) && (!C16 || N % 2 == 0);   // LDS-DMA kernel (bgemm8.hpp): (KC, KC) and (MC, MC)
-  if (big && !use8 && g_bgemm_persist && splits == 1 && blocks > 256) {   // persistent: one workgroup per CU walks the tiles (see bgemm256_kernel)
-    g.n_blocks = blocks;
-    blocks = 256;
-  }
   if (ep && !use8) return fail(SCLDM_ERR_SHAPE, "bgemm: a fused epilogue needs the 256-tile LDS-DMA kernel");
   bool rs_split = false;
   if (use8 && !a_kc && rowsum_out && g.tiles_n > 1 && (size_t)g.tiles_n * M <= part_floats) {   // bias gradient split over the tile columns (see wgrad_batch)
@@ -363,7 +327,6 @@ int bgemm(hipStream_t st, const __bf16* A, int lda, bool a_kc, const __bf16* B, 
   if (use8) rc = a_kc ? launch_bgemm8(g, blocks, st) : launch_bgemm8_mc(g, blocks, st);
   else if (big) rc = a_kc ? (b_kc ? launch_bgemm<true, true, true>(g, blocks, st) : launch_bgemm<true, true, false>(g, blocks, st))
                      : launch_bgemm<true, false, false>(g, blocks, st);
-  else if (a_kc && b_kc && !ep && (g_bgemm4 == 1 || (g_bgemm4 == 2 && !t_in_backward))) rc = launch_bgemm4(g, blocks, st);
   else rc = a_kc ? (b_kc ? launch_bgemm<false, true, true>(g, blocks, st) : launch_bgemm<false, true, false>(g, blocks, st))
                  : launch_bgemm<false, false, false>(g, blocks, st);
   if (rc != SCLDM_OK) return rc;
@@ -498,10 +461,6 @@ bool want_wt(const scldm_dit* h, int n) {
   static const int wt_min = [] { const char* e = getenv("SCLDM_WT_MIN_TILES"); return e ? atoi(e) : 32; }();
   return g_dgrad_wt && (g_bgemm256 == 2 || cdiv((long)n * kS, 256L) * cdiv((long)h->cfg.n_embed, 256L) >= wt_min);   // (2: the tests force 256-tiles)
 }
-constexpr int kCastAhead = 2;
-// (opt-in: measured +-0 - 45.7 / 45.8 against 45.8 / 45.8 ms at 1 024 cells, 19.4 / 19.45 against 19.4 / 19.6 at 256: the cast's 2.7 GB
-// slow the kernels it runs beside by what it saves)
-const bool g_cast_side = [] { const char* e = getenv("SCLDM_CAST_SIDE"); return e && atoi(e) != 0; }();
 int prepare_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st) {
   const size_t D = h->cfg.n_embed, H = h->cfg.hidden_dim, Hp = hidden16(h);
   const int L = h->cfg.n_layer;
@@ -529,8 +488,7 @@ int prepare_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st)
       jobs.push_back(CastJob{l < L ? w->ada_w[l] : w->fin_ada_w, a16 + (size_t)l * 6 * D * D, rows, (int)D, (int)D, 0, nullptr, 0, 0});
       jobs.push_back(CastJob{l < L ? w->ada_b[l] : w->fin_ada_b, reinterpret_cast<__bf16*>(h->ada_ball + (size_t)l * 6 * D), 1, rows, rows, 1, nullptr, 0, 0});
     }
-    // ... then the layers in order: the first two are cast ahead of the forward, the rest beside it (refresh_w16)
-    int n_first = (int)jobs.size();
+    // ... then the layers in order
     for (int l = 0; l < L; ++l) {
       const W16 d = w16_layer(h, l);
       const W16 dt = wt ? wt16_layer(h, l) : W16{};
@@ -540,14 +498,12 @@ int prepare_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st)
       jobs.push_back(CastJob{w->w1[l], tp(d.w1), (int)H, (int)D, (int)D, 0, tp(dt.w1), (int)(2 * Hp), (int)Hp});
       jobs.push_back(CastJob{w->w2[l], tp(d.w2), (int)H, (int)D, (int)D, 0, tp(dt.w2), (int)(2 * Hp), (int)Hp});
       jobs.push_back(CastJob{w->cproj[l], tp(d.cproj), (int)D, (int)H, (int)Hp, 0, tp(dt.cproj), (int)D, (int)D});
-      if (l < kCastAhead) n_first = (int)jobs.size();
     }
     if (!h->d_cast_jobs) HIP_TRY(hipMalloc(&h->d_cast_jobs, jobs.size() * sizeof(CastJob)));
     // (synchronous copy of a pageable vector: only when the parameters' device pointers changed)
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(h->d_cast_jobs, jobs.data(), jobs.size() * sizeof(CastJob), hipMemcpyHostToDevice));
     h->n_cast_jobs = (int)jobs.size();
-    h->n_cast_first = n_first;
     h->w16_key = key;
   }
   return SCLDM_OK;
@@ -556,26 +512,9 @@ int refresh_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st)
   if (h->cfg.n_layer == 0) return SCLDM_OK;
   int rc = prepare_w16(h, w, n, st);   // no-op (a pointer-list compare) once prepared for these parameters
   if (rc != SCLDM_OK) return rc;
-  // the adaLN matrices and the first kCastAhead layers on `st`; the other layers on a side stream beside the forward of those
-  // layers (2.7 GB of HBM traffic for DiT-L that nothing waits for until layer kCastAhead: the forward joins there)
-  const CastJob* jobs = (const CastJob*)h->d_cast_jobs;
-  const int first = g_cast_side ? h->n_cast_first : h->n_cast_jobs, rest = h->n_cast_jobs - first;
-  hipLaunchKernelGGL(cast_jobs_kernel, dim3(64, first), dim3(256), 0, st, jobs, first);
+  hipLaunchKernelGGL(cast_jobs_kernel, dim3(64, h->n_cast_jobs), dim3(256), 0, st, (const CastJob*)h->d_cast_jobs, h->n_cast_jobs);
   LAUNCH_CHECK();
-  if (rest > 0) {
-    hipStream_t ss = st;
-    rc = fused::fork_side(h, st, 0, &ss);
-    if (rc != SCLDM_OK) return rc;
-    hipLaunchKernelGGL(cast_jobs_kernel, dim3(64, rest), dim3(256), 0, ss, jobs + first, rest);
-    LAUNCH_CHECK();
-    h->cast_side_busy = true;
-  }
   return SCLDM_OK;
-}
-int join_cast(scldm_dit* h, hipStream_t st) {   // the forward, before the first layer whose copies the side stream writes
-  if (!h->cast_side_busy) return SCLDM_OK;
-  h->cast_side_busy = false;
-  return fused::join_side(h, st, 0);
 }
 
 // (ldw: elements per row of the bf16 weight copy = `in` rounded up to a multiple of 8)
@@ -868,7 +807,6 @@ extern "C" int scldm_dit_train_forward(scldm_dit* h, const scldm_dit_weights* w,
   for (int l = 0; l < L; ++l) {
     LayerSaved& a = s.layer[l];
     const int o = l * 6 * kD;   // a0..a5 at o + i*D (layers.py:214-216)
-    if (src16 && l == kCastAhead) TRY(join_cast(h, st));
     const W16 wh = src16 ? w16_layer(h, l) : W16{};
     float* x_next = l + 1 < L ? s.layer[l + 1].x_in : s.x_last;
     // (fuse_res: the previous layer's second residual step already produced x_in, h1 and st1 in one pass)
@@ -929,7 +867,6 @@ extern "C" int scldm_dit_train_set_grad_events(scldm_dit* h, void* const* events
 extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* g, const float* x,
                                         const int64_t* const* labels, const float* dout, int n, float* dx_out, int precision,
                                         void* saved_, void* ws, void* stream_) {
-  struct InBackward { InBackward() { t_in_backward = true; } ~InBackward() { t_in_backward = false; } } in_backward_scope;
   // the gradient-ready events belong to THIS call only: whatever way it returns, none of the raw hipEvent_t handles survives on the
   // handle (the caller may destroy them right after; a later backward without set_grad_events must not record into them)
   struct DropEvents { scldm_dit* h; ~DropEvents() { if (h) h->grad_events.clear(); } } drop_events_scope{h};
@@ -971,36 +908,9 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     TRY(ln_bwd(st, kD, n, k.dh, s.x_last, s.st_f, s.mod, (long)mw, of + kD, of, k.dx, 0, k.dmod));
     if (use_fused) TRY(fused::to_tile(k.dx, fs.dx, n, st));
   }
-  // Fused route, adaLN Linears mod_l = SiLU(c) W_l^T + b_l (round 5): the two products of every layer's slice of dmod - the weight
-  // gradient d W_l = dmod_l^T SiLU(c) (+ row sums = bias gradient) and the running sum d SiLU(c) += dmod_l W_l - are queued on a side
-  // stream as soon as that layer's backward kernel is (the final layer's slice first), so they run beside the layers still being
-  // differentiated instead of as two K = 13 824 / M = 13 824 products in the tail after the last layer (140 us of a 2.2 ms step).
-  // MEASURED SLOWER at 1 024 cells (2.77 against 2.15 ms per step: the small products take workgroup slots - and with them whole CUs'
-  // worth of LDS - from the backward layer, which needs one CU per tile) and +-0 at 256 cells: opt-in, SCLDM_TRAIN_ADA_STREAM=1.
-  static const bool ada_opt = [] { const char* e = getenv("SCLDM_TRAIN_ADA_STREAM"); return e && e[0] == '1'; }();
-  const bool ada_stream = use_fused && ada_opt;
-  hipStream_t s_ada_l = st;
-  auto ada_slice = [&](int l, bool first) -> int {
-    const int width = l < L ? 6 * kD : 2 * kD;
-    const size_t off = (size_t)l * 6 * kD;
-    float* dw_all = fs.ada_dw;
-    float* db_all = fs.ada_dw + (size_t)mw * kD;
-    TRY(gemm(s_ada_l, k.dmod + off, 1, mw, s.sc, 1, kD, dw_all + off * kD, kD, width, kD, n, nullptr, false, nullptr, 0, db_all + off));
-    TRY(gemm(s_ada_l, k.dmod + off, mw, 1, h->ada_t + off, mw, 1, k.dsc, kD, n, kD, width, nullptr, !first, nullptr, 0));
-    return SCLDM_OK;
-  };
   if (use_fused) {
     TRY(fused::backward_join(h, st));
-    if (ada_stream) {
-      TRY(fused::fork_side(h, st, 1, &s_ada_l));     // (the final layer's dmod slice is complete here)
-      TRY(ada_slice(L, true));
-      TRY(fused::backward_layers(h, g, s.mod, k.dmod, n, rec, fs, st, precision, [&](int l) -> int {
-        TRY(fused::fork_side(h, st, 1, &s_ada_l));   // the side stream waits for layer l's kernel
-        return ada_slice(l, false);
-      }));
-    } else {
-      TRY(fused::backward_layers(h, g, s.mod, k.dmod, n, rec, fs, st, precision));
-    }
+    TRY(fused::backward_layers(h, g, s.mod, k.dmod, n, rec, fs, st, precision));
     if (edge) TRY(fused::join_side(h, st, 0));   // the final layer's weight / bias gradient reduction (side stream 0, fused::final_backward)
     if (!edge || dx_out) TRY(fused::to_plain(fs.dx, k.dx, n, st));
   }
@@ -1214,8 +1124,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   // disjoint scratch, so the first two go to side streams and the chain stays on `st`.
   hipStream_t s_in = st, s_ada = st;
   if (edge && !dx_out) TRY(fused::fork_side(h, st, 0, &s_in));
-  if (use_fused && !ada_stream) TRY(fused::fork_side(h, st, 1, &s_ada));
-  if (ada_stream) s_ada = s_ada_l;
+  if (use_fused) TRY(fused::fork_side(h, st, 1, &s_ada));
   if (edge) {
     TRY(fused::inproj_backward(h, fs.dx, x, n, g->in_w, g->in_b, g->pos_embed, fs.edge_part, s_in));
   } else {
@@ -1230,15 +1139,10 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     // contiguous (mod_w, D) scratch, scattered to the per-layer gradient tensors by one kernel
     float* dw_all = fs.ada_dw;
     float* db_all = fs.ada_dw + (size_t)mw * kD;
-    if (ada_stream) {   // every slice's products are queued on the side stream already: scatter, and wait for the running sum
-      TRY(fused::scatter_ada_grads(h, g, dw_all, db_all, s_ada));
-      TRY(fused::join_side(h, st, 1));
-    } else {
-      // (200 output tiles, K = n: no split-K, so this GEMM needs no partial buffer and can run beside the chain below)
-      TRY(gemm(s_ada, k.dmod, 1, mw, s.sc, 1, kD, dw_all, kD, mw, kD, n, nullptr, false, nullptr, 0, db_all));
-      TRY(fused::scatter_ada_grads(h, g, dw_all, db_all, s_ada));
-      TRY(gemm(st, k.dmod, mw, 1, h->ada_t, mw, 1, k.dsc, kD, n, kD, mw, nullptr, false, k.part, k.part_floats));
-    }
+    // (200 output tiles, K = n: no split-K, so this GEMM needs no partial buffer and can run beside the chain below)
+    TRY(gemm(s_ada, k.dmod, 1, mw, s.sc, 1, kD, dw_all, kD, mw, kD, n, nullptr, false, nullptr, 0, db_all));
+    TRY(fused::scatter_ada_grads(h, g, dw_all, db_all, s_ada));
+    TRY(gemm(st, k.dmod, mw, 1, h->ada_t, mw, 1, k.dsc, kD, n, kD, mw, nullptr, false, k.part, k.part_floats));
   }
   // bf16-source route: one cast of dmod, then d SiLU(c) = dmod W_all as ONE split-K product and the per-layer weight
   // gradients straight into their tensors (column slices of dmod as the m-contiguous A operand, row sums = bias gradients).
@@ -1280,17 +1184,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     TRY(fire(SCLDM_GRAD_ADA, l));
     TRY(linear_dgrad(st, dm, mw, wl, n, width, kD, k.dsc, kD, l > 0, k));
   }
-  // Fused route (round 6): everything behind d SiLU(c) except the class tables as two exact-fp32 kernels (cond_bwd.hpp) instead of a chain
-  // of nine launches.  MEASURED +-0 to slower (same box, interleaved: 1 024 cells 1.984-1.998 against 1.972 ms per step, 256 cells 1.246
-  // against 1.208): the chain's launches already run on three streams beside the stacked adaLN weight gradient, and the two kernels
-  // (27 + 28 us: 128 workgroups each, latency-bound) share the chip with that product.  Opt-in: SCLDM_TRAIN_COND_BWD=1.
-  static const bool cond_bwd_on = [] { const char* e = getenv("SCLDM_TRAIN_COND_BWD"); return e && e[0] == '1'; }();
-  const bool cond2 = use_fused && cond_bwd_on && kD == kCbD;
-  if (cond2) {
-    hipLaunchKernelGGL(cond_bwd_rows_kernel, dim3(cdiv(n, kCbRows)), dim3(256), 0, st, k.dsc, s.c, s.th, w->t_w2, n, k.dc, k.dth);
-  } else {
-    hipLaunchKernelGGL(silu_bwd_kernel, dim3(ew_grid((long)n * kD)), dim3(256), 0, st, k.dsc, s.c, k.dc, (long)n * kD);
-  }
+  hipLaunchKernelGGL(silu_bwd_kernel, dim3(ew_grid((long)n * kD)), dim3(256), 0, st, k.dsc, s.c, k.dc, (long)n * kD);
   LAUNCH_CHECK();
 
   // ---- class embeddings and the timestep MLP (c = temb + sum emb) ----
@@ -1312,7 +1206,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   }
   if (par_tails) {
     TRY(fused::fork_side(h, st, 1, &s_tw2));
-    k_tw2.part = fs.part + (fs.part_layers > 1 ? (size_t)fs.part_layers * fs.part_floats : 0);   // (the spare block: the layers' blocks may still be read by the deferred reduction)
+    k_tw2.part = fs.part;
     k_tw2.part_floats = fs.part_floats;
   }
   for (int c = 0; c < cfg.n_classes; ++c) {
@@ -1330,27 +1224,14 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     }
     LAUNCH_CHECK();
   }
-  if (cond2) {
-    CondWgradArgs ca{};
-    ca.dy[0] = k.dc; ca.x[0] = s.sth; ca.dW[0] = g->t_w2; ca.db[0] = g->t_b2;
-    ca.dy[1] = k.dth; ca.x[1] = s.freq; ca.dW[1] = g->t_w0; ca.db[1] = g->t_b0;
-    ca.n = n;
-    hipLaunchKernelGGL(cond_bwd_wgrad_kernel, dim3(kCbD / 32, kCbD / 32, 2), dim3(256), 0, st, ca);
-    LAUNCH_CHECK();
-  } else {
-    TRY(linear_wgrad(s_tw2, k.dc, kD, s.sth, kD, n, kD, kD, g->t_w2, k_tw2, g->t_b2));
-    TRY(linear_dgrad(st, k.dc, kD, w->t_w2, n, kD, kD, k.dsth, kD, false, k));
-    hipLaunchKernelGGL(silu_bwd_kernel, dim3(ew_grid((long)n * kD)), dim3(256), 0, st, k.dsth, s.th, k.dth, (long)n * kD);
-    LAUNCH_CHECK();
-    TRY(linear_wgrad(st, k.dth, kD, s.freq, 256, n, kD, 256, g->t_w0, k, g->t_b0));
-  }
+  TRY(linear_wgrad(s_tw2, k.dc, kD, s.sth, kD, n, kD, kD, g->t_w2, k_tw2, g->t_b2));
+  TRY(linear_dgrad(st, k.dc, kD, w->t_w2, n, kD, kD, k.dsth, kD, false, k));
+  hipLaunchKernelGGL(silu_bwd_kernel, dim3(ew_grid((long)n * kD)), dim3(256), 0, st, k.dsth, s.th, k.dth, (long)n * kD);
+  LAUNCH_CHECK();
+  TRY(linear_wgrad(st, k.dth, kD, s.freq, 256, n, kD, 256, g->t_w0, k, g->t_b0));
   if (s_emb != st && s_emb != s_in) TRY(fused::join_side(h, st, 0));
   if (s_in != st) TRY(fused::join_side(h, st, 0));
   if (s_ada != st) TRY(fused::join_side(h, st, 1));
-  if (h->wgrad_reduce_on_side) {   // the layers' deferred weight-gradient reduction (fused::backward_layers)
-    h->wgrad_reduce_on_side = false;
-    TRY(fused::join_side(h, st, 2));
-  }
   if (f16) TRY(fused::unscale_grads(h, g, dx_out, (long)T * din, fs, st));
   TRY(fire(SCLDM_GRAD_END, 0));
   h->grad_events.clear();

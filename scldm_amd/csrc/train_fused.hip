@@ -306,26 +306,6 @@ __global__ void wgrad_reduce_kernel(const ReduceArgs g) {
   }
 }
 
-// The same for up to eight layers in ONE launch (blockIdx.y = layer): at batches whose backward kernel fills the chip the eight
-// per-layer reductions (10 us each + a launch gap, in series between backward layers) leave the layer loop - every layer keeps its
-// own partial block and they are summed behind the last layer (round 6; opt-in SCLDM_TRAIN_WGRAD_DEFER=1: measured +-0 to slower, below).
-struct ReduceAll { ReduceArgs layer[8]; };
-__global__ void wgrad_reduce_all_kernel(const ReduceAll all) {
-  const ReduceArgs& g = all.layer[blockIdx.y];
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < g.total; i += (long)gridDim.x * blockDim.x) {
-    int ji = 0;
-#pragma unroll
-    for (int k = 1; k < 7; ++k)
-      if (k < g.n_jobs && i >= g.job[k].first) ji = k;
-    const ReduceJob& j = g.job[ji];
-    const long e = i - j.first, mn = (long)j.M * j.N;
-    float s = 0.f;
-    for (int z = 0; z < g.splits; ++z) s += g.part[j.part_off + z * mn + e];
-    j.dst[(e / j.N) * j.ldc + (e % j.N)] = s;
-  }
-}
-static_assert(sizeof(ReduceAll) <= 4000, "kernel arguments must stay under 4 KB");
-
 __global__ void iota32_kernel(int32_t* __restrict__ ri, int n) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s < n) ri[s] = s;
@@ -623,13 +603,7 @@ Scratch carve_scratch(const scldm_dit* h, int n, void* base) {
   s.e_set_elems = (c.off - set_off0) / sizeof(__bf16);
   s.e_set1 = pad4(n) / 4 <= kOverlapTiles ? c.take<__bf16>(s.e_set_elems) : nullptr;
   s.part_floats = part_floats(h);
-  // one partial block per layer where the per-layer reductions are deferred to the end of the layer loop (no second operand-pair set:
-  // the backward kernel fills the chip), one block otherwise
-  static const bool defer_on = [] { const char* e = getenv("SCLDM_TRAIN_WGRAD_DEFER"); return e && e[0] == '1'; }();
-  s.part_layers = (s.e_set1 || !defer_on) ? 1 : h->cfg.n_layer;
-  // (+ one more block when deferring: the backward's tail borrows a block for the split-K partials of d t_w2 while the deferred
-  // reduction is still reading the layers' blocks on its side stream)
-  s.part = c.take<float>(s.part_floats * (size_t)(s.part_layers + (s.part_layers > 1 ? 1 : 0)));
+  s.part = c.take<float>(s.part_floats);
   s.ada_dw = c.take<float>((size_t)h->mod_w * (kD + 1));
   s.edge_part = c.take<float>(edge_part_floats(h));
   s.dout_s = c.take<float>(T * 32);
@@ -648,19 +622,6 @@ bool eligible(const scldm_dit* h, int n, int precision) {
          h->cfg.hidden_dim <= kHP && h->cfg.hidden_dim % 2 == 0 && h->lpl >= 1 && h->cfg.n_layer <= kMaxScatterLayers;
 }
 
-// side streams of the training step (experiment switch SCLDM_TRAIN_SIDE_PRIO=low: lowest HIP priority, so that what is queued on the
-// caller's stream - the step's critical path - wins the dispatcher when both have workgroups ready)
-static int make_side_stream(hipStream_t* s) {
-  static const bool low = [] { const char* e = getenv("SCLDM_TRAIN_SIDE_PRIO"); return e && e[0] == 'l'; }();
-  if (low) {
-    int least = 0, greatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(hipStreamCreateWithPriority(s, hipStreamNonBlocking, least));
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-  }
-  return SCLDM_OK;
-}
 // everything of a step that is not a kernel launch or an event: the pack-job tables of the live parameters, the side streams
 // and their events (scldm_dit_train_prepare calls it ahead of the first step; prepare() re-checks it per step for free)
 int prepare_tables(scldm_dit* h, const scldm_dit_weights* w, hipStream_t st) {
@@ -668,7 +629,7 @@ int prepare_tables(scldm_dit* h, const scldm_dit_weights* w, hipStream_t st) {
   if (rc) return rc;
   for (int k = 0; k < 3; ++k)
     if (!h->side[k]) {
-      { const int rc_s = make_side_stream(&h->side[k]); if (rc_s) return rc_s; }
+      HIP_TRY(hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking));
       HIP_TRY(hipEventCreateWithFlags(&h->join_ev[k], hipEventDisableTiming));
     }
   if (!h->fork_ev) HIP_TRY(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
@@ -682,24 +643,20 @@ int prepare(scldm_dit* h, const scldm_dit_weights* w, hipStream_t st, int precis
   // forked here, joined by prepare_join() before the first consumer of a packed copy.
   HIP_TRY(hipEventRecord(h->fork_ev, st));            // everything queued so far (the previous step's optimizer update) comes first
   HIP_TRY(hipStreamWaitEvent(h->side[0], h->fork_ev, 0));
-  // Two launches over the same job table: what the FORWARD reads first (its weight stream, biases, stacked adaLN copies - the main
-  // stream waits for these in prepare_join()), then the backward weight stream, which runs beside the adaLN GEMM and the recording
-  // forward and is awaited by the first backward layer (backward_join).  Measured +-0 (2.46 ms per step either way at 1 024 cells: the
-  // conditioning chain on the main stream takes as long as the whole pack), so the default stays ONE launch; SCLDM_TRAIN_PACK_SPLIT=1.
+  // ONE launch over the job table packs what the forward reads (its weight stream, biases, stacked adaLN copies) and the backward
+  // weight stream; prepare_join() and backward_join() wait for it.
   // bit 9: the backward stream is packed as fp16 (same buffer: it is re-packed every step, in the step's operand type)
-  static const bool split = [] { const char* e = getenv("SCLDM_TRAIN_PACK_SPLIT"); return e && e[0] == '1'; }();
   const unsigned bwd_bits = 0x100u | (precision == SCLDM_PREC_FP16 ? 0x200u : 0u);
-  rc = scldm_run_pack(h, true, (1u << precision) | (split ? 0u : bwd_bits), h->side[0]);
+  rc = scldm_run_pack(h, true, (1u << precision) | bwd_bits, h->side[0]);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->join_ev[0], h->side[0]));
-  if (split && (rc = scldm_run_pack(h, true, bwd_bits | 0x400u, h->side[0]))) return rc;
   HIP_TRY(hipEventRecord(h->bwd_pack_ev, h->side[0]));
   return SCLDM_OK;
 }
 // side stream k (created on first use) ordered after everything queued on `st` so far / `st` ordered after side stream k
 int fork_side(scldm_dit* h, hipStream_t st, int k, hipStream_t* out) {
   if (!h->side[k]) {
-    { const int rc_s = make_side_stream(&h->side[k]); if (rc_s) return rc_s; }
+    HIP_TRY(hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&h->join_ev[k], hipEventDisableTiming));
   }
   if (!h->fork_ev) HIP_TRY(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
@@ -911,7 +868,7 @@ SCLDM_BWD_POLICY(BwdFP16Small, bwdh32, _Float16, true);
 
 template <typename BW>
 static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float* mod, float* dmod, int n, const Record& rec, const Scratch& s,
-                             hipStream_t st, const std::function<int(int)>& after_layer) {
+                             hipStream_t st) {
   using E16 = typename BW::E;
   static bool attr_set[64] = {};   // (per instantiation)
   int dev = 0;
@@ -938,12 +895,6 @@ static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float
       if (!h->wg_ev[q]) HIP_TRY(hipEventCreateWithFlags(&h->wg_ev[q], hipEventDisableTiming));
   }
   const ptrdiff_t set_delta = overlap ? s.e_set1 - s.e_h1 : 0;
-  // MEASURED (round 6, same box, interleaved, 1 024 cells): one deferred launch on the main stream +-0 (2.019 / 2.000 against 2.013 / 2.015
-  // ms per step), on side stream 2 beside the tail 1.985 / 1.995 against 1.966 / 1.968 - SLOWER: the 200 MB pass competes with the tail's
-  // bandwidth-bound adaLN products.  The per-layer launches stay the default; SCLDM_TRAIN_WGRAD_DEFER=1 selects the deferred form.
-  const bool defer = !overlap && s.part_layers >= c.n_layer && c.n_layer > 1;
-  ReduceAll pending{};
-  int n_pending = 0;
   for (int l = c.n_layer - 1; l >= 0; --l) {
     const int set = overlap ? ((c.n_layer - 1 - l) & 1) : 0;
     const ptrdiff_t sd = set ? set_delta : 0;
@@ -972,10 +923,6 @@ static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float
     a.dbg = (want_dbg && tiles <= 16384) ? dbg_buf : nullptr;
     BW::launch(tiles, st, a);
     LAUNCH_CHECK();
-    if (after_layer) {
-      const int rc = after_layer(l);
-      if (rc) return rc;
-    }
     if (a.dbg) {
       HIP_TRY(hipStreamSynchronize(st));
       std::vector<unsigned long long> hst((size_t)tiles * BW::NW * 16);
@@ -1030,8 +977,7 @@ static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float
     wa.T = T;
     const int splits_req = h->wgrad_splits > 0 ? std::min(kSplits, h->wgrad_splits) : kSplitsDefault;
     wa.kchunk = cdiv(cdiv(T, splits_req), kWK) * kWK;
-    float* part_l = s.part + (defer ? (size_t)l * s.part_floats : 0);
-    wa.part = part_l;
+    wa.part = s.part;
     const int splits = cdiv(T, wa.kchunk);
     wa.splits = splits;
     wgrad_bf16_kernel<BW::kF16><<<tile0 * splits, 256, kWgradLds, sw>>>(wa);
@@ -1039,24 +985,9 @@ static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float
     ra.n_jobs = nr;
     ra.splits = splits;
     ra.total = first;
-    ra.part = part_l;
-    if (defer) {
-      pending.layer[n_pending++] = ra;
-      if (n_pending == 8 || l == 0) {
-        // on side stream 2, behind this layer's weight-gradient launch: nothing in the backward's tails reads a layer weight gradient, so
-        // the 200 MB pass (85 us for eight layers) runs beside them; scldm_dit_train_backward joins side 2 before its gradient events
-        hipStream_t sr = st;
-        const int rc = fork_side(h, st, 2, &sr);
-        if (rc) return rc;
-        wgrad_reduce_all_kernel<<<dim3((unsigned)std::min<long>(cdiv(first, 256), 1024), n_pending), 256, 0, sr>>>(pending);
-        LAUNCH_CHECK();
-        h->wgrad_reduce_on_side = true;
-        n_pending = 0;
-      }
-    } else {
-      wgrad_reduce_kernel<<<(unsigned)std::min<long>(cdiv(first, 256), 4096), 256, 0, sw>>>(ra);
-      LAUNCH_CHECK();
-    }
+    ra.part = s.part;
+    wgrad_reduce_kernel<<<(unsigned)std::min<long>(cdiv(first, 256), 4096), 256, 0, sw>>>(ra);
+    LAUNCH_CHECK();
     if (overlap) HIP_TRY(hipEventRecord(h->wg_ev[set], sw));
   }
   if (overlap) {   // every weight gradient is final before the caller's tails / gradient events
@@ -1067,16 +998,16 @@ static int backward_layers_t(scldm_dit* h, const scldm_dit_grads* g, const float
 }
 
 int backward_layers(scldm_dit* h, const scldm_dit_grads* g, const float* mod, float* dmod, int n, const Record& rec, const Scratch& s,
-                    hipStream_t st, int precision, const std::function<int(int)>& after_layer) {
+                    hipStream_t st, int precision) {
   // <= 320 cells: 32-token tiles (the same switch as the recording forward's, SCLDM_TRAIN_SMALL_NTT=0: off).  Measured per launch:
   // 256 cells 83 -> 71 us; at 512 cells the 256 half tiles take every CU, 93 us either way, and the weight gradients of the next layer
   // no longer find room beside them (graphed step 1.73 -> 1.75 ms) - so the rule stops where the side-stream overlap needs the CUs.
   static const bool small_ok = [] { const char* e = getenv("SCLDM_TRAIN_SMALL_NTT"); return !(e && e[0] == '0'); }();
   if (small_ok && pad4(n) / 4 * 2 <= kOverlapTiles)
-    return precision == SCLDM_PREC_FP16 ? backward_layers_t<BwdFP16Small>(h, g, mod, dmod, n, rec, s, st, after_layer)
-                                        : backward_layers_t<BwdBF16Small>(h, g, mod, dmod, n, rec, s, st, after_layer);
-  return precision == SCLDM_PREC_FP16 ? backward_layers_t<BwdFP16>(h, g, mod, dmod, n, rec, s, st, after_layer)
-                                      : backward_layers_t<BwdBF16>(h, g, mod, dmod, n, rec, s, st, after_layer);
+    return precision == SCLDM_PREC_FP16 ? backward_layers_t<BwdFP16Small>(h, g, mod, dmod, n, rec, s, st)
+                                        : backward_layers_t<BwdBF16Small>(h, g, mod, dmod, n, rec, s, st);
+  return precision == SCLDM_PREC_FP16 ? backward_layers_t<BwdFP16>(h, g, mod, dmod, n, rec, s, st)
+                                      : backward_layers_t<BwdBF16>(h, g, mod, dmod, n, rec, s, st);
 }
 
 int scale_dout(scldm_dit* h, const float* dout, long n_elem, const Scratch& s, hipStream_t st) {

@@ -1,5 +1,5 @@
 // C ABI of the TransformerVAE training step (scldm_vae_train_*, scldm_nb_loglik*; see include/scldm_hip.h): host-side
-// sequencing of the kernels in vae_train.hpp.  The forward is the inference path (mcab.hpp) with two extra outputs; the backward
+// sequencing of the kernels in vae_train.hpp and vae_train_wide.hpp.  The forward is the inference path (mcab.hpp) with two extra outputs; the backward
 // reads the parameters LIVE from the caller's tensors (PyTorch layouts) and writes every gradient in the same layout.
 #include <algorithm>
 #include <atomic>
@@ -23,9 +23,9 @@ struct Carver {
   }
 };
 
-// tiles of 64 tokens per workgroup / workgroups per cell of the two gene-axis kernels: about 2048 workgroups in flight, so that
+// tiles of 64 tokens per workgroup / workgroups per cell of the two gene-axis kernels: about `wgs` workgroups in flight, so that
 // one partial per workgroup stays small next to the work it summarises
-void split_tiles(int n_tok, int B, int* tiles, int* chunks, int wgs = 2048) {
+void split_tiles(int n_tok, int B, int* tiles, int* chunks, int wgs) {
   const int per_cell = cdiv(n_tok, 64);
   const int want = std::max(1, std::min(per_cell, wgs / std::max(B, 1)));
   *tiles = cdiv(per_cell, want);
@@ -43,39 +43,16 @@ Saved carve_saved(int B, void* base) {
   return s;
 }
 
-// SCLDM_VAE_CELL_WIDE=0: the first version of the cell-side kernels (one token per lane, four cells per wave) for A/B runs
-bool cell_wide() {
-  static const bool on = [] { const char* e = getenv("SCLDM_VAE_CELL_WIDE"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// SCLDM_VAE_GENE_WIDE=0: the first version of the gene-axis backward kernels (one token per lane)
-bool gene_wide() {
-  static const bool on = [] { const char* e = getenv("SCLDM_VAE_GENE_WIDE"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// SCLDM_VAE_GENE_MFMA: 2 (default): every contraction of the per-gene chain on the matrix pipe; 1: the MLP and the weight gradients
-// only; 0: the VALU form
-int gene_mfma() {
-  static const int v = [] { const char* e = getenv("SCLDM_VAE_GENE_MFMA"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2; }();
-  return v;
-}
-
-// precision of a training step: fp32 (exact), or fp16 (fp16 operands of the per-gene MCAB contractions, forward and backward), which
-// exists for the default kernel generations only
+// precision of a training step: fp32 (exact), or fp16 (fp16 operands of the per-gene MCAB contractions, forward and backward)
 int check_train_precision(int precision) {
   if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_FP16)
     return fail(SCLDM_ERR_SHAPE, "unsupported VAE training precision %d (SCLDM_PREC_FP32 or SCLDM_PREC_FP16)", precision);
-  if (precision == SCLDM_PREC_FP16 && (gene_mfma() != 2 || !gene_wide() || !cell_wide()))
-    return fail(SCLDM_ERR_STATE, "fp16 VAE training needs the default kernel generations: unset SCLDM_VAE_GENE_MFMA, SCLDM_VAE_GENE_WIDE "
-                                 "and SCLDM_VAE_CELL_WIDE (they select earlier fp32-only kernels)");
   return SCLDM_OK;
 }
 
 struct Ws {
   float *wct, *Q, *dQ, *xs_enc, *xs_dec, *ysave, *kv, *dl, *dz_dec, *dao, *dgq, *bsum, *p_gene, *p_dkv, *p_dcell, *p_ecell, *p_pool, *dl_scale;
-  int tilesD, chunksD, tilesE, chunksE, quads, cparts;
+  int tilesD, chunksD, tilesE, chunksE;
   size_t bytes;
 };
 Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
@@ -83,14 +60,13 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   const int L = c.n_layer;
   Carver k{reinterpret_cast<char*>(base)};
   Ws w;
-  // (the second version's workgroups are four waves, two per CU: one full round of 512 measured best at batch 32 - per-gene kernel
+  // (the workgroups are four waves, two per CU: one full round of 512 measured best at batch 32 - per-gene kernel
   // 606 us against 633-645 us with 1 024-4 096 workgroups, pooling 123 us against 130-138 us - and equal at batch 512;
   // SCLDM_VAE_GENE_WGS / SCLDM_VAE_POOL_WGS override the target counts)
   static const int wgs_d = [] { const char* e = getenv("SCLDM_VAE_GENE_WGS"); return e ? atoi(e) : 512; }();
   static const int wgs_e = [] { const char* e = getenv("SCLDM_VAE_POOL_WGS"); return e ? atoi(e) : 512; }();
-  split_tiles(G, B, &w.tilesD, &w.chunksD, gene_wide() ? wgs_d : 2048);
-  split_tiles(S, B, &w.tilesE, &w.chunksE, gene_wide() ? wgs_e : 2048);
-  w.quads = cdiv(B, 4);
+  split_tiles(G, B, &w.tilesD, &w.chunksD, wgs_d);
+  split_tiles(S, B, &w.tilesE, &w.chunksE, wgs_e);
   w.wct = k.take((size_t)(2 + 2 * L) * kHP * 32);
   w.Q = k.take(512);
   w.dQ = k.take(512);
@@ -105,9 +81,8 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   w.bsum = k.take((size_t)B);
   w.p_gene = k.take((size_t)B * w.chunksD * DP_SIZE);
   w.p_dkv = k.take((size_t)B * w.chunksD * kT * 64);
-  w.cparts = cell_wide() ? B : w.quads;     // cell-side partials: one per cell (vae_train_wide.hpp) or one per four cells
-  w.p_dcell = k.take((size_t)w.cparts * dc_size(L));
-  w.p_ecell = k.take((size_t)w.cparts * ec_size(L));
+  w.p_dcell = k.take((size_t)B * dc_size(L));      // cell-side partials: one per cell
+  w.p_ecell = k.take((size_t)B * ec_size(L));
   w.p_pool = k.take((size_t)B * w.chunksE * EP_SIZE);
   w.dl_scale = k.take((size_t)B);      // fp16: per-cell power of two of dl (head_bwd_kernel<true>)
   w.bytes = k.off;
@@ -267,7 +242,6 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   ea.w_lat = w->enc_latent_w; ea.xsave = k.xs_enc; ea.ysave = k.ysave;
   ea.dz_a = k.dz_dec; ea.dz_b = dz; ea.dao = k.dao; ea.dgq = k.dgq; ea.part = k.p_ecell;
   ea.B = B; ea.n_lat = nl; ea.n_layer = L; ea.eps = eps;
-  const bool wd = cell_wide();
   {   // (the attribute is per device: a process that drives several GPUs sets it on each)
     static std::atomic<bool> attr_set[64];
     int dev = 0;
@@ -277,8 +251,6 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
                             (const void*)wide::dec_cell_bwd_kernel})
         HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, wide::LDS_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::enc_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::PB_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::G_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
@@ -308,18 +280,14 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
       if (hipEventRecord(h->ev_fork, h->side) == hipSuccess) (void)hipStreamWaitEvent(st, h->ev_fork, 0);
     }
   } join_side{h, st, overlap};
-  if (wd) {
-    wide::enc_cell_fwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, s2>>>(ea);
-  } else enc_cell_fwd_kernel<<<k.quads, 64, 0, s2>>>(ea);
+  wide::enc_cell_fwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, s2>>>(ea);
   LAUNCH_CHECK();
   DecCellTrainArgs da{};
   da.z = z; da.w_in = w->dec_latent_w; da.blocks = blocks_of(w->dec_blocks, L, wct(2 + L), H);
   da.cln1_w = w->dec_cross.ln1_w; da.cln1_b = w->dec_cross.ln1_b; da.wkv = w->dec_cross.attn_kv;
   da.xsave = k.xs_dec; da.kv = k.kv; da.dkv_part = k.p_dkv; da.chunks = k.chunksD; da.dz = k.dz_dec; da.part = k.p_dcell;
   da.B = B; da.n_lat = nl; da.n_layer = L; da.eps = eps;
-  if (wd) wide::dec_cell_fwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, s2>>>(da);
-  else if (nl <= 16) dec_cell_fwd_kernel<16><<<k.quads, 64, 0, s2>>>(da);
-  else dec_cell_fwd_kernel<32><<<k.quads, 64, 0, s2>>>(da);
+  wide::dec_cell_fwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, s2>>>(da);
   LAUNCH_CHECK();
   if (overlap) HIP_TRY(hipEventRecord(h->ev_join, s2));
   // ---- NB head, then the per-gene decoder chain
@@ -332,34 +300,25 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   ga.ln2_w = w->dec_cross.ln2_w; ga.ln2_b = w->dec_cross.ln2_b; ga.head_w = w->head_w;
   ga.mlp = mlp_of(w->dec_cross.w1, w->dec_cross.w2, wct(1), H);
   ga.g_emb = g_emb; ga.part = k.p_gene; ga.dkv_part = k.p_dkv; ga.G = G; ga.tiles = k.tilesD; ga.eps = eps;
-  const int gene_mfma = ::gene_mfma();
-  if (f16) {    // (check_train_precision: the default generations)
+  if (f16) {
     ga.dl_scale = k.dl_scale;
     ga.found_inf = h->found_inf;
     wide::dec_gene_bwd_mfma2_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
-  } else if (gene_wide() && gene_mfma == 2) wide::dec_gene_bwd_mfma2_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
-  else if (gene_wide() && gene_mfma) wide::dec_gene_bwd_mfma_kernel<<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
-  else if (gene_wide()) wide::dec_gene_bwd_kernel<<<dim3(k.chunksD, B), wide::kThreads, wide::G_BYTES, st>>>(ga);
-  else dec_gene_bwd_kernel<<<dim3(k.chunksD, B), 64, 0, st>>>(ga);
+  } else wide::dec_gene_bwd_mfma2_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
   LAUNCH_CHECK();
   if (overlap) {
     HIP_TRY(hipEventRecord(h->ev_gene, st));
     HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
   }
-  if (wd) wide::dec_cell_bwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, st>>>(da);
-  else if (nl <= 16) dec_cell_bwd_kernel<16><<<k.quads, 64, 0, st>>>(da);
-  else dec_cell_bwd_kernel<32><<<k.quads, 64, 0, st>>>(da);
+  wide::dec_cell_bwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, st>>>(da);
   LAUNCH_CHECK();
-  if (wd) wide::enc_cell_bwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, st>>>(ea);
-  else if (nl <= 16) enc_cell_bwd_kernel<16><<<k.quads, 64, 0, st>>>(ea);
-  else enc_cell_bwd_kernel<32><<<k.quads, 64, 0, st>>>(ea);
+  wide::enc_cell_bwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, st>>>(ea);
   LAUNCH_CHECK();
   EncPoolBwdArgs pa{};
   pa.counts = counts_subset; pa.genes = genes_subset; pa.emb = w->gene_embedding;
   pa.ln1_w = w->enc_cross.ln1_w; pa.ln1_b = w->enc_cross.ln1_b; pa.wkv = w->enc_cross.attn_kv; pa.Q = k.Q; pa.lse2 = sv.lse2;
   pa.dao = k.dao; pa.dgq = k.dgq; pa.g_emb = g_emb; pa.part = k.p_pool; pa.S = S; pa.tiles = k.tilesE; pa.eps = eps;
-  if (gene_wide()) wide::enc_pool_bwd_kernel<<<dim3(k.chunksE, B), wide::kThreads, wide::PB_BYTES, st>>>(pa);
-  else enc_pool_bwd_kernel<<<dim3(k.chunksE, B), 64, 0, st>>>(pa);
+  wide::enc_pool_bwd_kernel<<<dim3(k.chunksE, B), wide::kThreads, wide::PB_BYTES, st>>>(pa);
   LAUNCH_CHECK();
 
   // ---- partial sums -> parameter gradients
@@ -391,7 +350,7 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
     j.vec(G_(g->dec_cross.ln1_w), dc_off_cln1w(L), 32);
     j.vec(G_(g->dec_cross.ln1_b), dc_off_cln1b(L), 32);
     j.mat(G_(g->dec_latent_w), dc_off_win(L), 32, nl, 32, nl);
-    if ((rc = j.run(k.p_dcell, k.cparts, dc_size(L), st))) return rc;
+    if ((rc = j.run(k.p_dcell, B, dc_size(L), st))) return rc;
   }
   {
     Jobs j;   // encoder cell side
@@ -405,7 +364,7 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
     j.vec(G_(gc.ln2_b), ec_off_ln2b(L), 32);
     j.mat(G_(g->enc_latent_w), ec_off_wlat(L), nl, 32, 32, 32);
     j.vec(G_(g->inducing_points), ec_off_ind(L), 512);
-    if ((rc = j.run(k.p_ecell, k.cparts, ec_size(L), st))) return rc;
+    if ((rc = j.run(k.p_ecell, B, ec_size(L), st))) return rc;
   }
   {
     Jobs j;   // encoder pooling

@@ -1,10 +1,9 @@
-// The 16-token side of a cell in the VAE training backward (row V1), second version: ONE WORKGROUP OF 256 THREADS PER CELL.
+// The heavy kernels of the VAE training backward (row V1): the two 16-token cell sides, the encoder pooling and the decoder's
+// per-gene chain (each section below has its own header).  First the 16-token side of a cell: ONE WORKGROUP OF 256 THREADS PER CELL.
 //   trunk Blocks                               src/scldm/layers.py:222-226 (x += c_proj(attn(LN_1 x)); x += MLP(LN_2 x); 8 heads x 4)
 //   encoder ends (c_proj of the pooling, LN_2, MLP, pos, latent Linear + LN)   layers.py:326-330, nnets.py:139-144
 //   decoder ends (LN, latent Linear, K|V = c_attn(LN_1 h))                     nnets.py:196-208, layers.py:312-318
-// The first version (vae_train.hpp: one token per lane, four cells per wave, weights as SGPR operands) walks eight layers in one
-// wave: at batch 32 that is 8 waves on 1 024 SIMDs, 3.3-3.7 ms per kernel whatever the batch, with 3.4-4.4 k spilled registers.
-// Here a token is spread over 16 lanes (a DPP row: LayerNorm statistics are row rotations), a cell's 16 tokens over the four waves
+// A token is spread over 16 lanes (a DPP row: LayerNorm statistics are row rotations), a cell's 16 tokens over the four waves
 // of a workgroup, and every operand lives in LDS:
 //   * a layer's five weight matrices (50 KB, rows padded to 36 floats) are copied into LDS once per layer by all 256 threads,
 //     the next layer's copy in flight (registers) while the current layer's weight gradients are contracted;
@@ -777,13 +776,13 @@ __global__ __launch_bounds__(kThreads) void enc_cell_bwd_kernel(const EncCellTra
 }
 
 // =================================================================================================================================
-// Encoder MCAB pooling backward, key side (layers.py:111-118, 248-264, 325-326), second version: 16 lanes per gene token, four
+// Encoder MCAB pooling backward, key side (layers.py:111-118, 248-264, 325-326): 16 lanes per gene token, four
 // tokens per wave, the four waves of a workgroup independent (no workgroup barrier inside the token loop).
 //   x = E[gene] log1p(count); xn = LN_1(x); k | v = c_attn xn; p[i][h] = exp2(log2e / sqrt 8 * Q[i][h] . k[h] - lse2[i][h])
 // Sums over tokens (d c_attn 64 x 32, dQ 64 x 8, LN_1's vectors) are contracted per wave over its four tokens into 41 registers
 // per lane that live across the whole token range; the four waves are added through LDS in wave order at the end (deterministic).
 // grid = (chunks, B); partial per workgroup: EP_* of vae_train.hpp (only the block-diagonal entries of EP_DQ are written - the only
-// ones fold_dq_kernel reads).  Gene-embedding gradient by atomics, as before.
+// ones fold_dq_kernel reads).  Gene-embedding gradient by atomics.
 // =================================================================================================================================
 constexpr int kP64 = 68;                                   // floats per 64-wide row
 constexpr int PB_W = 0, PB_Q = PB_W + 64 * kP, PB_DAO = PB_Q + 16 * kP, PB_LSE = PB_DAO + 16 * kP, PB_DG = PB_LSE + 64, PB_WAVE = PB_DG + 64;
@@ -918,8 +917,9 @@ __global__ __launch_bounds__(kThreads) void enc_pool_bwd_kernel(const EncPoolBwd
 }
 
 // =================================================================================================================================
-// Decoder MCAB, per-gene chain backward (layers.py:305-330 with q = gene embeddings, nnets.py:206-208; NB logit head), second
-// version: 16 lanes per decoded gene, 16 genes per workgroup step, two workgroups per CU.
+// Decoder MCAB, per-gene chain backward (layers.py:305-330 with q = gene embeddings, nnets.py:206-208; NB logit head): 16 genes per
+// workgroup step, every contraction on the matrix pipe (exact fp32: v_mfma_f32_16x16x4_f32, the step's 16 genes on one axis; fp16
+// operands under F16), two workgroups per CU.
 //   q0 = E[gene]; qn = LN_1q(q0); qq = Wq qn; ao = softmax(qq K^T / sqrt 8) V (4 heads x 8, 16 latent keys of the cell);
 //   y = q0 + Wp ao; h2 = LN_2(y); yo = y + Wc (silu(W1 h2) * W2 h2); logit = w_head . yo + b
 // What makes it cheap: the gradient entering the MLP is RANK ONE per gene, d yo = dlogit * w_head.  So
@@ -928,571 +928,38 @@ __global__ __launch_bounds__(kThreads) void enc_pool_bwd_kernel(const EncPoolBwd
 //   d w_head = sum dlogit * y + Wc c  (the MLP's forward output is never formed),
 // and Wc leaves the per-gene path altogether.  Token-axis sums that are plain column sums (LN vectors, head, c) are running sums in
 // the lanes' own registers, folded over the 16 gene slots once at the end; the outer products (d Wq, d Wp, d W1, d W2, dK | dV of
-// the cell) are contracted over the step's 16 genes from LDS rows into 36 accumulator registers per thread that live across the
-// whole gene range.  grid = (chunks, B); partial per workgroup: DP_* of vae_train.hpp, dkv_part as before; dE[gene] by atomics.
-// =================================================================================================================================
-constexpr int G_WQ = 0, G_WP = G_WQ + 32 * kP, G_W1 = G_WP + 32 * kP, G_W2 = G_W1 + 96 * kP, G_KV = G_W2 + 96 * kP;
-constexpr int G_QN = G_KV + 16 * kP64, G_QQ = G_QN + 16 * kP, G_AO = G_QQ + 16 * kP, G_H2 = G_AO + 16 * kP, G_DY = G_H2 + 16 * kP,
-              G_DAO = G_DY + 16 * kP, G_DQQ = G_DAO + 16 * kP, G_TX = G_DQQ + 16 * kP, G_DA = G_TX + 16 * kP, G_DB = G_DA + 16 * kQ,
-              G_PP = G_DB + 16 * kQ, G_DS = G_PP + 16 * kP64, G_FLOATS = G_DS + 16 * kP64;
-constexpr int G_BYTES = G_FLOATS * 4;
-static_assert(G_BYTES <= 80 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ float quad_max(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false)));
-  return v;
-}
-// acc[m] += sum_t DY[t][oo + 32 m] X[t][4 i4 ..]
-template <int OUT>
-__device__ __forceinline__ void wgrad_acc(const float* __restrict__ DY, int py, const float* __restrict__ X, f32x4* __restrict__ acc, int tid) {
-  const int i4 = tid & 7, oo = tid >> 3;
-#pragma unroll 4
-  for (int t = 0; t < kT; ++t) {
-    const f32x4 xv = *v4(X + t * kP + 4 * i4);
-#pragma unroll
-    for (int m = 0; m < OUT / 32; ++m) acc[m] = fma4(DY[t * py + oo + 32 * m], xv, acc[m]);
-  }
-}
-
-__global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_kernel(const DecBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float S[];
-  const int tid = threadIdx.x, tok = tid >> 4, j = tid & 15, chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
-  constexpr float kScale = 0.35355339059327373f;   // 1 / sqrt(8)
-  const int H = a.mlp.H;
-  {
-    RowCopy<32> cq, cp;
-    RowCopy<96> c1, c2;
-    cq.load(a.wq, 32, tid); cp.load(a.wp, 32, tid); c1.load(a.mlp.w1, H, tid); c2.load(a.mlp.w2, H, tid);
-    cq.store(S + G_WQ, tid); cp.store(S + G_WP, tid); c1.store(S + G_W1, tid); c2.store(S + G_W2, tid);
-    for (int idx = tid; idx < kT * 64; idx += kThreads) S[G_KV + (idx >> 6) * kP64 + (idx & 63)] = a.kv[(size_t)cell * (kT * 64) + idx];
-  }
-  // c0[u] = sum_i Wc[i][u] w_head[i] for this lane's hidden units u = j + 16 m (zero beyond H)
-  float c0[6];
-#pragma unroll
-  for (int m = 0; m < 6; ++m) {
-    const int u = j + 16 * m;
-    float s = 0.f;
-    if (u < H)
-      for (int i = 0; i < 32; ++i) s = fmaf(a.mlp.wct[u * 32 + i], a.head_w[i], s);
-    c0[m] = s;
-  }
-  const float l1w0 = a.ln1q_w[j], l1w1 = a.ln1q_w[j + 16], l1b0 = a.ln1q_b[j], l1b1 = a.ln1q_b[j + 16];
-  const float l2w0 = a.ln2_w[j], l2w1 = a.ln2_w[j + 16], l2b0 = a.ln2_b[j], l2b1 = a.ln2_b[j + 16];
-  const float hw0 = a.head_w[j], hw1 = a.head_w[j + 16];
-  __syncthreads();
-  f32x4 gq[1] = {z4()}, gp[1] = {z4()}, g1[3] = {z4(), z4(), z4()}, g2[3] = {z4(), z4(), z4()}, gkv = z4();
-  float vs[16];       // running sums of this lane's gene slot: ln1q w|b, ln2 w|b, head (two features each), c (six hidden units)
-#pragma unroll
-  for (int i = 0; i < 16; ++i) vs[i] = 0.f;
-  const int h = j >> 2, jq = j & 3;
-  const int begin = chunk * a.tiles * 64, end = min(a.G, begin + a.tiles * 64);
-  for (int g0 = begin; g0 < end; g0 += 16) {
-    const int g = g0 + tok;
-    const bool valid = g < end;
-    const size_t gi = (size_t)cell * a.G + (valid ? g : end - 1);
-    const long long gene = a.genes[gi];
-    const float dlog = valid ? a.dl[gi] : 0.f;
-    const float* e = a.emb + (size_t)gene * 32;
-    const float q00 = e[j], q01 = e[j + 16];
-    const Ln n1 = ln_own(q00, q01, a.eps);
-    S[G_QN + tok * kP + j] = fmaf(n1.h0, l1w0, l1b0);
-    S[G_QN + tok * kP + j + 16] = fmaf(n1.h1, l1w1, l1b1);
-    tsync();
-    lin32<32>(S + G_WQ, S + G_QN + tok * kP, j, [&](int, int o, float v) { S[G_QQ + tok * kP + o] = v; });
-    tsync();
-    float p[4];
-    {
-      const f32x4 qa = *v4(S + G_QQ + tok * kP + 8 * h), qb = *v4(S + G_QQ + tok * kP + 8 * h + 4);
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float* K = S + G_KV + (4 * jq + kk) * kP64 + 8 * h;
-        p[kk] = (dot4(qa, *v4(K)) + dot4(qb, *v4(K + 4))) * kScale;
-        mx = fmaxf(mx, p[kk]);
-      }
-      mx = quad_max(mx);
-      float l = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) { p[kk] = __expf(p[kk] - mx); l += p[kk]; }
-      const float inv = 1.0f / quad_sum(l);
-      f32x4 aa = z4(), ab = z4();
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        p[kk] *= inv;
-        const float* V = S + G_KV + (4 * jq + kk) * kP64 + 32 + 8 * h;
-        aa = fma4(p[kk], *v4(V), aa);
-        ab = fma4(p[kk], *v4(V + 4), ab);
-      }
-      aa = quad_sum4(aa);
-      ab = quad_sum4(ab);
-      if (jq < 2) *v4(S + G_AO + tok * kP + 8 * h + 4 * jq) = jq == 0 ? aa : ab;
-      *v4(S + G_PP + tok * kP64 + h * 16 + 4 * jq) = f32x4{p[0], p[1], p[2], p[3]};
-    }
-    tsync();
-    float y0 = q00, y1 = q01;
-    lin32<32>(S + G_WP, S + G_AO + tok * kP, j, [&](int m, int, float v) { if (m == 0) y0 += v; else y1 += v; });
-    const Ln n2 = ln_own(y0, y1, a.eps);
-    S[G_H2 + tok * kP + j] = fmaf(n2.h0, l2w0, l2b0);
-    S[G_H2 + tok * kP + j + 16] = fmaf(n2.h1, l2w1, l2b1);
-    tsync();
-    {
-      float aa[6], bb[6];
-      lin32<96>(S + G_W1, S + G_H2 + tok * kP, j, [&](int m, int, float v) { aa[m] = v; });
-      lin32<96>(S + G_W2, S + G_H2 + tok * kP, j, [&](int m, int, float v) { bb[m] = v; });
-#pragma unroll
-      for (int m = 0; m < 6; ++m) {
-        const float s = sigm(aa[m]), sa = aa[m] * s, dh = dlog * c0[m];
-        vs[10 + m] = fmaf(dlog, sa * bb[m], vs[10 + m]);
-        S[G_DA + tok * kQ + j + 16 * m] = dh * bb[m] * (s * (1.0f + aa[m] * (1.0f - s)));
-        S[G_DB + tok * kQ + j + 16 * m] = dh * sa;
-      }
-    }
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<96>(S + G_W1, S + G_DA + tok * kQ, j, acc);
-      lin32_t_acc<96>(S + G_W2, S + G_DB + tok * kQ, j, acc);
-      acc = half_sum4(acc);
-      if (j < 8) *v4(S + G_TX + tok * kP + 4 * j) = acc;
-    }
-    tsync();
-    float d0, d1;
-    {
-      const float t0 = S[G_TX + tok * kP + j], t1 = S[G_TX + tok * kP + j + 16];
-      vs[4] = fmaf(t0, n2.h0, vs[4]); vs[5] = fmaf(t1, n2.h1, vs[5]); vs[6] += t0; vs[7] += t1;
-      vs[8] = fmaf(dlog, y0, vs[8]); vs[9] = fmaf(dlog, y1, vs[9]);
-      ln_back(n2, t0 * l2w0, t1 * l2w1, d0, d1);
-      d0 = fmaf(dlog, hw0, d0);
-      d1 = fmaf(dlog, hw1, d1);
-    }
-    S[G_DY + tok * kP + j] = d0;
-    S[G_DY + tok * kP + j + 16] = d1;
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<32>(S + G_WP, S + G_DY + tok * kP, j, acc);
-      acc = half_sum4(acc);
-      if (j < 8) *v4(S + G_DAO + tok * kP + 4 * j) = acc;
-    }
-    tsync();
-    {
-      const f32x4 da = *v4(S + G_DAO + tok * kP + 8 * h), db = *v4(S + G_DAO + tok * kP + 8 * h + 4);
-      float dp[4], dg = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float* V = S + G_KV + (4 * jq + kk) * kP64 + 32 + 8 * h;
-        dp[kk] = dot4(da, *v4(V)) + dot4(db, *v4(V + 4));
-        dg = fmaf(p[kk], dp[kk], dg);
-      }
-      dg = quad_sum(dg);
-      f32x4 qa = z4(), qb = z4(), dsv;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float ds = p[kk] * (dp[kk] - dg) * kScale;
-        dsv[kk] = ds;
-        const float* K = S + G_KV + (4 * jq + kk) * kP64 + 8 * h;
-        qa = fma4(ds, *v4(K), qa);
-        qb = fma4(ds, *v4(K + 4), qb);
-      }
-      qa = quad_sum4(qa);
-      qb = quad_sum4(qb);
-      if (jq < 2) *v4(S + G_DQQ + tok * kP + 8 * h + 4 * jq) = jq == 0 ? qa : qb;
-      *v4(S + G_DS + tok * kP64 + h * 16 + 4 * jq) = dsv;
-    }
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<32>(S + G_WQ, S + G_DQQ + tok * kP, j, acc);
-      acc = half_sum4(acc);
-      tsync();      // (G_TX of this gene was read above; the fence keeps the store below it)
-      if (j < 8) *v4(S + G_TX + tok * kP + 4 * j) = acc;
-    }
-    tsync();
-    {
-      const float t0 = S[G_TX + tok * kP + j], t1 = S[G_TX + tok * kP + j + 16];
-      vs[0] = fmaf(t0, n1.h0, vs[0]); vs[1] = fmaf(t1, n1.h1, vs[1]); vs[2] += t0; vs[3] += t1;
-      float o0, o1;
-      ln_back(n1, t0 * l1w0, t1 * l1w1, o0, o1);
-      if (valid && dlog != 0.f) {
-        float* ge = a.g_emb + (size_t)gene * 32;
-        atomicAdd(ge + j, d0 + o0);
-        atomicAdd(ge + j + 16, d1 + o1);
-      }
-    }
-    __syncthreads();
-    wgrad_acc<32>(S + G_DQQ, kP, S + G_QN, gq, tid);
-    wgrad_acc<32>(S + G_DY, kP, S + G_AO, gp, tid);
-    wgrad_acc<96>(S + G_DA, kQ, S + G_H2, g1, tid);
-    wgrad_acc<96>(S + G_DB, kQ, S + G_H2, g2, tid);
-    {   // dK | dV of the cell: thread = (key, four of the 64 columns)
-      const int key = tid >> 4, f4 = tid & 15, hh = (f4 & 7) >> 1;
-      const float* sc = S + (f4 < 8 ? G_DS : G_PP) + hh * 16 + key;
-      const float* vec = S + (f4 < 8 ? G_QQ : G_DAO) + 4 * (f4 & 7);
-#pragma unroll 4
-      for (int t = 0; t < kT; ++t) gkv = fma4(sc[t * kP64], *v4(vec + t * kP), gkv);
-    }
-    __syncthreads();
-  }
-  // ---- one partial per workgroup
-  float* P = a.part + (size_t)(cell * nch + chunk) * DP_SIZE;
-  {
-    const int i4 = tid & 7, oo = tid >> 3;
-    *v4(P + DP_WQ + oo * 32 + 4 * i4) = gq[0];
-    *v4(P + DP_WP + oo * 32 + 4 * i4) = gp[0];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      *v4(P + DP_W1 + (oo + 32 * m) * 32 + 4 * i4) = g1[m];
-      *v4(P + DP_W2 + (oo + 32 * m) * 32 + 4 * i4) = g2[m];
-    }
-    *v4(a.dkv_part + (size_t)(cell * nch + chunk) * (kT * 64) + (tid >> 4) * 64 + 4 * (tid & 15)) = gkv;
-  }
-  // the 16 gene slots' running sums: R[slot][16 values][16 lanes]
-  float* R = S;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) R[(tok * 16 + i) * 16 + j] = vs[i];
-  __syncthreads();
-  {
-    const int i = tid >> 4;       // value index, lane j
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < kT; ++t) s += R[(t * 16 + i) * 16 + j];
-    __syncthreads();
-    // feature / hidden-unit index of value i in lane j
-    if (i < 10) {
-      const int f = j + 16 * (i & 1);
-      const int off = i < 2 ? DP_LN1QW : i < 4 ? DP_LN1QB : i < 6 ? DP_LN2W : i < 8 ? DP_LN2B : -1;
-      if (off >= 0) P[off + f] = s;
-      else R[512 + f] = s;                       // head: sum dlogit * y (completed below)
-    } else R[j + 16 * (i - 10)] = s;             // c[u]
-  }
-  __syncthreads();
-  if (tid < 32) {
-    float s = R[512 + tid];
-    for (int u = 0; u < H; ++u) s = fmaf(a.mlp.wct[u * 32 + tid], R[u], s);
-    P[DP_HEADW + tid] = s;
-  }
-  for (int idx = tid; idx < 32 * kHP; idx += kThreads) P[DP_WC + idx] = a.head_w[idx / kHP] * R[idx % kHP];
-}
-
-// =================================================================================================================================
-// The same kernel with its heavy contractions on the matrix pipe (exact fp32: v_mfma_f32_16x16x4_f32, the step's 16 genes on one
-// axis).  The version above is LDS-bandwidth bound: every wave re-reads each weight piece for its four genes.  Here a step has five
-// phases separated by workgroup barriers:
-//   1  per gene (16 lanes each, as above): LN_1q, q, attention, c_proj, LN_2 -> rows QN, QQ, AO, PP, H2
+// the cell) are contracted over the step's 16 genes from LDS rows into accumulator registers that live across the whole gene range.
+// grid = (chunks, B); partial per workgroup: DP_* of vae_train.hpp, dkv_part[(cell * chunks + chunk)][16][64]; dE[gene] by atomics.
+// The MLP and the weight gradients of a step:
 //   A  a | b = W1 h2 | W2 h2 as 16 x 16 tiles D[gene][hidden unit] (wave w: unit tiles w, w + 4), SwiGLU gradient in place -> rows DA, DB
 //   B  d h2 = W1^T da + W2^T db: D[gene][feature], wave = (feature half, matrix); the two matrices' partials are added by the reader
-//   2  per gene: LN_2 backward, d y, d ao, attention backward, d q, LN_1q backward, dE[gene] atomics -> rows DY, DAO, DQQ, DS
 //   C  weight gradients as D[out][in] += sum_genes dy[gene][out] x[gene][in]: 8 + 2 tiles of 16 x 16 per wave (d W1, d W2, d Wq, d Wp,
 //      dK and dV of one head), accumulators in 40 registers across the whole gene range
-// An MFMA reads one scalar per lane and operand: 2 x 256 B of LDS per 2 048 FLOP.
-// =================================================================================================================================
-constexpr int M_DL = G_FLOATS, M_C0 = M_DL + 16, M_FLOATS = M_C0 + 96;
-constexpr int M_BYTES = M_FLOATS * 4;
-static_assert(M_BYTES <= 80 * 1024, "two workgroups per CU");
-__device__ __forceinline__ f32x4 mfma16(float x, float y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0); }
-
-__global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma_kernel(const DecBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float S[];
-  const int tid = threadIdx.x, tok = tid >> 4, j = tid & 15, chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
-  const int wave = tid >> 6, li = tid & 15, g4 = (tid & 63) >> 4;      // MFMA roles: lane = (li, g4)
-  constexpr float kScale = 0.35355339059327373f;   // 1 / sqrt(8)
-  const int H = a.mlp.H;
-  {
-    RowCopy<32> cq, cp;
-    RowCopy<96> c1, c2;
-    cq.load(a.wq, 32, tid); cp.load(a.wp, 32, tid); c1.load(a.mlp.w1, H, tid); c2.load(a.mlp.w2, H, tid);
-    cq.store(S + G_WQ, tid); cp.store(S + G_WP, tid); c1.store(S + G_W1, tid); c2.store(S + G_W2, tid);
-    for (int idx = tid; idx < kT * 64; idx += kThreads) S[G_KV + (idx >> 6) * kP64 + (idx & 63)] = a.kv[(size_t)cell * (kT * 64) + idx];
-    if (tid < 96) {      // c0[u] = sum_i Wc[i][u] w_head[i]
-      float s = 0.f;
-      if (tid < H)
-        for (int i = 0; i < 32; ++i) s = fmaf(a.mlp.wct[tid * 32 + i], a.head_w[i], s);
-      S[M_C0 + tid] = s;
-    }
-  }
-  const float l1w0 = a.ln1q_w[j], l1w1 = a.ln1q_w[j + 16], l1b0 = a.ln1q_b[j], l1b1 = a.ln1q_b[j + 16];
-  const float l2w0 = a.ln2_w[j], l2w1 = a.ln2_w[j + 16], l2b0 = a.ln2_b[j], l2b1 = a.ln2_b[j + 16];
-  const float hw0 = a.head_w[j], hw1 = a.head_w[j + 16];
-  __syncthreads();
-  f32x4 gw1[3] = {z4(), z4(), z4()}, gw2[3] = {z4(), z4(), z4()}, gq = z4(), gp = z4(), gk = z4(), gv = z4();
-  float cacc[2] = {0.f, 0.f};   // c[u] partials of this lane's gene quad, hidden-unit tiles wave, wave + 4
-  float vs[10];                 // running sums of this lane's gene slot: ln1q w|b, ln2 w|b, head (two features each)
-#pragma unroll
-  for (int i = 0; i < 10; ++i) vs[i] = 0.f;
-  const int h = j >> 2, jq = j & 3;
-  const int begin = chunk * a.tiles * 64, end = min(a.G, begin + a.tiles * 64);
-  for (int g0 = begin; g0 < end; g0 += 16) {
-    const int g = g0 + tok;
-    const bool valid = g < end;
-    const size_t gi = (size_t)cell * a.G + (valid ? g : end - 1);
-    const long long gene = a.genes[gi];
-    const float dlog = valid ? a.dl[gi] : 0.f;
-    if (j == 0) S[M_DL + tok] = dlog;
-    const float* e = a.emb + (size_t)gene * 32;
-    const float q00 = e[j], q01 = e[j + 16];
-    const Ln n1 = ln_own(q00, q01, a.eps);
-    S[G_QN + tok * kP + j] = fmaf(n1.h0, l1w0, l1b0);
-    S[G_QN + tok * kP + j + 16] = fmaf(n1.h1, l1w1, l1b1);
-    tsync();
-    lin32<32>(S + G_WQ, S + G_QN + tok * kP, j, [&](int, int o, float v) { S[G_QQ + tok * kP + o] = v; });
-    tsync();
-    float p[4];
-    {
-      const f32x4 qa = *v4(S + G_QQ + tok * kP + 8 * h), qb = *v4(S + G_QQ + tok * kP + 8 * h + 4);
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float* K = S + G_KV + (4 * jq + kk) * kP64 + 8 * h;
-        p[kk] = (dot4(qa, *v4(K)) + dot4(qb, *v4(K + 4))) * kScale;
-        mx = fmaxf(mx, p[kk]);
-      }
-      mx = quad_max(mx);
-      float l = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) { p[kk] = __expf(p[kk] - mx); l += p[kk]; }
-      const float inv = 1.0f / quad_sum(l);
-      f32x4 aa = z4(), ab = z4();
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        p[kk] *= inv;
-        const float* V = S + G_KV + (4 * jq + kk) * kP64 + 32 + 8 * h;
-        aa = fma4(p[kk], *v4(V), aa);
-        ab = fma4(p[kk], *v4(V + 4), ab);
-      }
-      aa = quad_sum4(aa);
-      ab = quad_sum4(ab);
-      if (jq < 2) *v4(S + G_AO + tok * kP + 8 * h + 4 * jq) = jq == 0 ? aa : ab;
-      *v4(S + G_PP + tok * kP64 + h * 16 + 4 * jq) = f32x4{p[0], p[1], p[2], p[3]};
-    }
-    tsync();
-    float y0 = q00, y1 = q01;
-    lin32<32>(S + G_WP, S + G_AO + tok * kP, j, [&](int m, int, float v) { if (m == 0) y0 += v; else y1 += v; });
-    const Ln n2 = ln_own(y0, y1, a.eps);
-    S[G_H2 + tok * kP + j] = fmaf(n2.h0, l2w0, l2b0);
-    S[G_H2 + tok * kP + j + 16] = fmaf(n2.h1, l2w1, l2b1);
-    __syncthreads();
-    // ---- phase A: a | b tiles D[gene 4 g4 + r][unit 16 ot + li], SwiGLU gradient in place
-    {
-      float hk[8];
-#pragma unroll
-      for (int s = 0; s < 8; ++s) hk[s] = S[G_H2 + li * kP + 4 * s + g4];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int ot = wave + 4 * q;
-        if (ot < 6) {
-          f32x4 aa = z4(), bb = z4();
-#pragma unroll
-          for (int s = 0; s < 8; ++s) {
-            aa = mfma16(hk[s], S[G_W1 + (16 * ot + li) * kP + 4 * s + g4], aa);
-            bb = mfma16(hk[s], S[G_W2 + (16 * ot + li) * kP + 4 * s + g4], bb);
-          }
-          const float c0u = S[M_C0 + 16 * ot + li];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int tk = 4 * g4 + r;
-            const float dl = S[M_DL + tk], sg = sigm(aa[r]), sa = aa[r] * sg, dh = dl * c0u;
-            cacc[q] = fmaf(dl, sa * bb[r], cacc[q]);
-            S[G_DA + tk * kQ + 16 * ot + li] = dh * bb[r] * (sg * (1.0f + aa[r] * (1.0f - sg)));
-            S[G_DB + tk * kQ + 16 * ot + li] = dh * sa;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // ---- phase B: d h2 partials, wave = (feature half it, matrix); W1's go to the TX rows, W2's to the DQQ rows (free until phase 2)
-    {
-      const int it = wave & 1, mtx = wave >> 1;
-      const float* Wm = S + (mtx ? G_W2 : G_W1);
-      const float* Dm = S + (mtx ? G_DB : G_DA);
-      // k slot (s, g4) <-> hidden unit u = 16 (s >> 2) + 4 g4 + (s & 3): the two weight rows a 32-lane group reads are 4 rows = 16 banks
-      // apart (4 s + g4 would put them 4 banks apart: two-way conflicts); two accumulator chains keep the pipe fed
-      f32x4 acc = z4(), acc2 = z4();
-#pragma unroll 6
-      for (int s = 0; s < 24; s += 2) {
-        const int u0 = 16 * (s >> 2) + 4 * g4 + (s & 3), u1 = u0 + 1;
-        acc = mfma16(Dm[li * kQ + u0], Wm[u0 * kP + 16 * it + li], acc);
-        acc2 = mfma16(Dm[li * kQ + u1], Wm[u1 * kP + 16 * it + li], acc2);
-      }
-      acc += acc2;
-      float* Pt = S + (mtx ? G_DQQ : G_TX);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Pt[(4 * g4 + r) * kP + 16 * it + li] = acc[r];
-    }
-    __syncthreads();
-    // ---- phase 2: per gene
-    float d0, d1;
-    {
-      const float t0 = S[G_TX + tok * kP + j] + S[G_DQQ + tok * kP + j], t1 = S[G_TX + tok * kP + j + 16] + S[G_DQQ + tok * kP + j + 16];
-      vs[4] = fmaf(t0, n2.h0, vs[4]); vs[5] = fmaf(t1, n2.h1, vs[5]); vs[6] += t0; vs[7] += t1;
-      vs[8] = fmaf(dlog, y0, vs[8]); vs[9] = fmaf(dlog, y1, vs[9]);
-      ln_back(n2, t0 * l2w0, t1 * l2w1, d0, d1);
-      d0 = fmaf(dlog, hw0, d0);
-      d1 = fmaf(dlog, hw1, d1);
-    }
-    S[G_DY + tok * kP + j] = d0;
-    S[G_DY + tok * kP + j + 16] = d1;
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<32>(S + G_WP, S + G_DY + tok * kP, j, acc);
-      acc = half_sum4(acc);
-      if (j < 8) *v4(S + G_DAO + tok * kP + 4 * j) = acc;
-    }
-    tsync();
-    {
-      const f32x4 da = *v4(S + G_DAO + tok * kP + 8 * h), db = *v4(S + G_DAO + tok * kP + 8 * h + 4);
-      float dp[4], dg = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float* V = S + G_KV + (4 * jq + kk) * kP64 + 32 + 8 * h;
-        dp[kk] = dot4(da, *v4(V)) + dot4(db, *v4(V + 4));
-        dg = fmaf(p[kk], dp[kk], dg);
-      }
-      dg = quad_sum(dg);
-      f32x4 qa = z4(), qb = z4(), dsv;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const float ds = p[kk] * (dp[kk] - dg) * kScale;
-        dsv[kk] = ds;
-        const float* K = S + G_KV + (4 * jq + kk) * kP64 + 8 * h;
-        qa = fma4(ds, *v4(K), qa);
-        qb = fma4(ds, *v4(K + 4), qb);
-      }
-      qa = quad_sum4(qa);
-      qb = quad_sum4(qb);
-      if (jq < 2) *v4(S + G_DQQ + tok * kP + 8 * h + 4 * jq) = jq == 0 ? qa : qb;
-      *v4(S + G_DS + tok * kP64 + h * 16 + 4 * jq) = dsv;
-    }
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<32>(S + G_WQ, S + G_DQQ + tok * kP, j, acc);
-      acc = half_sum4(acc);
-      if (j < 8) *v4(S + G_TX + tok * kP + 4 * j) = acc;
-    }
-    tsync();
-    {
-      const float t0 = S[G_TX + tok * kP + j], t1 = S[G_TX + tok * kP + j + 16];
-      vs[0] = fmaf(t0, n1.h0, vs[0]); vs[1] = fmaf(t1, n1.h1, vs[1]); vs[2] += t0; vs[3] += t1;
-      float o0, o1;
-      ln_back(n1, t0 * l1w0, t1 * l1w1, o0, o1);
-      if (valid && dlog != 0.f) {
-        float* ge = a.g_emb + (size_t)gene * 32;
-        atomicAdd(ge + j, d0 + o0);
-        atomicAdd(ge + j + 16, d1 + o1);
-      }
-    }
-    __syncthreads();
-    // ---- phase C: weight gradients, D[out 16 ot + 4 g4 + r][in 16 it + li] += sum_genes dy[gene][out] x[gene][in]
-    {
-#pragma unroll
-      for (int n = 0; n < 3; ++n) {
-        const int idx = wave + 4 * n, ot = idx >> 1, it = idx & 1;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int tk = s + 4 * g4;       // (k slot <-> gene: rows 4 apart = 16 banks apart within a 32-lane group: conflict-free)
-          const float x = S[G_H2 + tk * kP + 16 * it + li];
-          gw1[n] = mfma16(S[G_DA + tk * kQ + 16 * ot + li], x, gw1[n]);
-          gw2[n] = mfma16(S[G_DB + tk * kQ + 16 * ot + li], x, gw2[n]);
-        }
-      }
-      const int ot = wave >> 1, it = wave & 1;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int tk = s + 4 * g4;
-        gq = mfma16(S[G_DQQ + tk * kP + 16 * ot + li], S[G_QN + tk * kP + 16 * it + li], gq);
-        gp = mfma16(S[G_DY + tk * kP + 16 * ot + li], S[G_AO + tk * kP + 16 * it + li], gp);
-        // head `wave` of the cell's keys: D[key 4 g4 + r][column 16 (wave >> 1) + li], useful where (li >> 3) == (wave & 1)
-        gk = mfma16(S[G_DS + tk * kP64 + wave * 16 + li], S[G_QQ + tk * kP + 16 * (wave >> 1) + li], gk);
-        gv = mfma16(S[G_PP + tk * kP64 + wave * 16 + li], S[G_DAO + tk * kP + 16 * (wave >> 1) + li], gv);
-      }
-    }
-    __syncthreads();
-  }
-  // ---- one partial per workgroup
-  float* P = a.part + (size_t)(cell * nch + chunk) * DP_SIZE;
-  {
-#pragma unroll
-    for (int n = 0; n < 3; ++n) {
-      const int idx = wave + 4 * n, ot = idx >> 1, it = idx & 1;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        P[DP_W1 + (16 * ot + 4 * g4 + r) * 32 + 16 * it + li] = gw1[n][r];
-        P[DP_W2 + (16 * ot + 4 * g4 + r) * 32 + 16 * it + li] = gw2[n][r];
-      }
-    }
-    const int ot = wave >> 1, it = wave & 1;
-    float* DK = a.dkv_part + (size_t)(cell * nch + chunk) * (kT * 64);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      P[DP_WQ + (16 * ot + 4 * g4 + r) * 32 + 16 * it + li] = gq[r];
-      P[DP_WP + (16 * ot + 4 * g4 + r) * 32 + 16 * it + li] = gp[r];
-      if ((li >> 3) == (wave & 1)) {
-        DK[(4 * g4 + r) * 64 + 16 * (wave >> 1) + li] = gk[r];
-        DK[(4 * g4 + r) * 64 + 32 + 16 * (wave >> 1) + li] = gv[r];
-      }
-    }
-  }
-  // the 16 gene slots' running sums R[slot][10 values][16 lanes]; c partials RC[g4][96 units] of every wave's tiles
-  float* R = S;
-  float* RC = S + 16 * 10 * 16;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) R[(tok * 10 + i) * 16 + j] = vs[i];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    if (wave + 4 * q < 6) RC[g4 * 96 + 16 * (wave + 4 * q) + li] = cacc[q];
-  __syncthreads();
-  float sum = 0.f;
-  const int vi = tid >> 4;
-  if (vi < 10) {
-#pragma unroll
-    for (int t = 0; t < kT; ++t) sum += R[(t * 10 + vi) * 16 + j];
-  }
-  float cu = 0.f;
-  if (tid < 96) cu = (RC[tid] + RC[96 + tid]) + (RC[192 + tid] + RC[288 + tid]);
-  __syncthreads();
-  float* C = S;            // c[u]
-  float* HD = S + 128;     // sum dlogit * y
-  if (tid < 96) C[tid] = cu;
-  if (vi < 10) {
-    const int f = j + 16 * (vi & 1);
-    if (vi < 2) P[DP_LN1QW + f] = sum;
-    else if (vi < 4) P[DP_LN1QB + f] = sum;
-    else if (vi < 6) P[DP_LN2W + f] = sum;
-    else if (vi < 8) P[DP_LN2B + f] = sum;
-    else HD[f] = sum;
-  }
-  __syncthreads();
-  if (tid < 32) {
-    float s2 = HD[tid];
-    for (int u = 0; u < H; ++u) s2 = fmaf(a.mlp.wct[u * 32 + tid], C[u], s2);
-    P[DP_HEADW + tid] = s2;
-  }
-  for (int idx = tid; idx < 32 * kHP; idx += kThreads) P[DP_WC + idx] = a.head_w[idx / kHP] * C[idx % kHP];
-}
-
-
-// =================================================================================================================================
-// Third generation (round 5): the four 32 x 32 Linears of the per-gene chain - q = Wq LN_1q(e), y = Wp ao, d ao = Wp^T d y,
-// d qn = Wq^T d q - on the matrix pipe as well.  In the kernel above every gene's 16 lanes re-read the whole 32 x 36 weight image
-// for each of them (16 KB of LDS reads per gene: a third of the kernel's LDS cycles, and four dependent chains of 24 16-byte reads
-// per step); here one step's 16 genes are the 16 rows of 16 x 16 x 4 MFMAs: a wave owns (output half, k half) of a product - 4 MFMAs -
+// The four 32 x 32 Linears of the chain - q = Wq LN_1q(e), y = Wp ao, d ao = Wp^T d y, d qn = Wq^T d q - have one step's 16 genes as
+// the 16 rows of 16 x 16 x 4 MFMAs: a wave owns (output half, k half) of a product - 4 MFMAs -
 // writes its partial tile to a row set that is free at that point of the step, and the per-gene phase that follows adds the two
 // partials.  Operand reads are LDS-bank aware (ds_read_b32 banks are address mod 32 within 32 lanes, b64 / b128 mod 64):
 //   k along the contiguous axis of BOTH images (q, y, a | b):  lane (li, g4) reads the PAIR of k values 8 p + 2 g4, + 1 as one
 //     ds_read_b64 - row pitch 36 = 4 mod 32 walks 16 rows over 16 distinct 4-bank groups, g4 fills the odd pairs: conflict-free, and
 //     half the LDS instructions of the scalar reads (which were 2-way conflicts: rows li and li + 8 share a bank)
 //   k along the rows of the weight image (d h2, d ao, d qn):  k slot (s, g4) <-> row 16 (s >> 2) + 4 g4 + (s & 3): the B reads of a
-//     32-lane group hit rows 4 apart = 16 banks apart (conflict-free, as before); the A operand's four values of a lane are then
+//     32-lane group hit rows 4 apart = 16 banks apart (conflict-free); the A operand's four values of a lane are then
 //     CONSECUTIVE - one ds_read_b128 instead of four 4-way conflicting scalar reads
 // The gene's attention over the cell's 16 latent tokens and its backward run on the matrix pipe as well, one head per wave: scores
 // (16 genes x 16 keys, k = 8 head dims) and P V / d P / d S K as 16 x 16 x 4 tiles, softmax and its backward across the 16 lanes of a
-// DPP row in the accumulator layout (lane = key) - before, 16 lanes per gene spent ~190 VALU operations per step on them.
+// DPP row in the accumulator layout (lane = key).
 // Per step: S0 embeddings, LN_1q | S1 q partials | S2 attention | S3 y partials, q summed | S4 LN_2 | A | B | S5 LN_2 backward |
 // S6 d ao (two waves, whole k: the next phase's MFMAs read whole rows) | S7 attention backward | S8 d qn (likewise) + C weight
 // gradients | S9 LN_1q backward, dE atomics - separated by workgroup barriers (two workgroups per CU fill each other's waits).
 // =================================================================================================================================
+constexpr int G_WQ = 0, G_WP = G_WQ + 32 * kP, G_W1 = G_WP + 32 * kP, G_W2 = G_W1 + 96 * kP, G_KV = G_W2 + 96 * kP;
+constexpr int G_QN = G_KV + 16 * kP64, G_QQ = G_QN + 16 * kP, G_AO = G_QQ + 16 * kP, G_H2 = G_AO + 16 * kP, G_DY = G_H2 + 16 * kP,
+              G_DAO = G_DY + 16 * kP, G_DQQ = G_DAO + 16 * kP, G_TX = G_DQQ + 16 * kP, G_DA = G_TX + 16 * kP, G_DB = G_DA + 16 * kQ,
+              G_PP = G_DB + 16 * kQ, G_DS = G_PP + 16 * kP64, G_FLOATS = G_DS + 16 * kP64;
+constexpr int M_DL = G_FLOATS, M_C0 = M_DL + 16, M_FLOATS = M_C0 + 96;
+constexpr int M_BYTES = M_FLOATS * 4;
+static_assert(M_BYTES <= 80 * 1024, "two workgroups per CU");
+__device__ __forceinline__ f32x4 mfma16(float x, float y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0); }
 #ifndef SCLDM_VAE_PHASE_CLOCKS
 #define SCLDM_VAE_PHASE_CLOCKS 0   // 1: one workgroup prints its cycles per phase of dec_gene_bwd_mfma2_kernel (tools only)
 #endif

@@ -27,17 +27,3 @@ def test_training_precision_is_validated():
             assert call(L, prec) == -1 and b"precision" not in L.scldm_last_error()
     assert L.scldm_vae_train_set_found_inf(None, None) == -1
 
-
-def test_fp16_training_refuses_the_earlier_kernel_generations():
-    code = ("from scldm_amd import _lib\n"
-            "from test_vae_train_fp16_cpu import _call_forward, _call_backward\n"
-            "L = _lib.lib()\n"
-            "for call in (_call_forward, _call_backward):\n"
-            "    assert call(L, _lib.PREC_FP16) == -3, L.scldm_last_error()\n"
-            "    assert b'default kernel generations' in L.scldm_last_error()\n"
-            "    assert call(L, _lib.PREC_FP32) == -1\n")
-    for env in ({"SCLDM_VAE_GENE_MFMA": "1"}, {"SCLDM_VAE_GENE_MFMA": "0"}, {"SCLDM_VAE_GENE_WIDE": "0"}, {"SCLDM_VAE_CELL_WIDE": "0"}):
-        e = dict(os.environ, **env)
-        e["PYTHONPATH"] = os.pathsep.join([ROOT, os.path.join(ROOT, "tests")])
-        r = subprocess.run([sys.executable, "-c", code], env=e, cwd=ROOT, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (env, r.stderr[-2000:])
