@@ -120,7 +120,7 @@ extern "C" int scldm_dit_create(const scldm_dit_config* cfg, scldm_dit** out) {
   h->half[0] = 0;
   {
     int hp = (cfg->hidden_dim + 63) / 64 * 64;     // FT=2: pad to 64, last chunk may be a half chunk
-    if (getenv("SCLDM_PAD128")) hp = (cfg->hidden_dim + 127) / 128 * 128;   // A/B switch: whole chunks only (needed for SCLDM_PF=8 builds)
+    if (getenv("SCLDM_PAD128")) hp = (cfg->hidden_dim + 127) / 128 * 128;   // A/B switch: whole chunks only, no trailing half chunk
     h->n_chunks[1] = hp / kHC;
     h->half[1] = (hp % kHC) / 64;
   }
@@ -633,7 +633,7 @@ static int trunk(scldm_dit* h, const float* x, int n_direct, int rep, int n_fwd,
   // shape that carried it (same k order, same per-token LayerNorm / softmax arithmetic: bit-identical, tested).
   // MEASURED SLOWER (profiles/r4o_ab_tail_split.txt: 1 024 cells x 3 forwards 0.415 -> 0.366 of peak, 512 cells 0.366 -> 0.357, 1 000
   // cells 0.412 -> 0.363, 300 cells 0.332 -> 0.293): a 32-token tile streams twice the weight bytes per token, and that stream is what
-  // the kernel waits for (dit_forward.hpp, SCLDM_PROXY); lone workgroups of the partial round already run ~1.5x faster.  Off by default.
+  // the kernel waits for (profiles/r4j_timing_proxies_random_vs_zero.txt); lone workgroups of the partial round already run ~1.5x faster.  Off by default.
   int tail_full = 0;
   if (h->tail_split && G == 1 && ntt == 2 && ft == 2 && (prec == SCLDM_PREC_BF16 || prec == SCLDM_PREC_FP16)) {
     const int slots = 2 * h->n_cu, r = tiles_all % slots;

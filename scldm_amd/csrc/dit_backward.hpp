@@ -16,12 +16,13 @@
 // images), so every matrix product below is a gemm_pass over a different packed stream (dit_aux.hpp: pack_bwd_val).
 //
 // Included once per 16-bit operand policy (round 4): the including translation unit defines SCLDM_BWD_NS (namespace of this
-// instantiation) and SCLDM_BWD_OP (OpBF16, or OpFP16 = the reference's TF32 mantissa; its gradients are loss-scaled by the caller,
-// train_api.hip) before each inclusion.  Nothing below depends on the element type beyond OP.
+// instantiation), SCLDM_BWD_OP (OpBF16, or OpFP16 = the reference's TF32 mantissa; its gradients are loss-scaled by the caller,
+// train_api.hip) and SCLDM_BWD_NTT (32-token row tiles per workgroup, below) before each inclusion.  Nothing below depends on the
+// element type beyond OP.
 #include "bwd_layout.hpp"
 #include "dit_forward.hpp"
-#if !defined(SCLDM_BWD_NS) || !defined(SCLDM_BWD_OP)
-#error "define SCLDM_BWD_NS and SCLDM_BWD_OP before including dit_backward.hpp"
+#if !defined(SCLDM_BWD_NS) || !defined(SCLDM_BWD_OP) || !defined(SCLDM_BWD_NTT)
+#error "define SCLDM_BWD_NS, SCLDM_BWD_OP and SCLDM_BWD_NTT before including dit_backward.hpp"
 #endif
 
 namespace scldm {
@@ -34,59 +35,16 @@ using Quad = OP::Quad;
 // SCLDM_BWD_NTT: 32-token row tiles per workgroup.  2 = the 64-token tile of the forward kernel's record; 1 = half of one (round 5:
 // while 32-token tiles still get a CU each - at most 512 cells - the layer's walk is shorter with half the MFMAs and LDS fragment
 // reads per k-step on the same weight stream; the record and the gradient keep the 64-token geometry, a workgroup reads its half).
-#ifndef SCLDM_BWD_NTT
-#define SCLDM_BWD_NTT 2
-#endif
 constexpr int NTT = SCLDM_BWD_NTT, NW = 8, NT = 64 * NW, TM = 32 * NTT, NS = 2 * NTT;
 static_assert(NTT == 1 || NTT == 2, "the record is laid out in 64-token tiles");
-#ifndef SCLDM_BWD_PF
-#define SCLDM_BWD_PF 8
-#endif
-constexpr int PF = SCLDM_BWD_PF;
-// Cache policy of the streaming traffic (A/B switches, round 5): the operand-pair stores (written once here, read once by the
-// weight-gradient GEMM) and the record loads (read once per phase) pass through the XCD's 4 MB L2 next to the 2.8 MB backward weight
-// stream that every workgroup of the XCD re-reads.  0 = default policy, 1 = nt, 2 = sc1 (stores: write through, drop the line),
-// 3 = timing proxy without the stores (98 -> 76 us per launch at 1 024 cells: what the twelve store bursts of a layer cost - vmcnt is
-// in-order, so the weight ring's next wait after a burst is also a wait for the burst's write acknowledgements).
-#ifndef SCLDM_BWD_PAIR_ST
-#define SCLDM_BWD_PAIR_ST 0
-#endif
-#ifndef SCLDM_BWD_REC_NT
-#define SCLDM_BWD_REC_NT 0
-#endif
-// debugging aid: 1 = wait for every vector-memory operation in flight after each group of operand-pair stores
-// which phases request their global reads ahead of use (bit 0: kernel start, bit 1: LayerNorm-2 backward, bit 2: before the K = 768 pass)
-#ifndef SCLDM_BWD_HOIST
-#define SCLDM_BWD_HOIST 10
-#endif
-// 1: the LayerNorm reductions alternate between two LDS buffers and need ONE barrier each; 0: one buffer, two barriers
-#ifndef SCLDM_BWD_RED2
-#define SCLDM_BWD_RED2 1
-#endif
-// 1: the weight ring is parked (not refilled) across the attention core, whose operand fragments are the kernel's register peak
-#ifndef SCLDM_BWD_PARK
-#define SCLDM_BWD_PARK 1
-#endif
-// 1: d x_mid stays in 32 registers from the LayerNorm-2 backward to the LayerNorm-1 backward (one 64 KB store and one load per tile less)
-#ifndef SCLDM_BWD_KEEP_DX
-#define SCLDM_BWD_KEEP_DX 1
-#endif
-// 1: x_in stays in registers from the LayerNorm-1 forward recompute to the LayerNorm-1 backward as well
-#ifndef SCLDM_BWD_KEEP_XIN
-#define SCLDM_BWD_KEEP_XIN 1
-#endif
-// 1: d x_out stays in registers across the SwiGLU chunks too (needs KEEP_DX: the gradient is then read once and written once per layer)
-#ifndef SCLDM_BWD_KEEP_DXOUT
-#define SCLDM_BWD_KEEP_DXOUT 1
-#endif
-// 1: x_in stays in registers across the SwiGLU chunks as well (x_mid is a temporary of phases 1-2 and of the LayerNorm-2 backward):
-// the record's residual is then read once per layer
-#ifndef SCLDM_BWD_KEEP_XIN_MLP
-#define SCLDM_BWD_KEEP_XIN_MLP 1
-#endif
-#ifndef SCLDM_BWD_ST_WAIT
-#define SCLDM_BWD_ST_WAIT 0
-#endif   // k-steps of weight-ring run-ahead: one wave gets two MFMAs (64 cycles) out of a fragment, an L2 round trip is ~10 of those
+constexpr int PF = 8;   // k-steps of weight-ring run-ahead: one wave gets two MFMAs (64 cycles) out of a fragment, an L2 round trip is ~10 of those
+// Register residency (round 5): the gradient is read once and written once per layer, the record's residual read once.
+// d x_out stays in registers across the SwiGLU chunks, d x_mid from the LayerNorm-2 backward to the LayerNorm-1 backward, x_in from
+// its load in phase 1 through the SwiGLU chunks to the LayerNorm-1 backward (x_mid is a temporary of phases 1-2 and of the
+// LayerNorm-2 backward).  The weight ring is parked (not refilled) across every phase without a GEMM pass - the attention core's operand
+// fragments are the kernel's register peak.  The operand-pair stores use the default cache policy: they cost 98 -> 76 us per launch
+// at 1 024 cells (a timing proxy without them; vmcnt is in-order, so the ring's next wait after a store burst also waits for the
+// burst's write acknowledgements); nt and sc1 stores measured slower (2.72-3.05 against 2.51 ms per training step).
 constexpr int XA_LD = kD + 8, DADB_LD = 2 * kBwdChunk + 8, DQKV_LD = 3 * kD + 8;   // bf16 elements per image row (+16 B pad)
 constexpr int R0_OFF = 0;                                   // h2 image, later h1 image
 constexpr int R1_OFF = R0_OFF + TM * XA_LD * 2;             // dy2 image, later dy1 image
@@ -167,13 +125,7 @@ __device__ __forceinline__ gchar* uniform_ptr(const void* p) {
 }
 __device__ __forceinline__ void pair_store(const PairDst& d, unsigned imm, const u32x4 v) {
   g_u32x4* gp = (g_u32x4*)(d.base + (d.voff + imm));
-#if SCLDM_BWD_PAIR_ST == 3   // timing proxy: no operand-pair stores at all (weight gradients are garbage)
-  asm volatile("" :: "v"(v), "v"(gp));
-#elif SCLDM_BWD_PAIR_ST == 1
-  __builtin_nontemporal_store(v, gp);
-#else
   *gp = v;
-#endif
 }
 // quads q (q0) and q+1 (q1) of a 32-feature tile -> 16 bytes per lane (features f8 + 8*hh .. +7 of the lane's token), stored
 // to the LDS image row and, when g.on, to the same position of the plain global operand array
@@ -200,9 +152,6 @@ __device__ __forceinline__ void put_tile(const float (&t)[16], E* lrow, const Pa
     if (lrow) *reinterpret_cast<u32x4*>(lrow + col0 + q * 8 + 8 * hh) = v;
     if (g.on) pair_store(g, (unsigned)(q * 8) * 2u, v);
   }
-#if SCLDM_BWD_ST_WAIT
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-#endif
 }
 
 // LDS byte offsets above 64 KB do not fit a ds instruction's 16-bit immediate: hipcc then builds ONE address register per
@@ -270,7 +219,7 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
   // reduction scratch [buffer][2][wave][token]: this lane's write slot (own wave) / first read slot (wave 0)
   auto red_w = [&]() { return reinterpret_cast<float*>(smem + opaque(RED_OFF + (wave * TM + (lane_now() & 31)) * 4)); };
   auto red_r = [&]() { return reinterpret_cast<const float*>(smem + opaque(RED_OFF + (lane_now() & 31) * 4)); };
-  constexpr int RED0 = 0, RED1 = SCLDM_BWD_RED2 ? RED_BYTES / 4 : 0;   // float offset of the two buffers
+  constexpr int RED0 = 0, RED1 = RED_BYTES / 4;   // float offset of the two buffers: the reductions alternate, ONE barrier each
   auto mod_base = [&]() {
     const int l = lane_now();
     return reinterpret_cast<const ModE*>(smem + opaque(MOD_OFF + (((l & 31) >> 4) * kModBlock + fb + (l >> 5) * 4) * (int)sizeof(ModE)));
@@ -282,9 +231,7 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     if (a.dbg && lane == 0) a.dbg[((size_t)blockIdx.x * NW + wave) * 16 + (i)] = __builtin_readcyclecounter();             \
   } while (0)
   BWD_STAMP(0);
-  WStream<OP, PF, 1> ws;   // the weight ring is requested at the end of phase 2 and parked across every phase without a GEMM pass (SCLDM_BWD_PARK)
-  constexpr bool kPark = SCLDM_BWD_PARK && PF <= 8;
-  if (!kPark) ws.init(reinterpret_cast<const Frag*>(a.w_stream) + (size_t)wave * kBwdUnitsLayer * 64, lane);
+  WStream<OP, PF, 1> ws;   // the weight ring is requested at the end of phase 2 and parked across every phase without a GEMM pass
 
   // record / gradient tiles in the 4-wave forward kernel's layout [tile][fwd wave = wave >> 1][quad (tt*2 + ft)*4 + q][lane][4],
   // ft = wave & 1: a quad is 1 KB (fp32) / 512 B (16-bit) contiguous per wave; the descriptors start at this wave's first quad
@@ -386,9 +333,6 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
       mean[tt] = m * (1.0f / kD);
       rstd[tt] = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean[tt], mean[tt], e2 * (1.0f / kD)), 0.f) + a.eps);
     }
-#if !SCLDM_BWD_RED2
-    lds_barrier();   // RED may be rewritten by the next reduction
-#endif
   };
   // y = LN(v) * S + shift (S = 1 + scale, staged) -> LDS image + operand array
   auto ln_modulate = [&](const float (&v)[NTT][16], const float (&mean)[NTT], const float (&rstd)[NTT], int sc_v, int sh_v, E* img, const E* gout) {
@@ -465,9 +409,6 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
         }
       }
     }
-#if !SCLDM_BWD_RED2
-    lds_barrier();
-#endif
   };
   auto bias_tile = [&](int p) {   // bias of c_attn rows p * 256 + fb .. + 31 as an initial accumulator tile
     const float* const BIAS_R = reinterpret_cast<const float*>(smem + opaque(BIAS_OFF + (fb + (lane_now() >> 5) * 4) * 4));
@@ -500,8 +441,8 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     F[1] = hi_half.f;
   };
 
-  // ---- phase 1: every global read of the phase is requested up front (one round trip, not one per use): the adaLN vectors and
-  // the c_attn bias (staged to LDS), d x_out, y2, x_in, y1 ----
+  // ---- phase 1: the adaLN vectors and the c_attn bias (staged to LDS), d x_out and y2 are requested up front (one round trip, not
+  // one per use); x_in and y1 follow once d y2 is out ----
   constexpr int kModQuads = NS * kModBlock / 4;               // float4s of the tile's adaLN vectors
   constexpr int kModLd = (kModQuads + NT - 1) / NT;           // 3 per thread (64-token tile), 1.5 (32-token tile: the second one on half the threads)
   f32x4 mstage[kModLd], bstage = {0.f, 0.f, 0.f, 0.f};
@@ -511,15 +452,9 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     mstage[j] = *reinterpret_cast<const f32x4*>(a.mod + (size_t)min(smp0 + sl, a.n - 1) * a.mod_stride + a.mod_off + w4 * 4);
   }
   if (tid < 3 * kD / 4) bstage = *reinterpret_cast<const f32x4*>(a.b_qkv + tid * 4);
-  // The residual x and its gradient are NOT kept in registers across the GEMM phases (the up-projection tiles, the operand
-  // fragments of the attention core and the weight ring need them): each phase re-reads what it needs from the record / from
-  // a.dx (L2-resident, 64 KB per tile).
   float mean2[NTT], rstd2[NTT];
-  float xr[NTT][16];    // x_mid in phases 1-2, x_in from the LayerNorm-2 backward on
-#if SCLDM_BWD_KEEP_DXOUT
-  static_assert(SCLDM_BWD_KEEP_DX, "KEEP_DXOUT extends KEEP_DX");
-  float dxr[NTT][16];
-#endif
+  float xr[NTT][16];    // x_in, from its load in phase 1 to the LayerNorm-1 backward
+  float dxr[NTT][16];   // d x_out, then d x_mid, then d x_in: read once here, written once at the end
   {
   auto stage_mod = [&]() {
 #pragma unroll
@@ -532,22 +467,10 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     }
     if (tid < 3 * kD / 4) *reinterpret_cast<f32x4*>(BIAS + tid * 4) = bstage;
   };
-#if !SCLDM_BWD_KEEP_DXOUT
-  float dxr[NTT][16];
-#endif
   u32x2 y2raw[NTT][4], y1raw[NTT][4];
-#if !(SCLDM_BWD_HOIST & 8)
-  stage_mod();
-#endif
   load_f32(r_dx, dxr);
   load_16(r_y2, y2raw);
-#if SCLDM_BWD_HOIST & 1
-  load_f32(r_xin, xr);
-  load_16(r_y1, y1raw);
-#endif
-#if SCLDM_BWD_HOIST & 8
   stage_mod();
-#endif
   lds_barrier();
 
   // ================= MLP branch: x_out = x_mid + a5 * c_proj(silu(w1 h2) * (w2 h2)),  h2 = LN(x_mid) (1 + a3) + a4 =================
@@ -571,15 +494,9 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     }
     dmod_store(t, 5);
     // x_mid = x_in + a2 * y1
-#if !(SCLDM_BWD_HOIST & 1)
     load_f32(r_xin, xr);
     load_16(r_y1, y1raw);
-#endif
-#if SCLDM_BWD_KEEP_XIN_MLP
     float xm[NTT][16];
-#else
-    float (&xm)[NTT][16] = xr;
-#endif
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
@@ -593,7 +510,7 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
   ln_modulate(xm, mean2, rstd2, 3, 4, R0, a.e_h2);
   }
   }
-  if (kPark) ws.init(reinterpret_cast<const Frag*>(a.w_stream) + (size_t)wave * kBwdUnitsLayer * 64, lane);
+  ws.init(reinterpret_cast<const Frag*>(a.w_stream) + (size_t)wave * kBwdUnitsLayer * 64, lane);
   lds_barrier();   // h2 and dy2 images complete
   BWD_STAMP(2);
 
@@ -628,31 +545,18 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     lds_barrier();
     if (c == 0) BWD_STAMP(5);
     if (c == 0) gemm_pass<OP, NTT, 1, 32, false, true, PF>(dh, ws, R2, DADB_LD, lane_now());    // d h2^T (+)= [w1^T | w2^T] [da | db]
-    else if (kPark && c == kBwdChunks - 1) gemm_pass<OP, NTT, 1, 32, false, false, PF, kPark>(dh, ws, R2, DADB_LD, lane_now());
+    else if (c == kBwdChunks - 1) gemm_pass<OP, NTT, 1, 32, false, false, PF, true>(dh, ws, R2, DADB_LD, lane_now());   // parks the ring
     else gemm_pass<OP, NTT, 1, 32, false, false, PF>(dh, ws, R2, DADB_LD, lane_now());
     if (c == 0) BWD_STAMP(6);
   }
   BWD_STAMP(7);
   // d x_mid = d x_out + LN2-backward(d h2);  d a3, d a4
   float mean1[NTT], rstd1[NTT];
-#if SCLDM_BWD_KEEP_DX && !SCLDM_BWD_KEEP_DXOUT
-  float dxr[NTT][16];
-#endif
   {
-  // every global read of the two phases is requested here: d x_out (needed at the end of the LayerNorm-2 backward), y1 and x_in.
-  // x_mid = x_in + a2 y1 is REBUILT here instead of living in 32 registers across the SwiGLU chunks (round 5: that loop is the
-  // kernel's register peak, and x_in / y1 are read again for this phase anyway)
-#if !SCLDM_BWD_KEEP_DX
-  float dxr[NTT][16];
-#endif
+  // x_mid = x_in + a2 y1 is REBUILT here (y1 read again) instead of living in 32 more registers across the SwiGLU chunks (round 5:
+  // that loop is the kernel's register peak)
   u32x2 y1raw[NTT][4];
-#if !SCLDM_BWD_KEEP_DXOUT
-  load_f32(r_dx, dxr);
-#endif
   load_16(r_y1, y1raw);
-#if !SCLDM_BWD_KEEP_XIN_MLP
-  load_f32(r_xin, xr);
-#endif
   {
     const ModE* const mb = mod_base();
     float xm[NTT][16];
@@ -688,14 +592,10 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     }
     dmod_store(t, 2);
   }
-#if !SCLDM_BWD_KEEP_DX
-  // d x_mid waits in a.dx for the LayerNorm-1 backward at the end
-  store_dx(dxr);
-#endif
   ln_stats(xr, mean1, rstd1, RED0);
   ln_modulate(xr, mean1, rstd1, 0, 1, R0, a.e_h1);   // h1 (R0's last readers were chunk 2's a / b passes)
   }
-  if (kPark) ws.unpark();
+  ws.unpark();
   lds_barrier();
 
   BWD_STAMP(9);
@@ -719,7 +619,7 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     gemm_pass<OP, NTT, 1, 16, false, true, PF>(acc, ws, R0, XA_LD, lane_now(), &b);
     keep(KF);
     b = bias_tile(2);
-    gemm_pass<OP, NTT, 1, 16, false, true, PF, kPark>(acc, ws, R0, XA_LD, lane_now(), &b);
+    gemm_pass<OP, NTT, 1, 16, false, true, PF, true>(acc, ws, R0, XA_LD, lane_now(), &b);   // parks the ring across the attention core
     keep(VF);
   }
   const int l_tr = lane_now();
@@ -842,30 +742,10 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
     }
   }
   BWD_STAMP(11);
-  if (kPark) ws.unpark();
+  ws.unpark();
   lds_barrier();   // dqkv image complete
-  // x_in (and d x_mid) are requested before the K = 768 pass and arrive under it
-#if !SCLDM_BWD_KEEP_DX
-  float dxr[NTT][16];
-#endif
-#if (SCLDM_BWD_HOIST & 4) && !SCLDM_BWD_KEEP_XIN
-  load_f32(r_xin, xr);
-#endif
-#if SCLDM_BWD_HOIST & 4
-#if !SCLDM_BWD_KEEP_DX
-  load_f32(r_dx, dxr);
-#endif
-#endif
-  gemm_pass<OP, NTT, 1, 48, false, true, PF, kPark>(dh, ws, DQKV, DQKV_LD, lane_now());   // d h1^T = c_attn^T d qkv (last pass: the ring ends here)
+  gemm_pass<OP, NTT, 1, 48, false, true, PF, true>(dh, ws, DQKV, DQKV_LD, lane_now());   // d h1^T = c_attn^T d qkv (last pass: the ring ends here)
   BWD_STAMP(12);
-#if !(SCLDM_BWD_HOIST & 4) && !SCLDM_BWD_KEEP_XIN
-  load_f32(r_xin, xr);
-#endif
-#if !(SCLDM_BWD_HOIST & 4)
-#if !SCLDM_BWD_KEEP_DX
-  load_f32(r_dx, dxr);
-#endif
-#endif
   // d x_in = d x_mid + LN1-backward(d h1);  d a0, d a1
   ln_backward(dh[0], xr, mean1, rstd1, 0, 1, dxr, RED1);
 

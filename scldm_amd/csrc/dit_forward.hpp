@@ -42,28 +42,12 @@
 
 #include "common.hpp"
 
-// Issue priority of a wave while it runs a weight-streaming GEMM pass (s_setprio; 0 elsewhere).  Two workgroups share
-// each SIMD: letting the wave that is feeding the matrix pipe win instruction issue over its neighbour's LayerNorm /
-// softmax / SiLU VALU work measured -2 % kernel time (389 -> 381 us, same session); priority held across the whole layer
-// except LayerNorm measured +1 % instead.  -DSCLDM_SETPRIO=0 disables it.
-#ifndef SCLDM_SETPRIO
-#define SCLDM_SETPRIO 1
-#endif
-// k-steps of run-ahead of the activation-fragment LDS reads in the one-tile up-projection pass (1 or 2)
-#ifndef SCLDM_BPF
-#define SCLDM_BPF 1
-#endif
-// 1: Linear biases enter as the INITIAL accumulator of their GEMM pass (the MFMA's C operand) instead of a VALU add per output
-// element afterwards; 2 fewer VALU ops per LayerNorm element (scale and offset folded per token).  A/B switch.
-#ifndef SCLDM_LEAN_VALU
-#define SCLDM_LEAN_VALU 1
-#endif
-// 1: activation tiles are stored to LDS as 16-byte pieces after a half-wave exchange (common.hpp: halfwave_pair) instead of
-// 8-byte pieces (2-way bank conflicted on 16-byte-aligned rows).  A/B switch.
-#ifndef SCLDM_PAIR_STORE
-#define SCLDM_PAIR_STORE 1
-#endif
-
+// Two conventions of this file, each the winner of a measured A/B:
+//   * Linear biases enter as the INITIAL accumulator of their GEMM pass (the MFMA's C operand) instead of a VALU add per output
+//     element afterwards, and LayerNorm folds scale and offset per token: 2 fewer VALU ops per LayerNorm element;
+//   * activation tiles are stored to LDS as 16-byte pieces after a half-wave exchange (common.hpp: halfwave_pair); 8-byte pieces
+//     are 2-way bank conflicted on 16-byte-aligned rows.
+//
 // Floating-point contraction is OFF in this file and every fused multiply-add is written out (fmaf): the layer body is
 // instantiated once per layer slot of a launch, and with the default contract(fast) hipcc is free to fuse a * b + c in one
 // slot's schedule and not in another's - results then depend on which slot (i.e. on SCLDM_LPL) a layer happens to run in.
@@ -75,37 +59,16 @@ constexpr int kD = 256;        // n_embed
 constexpr int kHC = 128;       // hidden chunk per workgroup (4 waves x 32)
 constexpr int kModBlock = 6 * kD;
 constexpr int kDbgStamps = 32;
-// layer slots instantiated in the fused kernel (code size grows with it: ~30 KB of ISA per slot).  Round 4: EIGHT for the inference
+// Issue priority of a wave while it runs a weight-streaming GEMM pass (s_setprio; 0 elsewhere).  Two workgroups share
+// each SIMD: letting the wave that is feeding the matrix pipe win instruction issue over its neighbour's LayerNorm /
+// softmax / SiLU VALU work measured -2 % kernel time (389 -> 381 us, same session); priority held across the whole layer
+// except LayerNorm measured +1 % instead.
+constexpr int kGemmPassPrio = 1;
+// layer slots instantiated in the fused kernel (code size grows with it: ~30 KB of ISA per slot): EIGHT for the inference
 // kernels - the whole reference network in one launch, no residual hand-off through HBM at all (same-box interleaved A/B,
-// profiles/r4a_ab_lpl8_l2warm.txt: +0.8 % at 4 096 cells, +2.0 % at 1 024, +1.9 % at 512 over four); the recording (training)
-// instantiation keeps four (-DSCLDM_MAX_LPL=4 restores four everywhere).
-#ifndef SCLDM_MAX_LPL
-#define SCLDM_MAX_LPL 8
-#endif
-constexpr int kMaxLayersPerLaunch = SCLDM_MAX_LPL;
-#ifndef SCLDM_REC_LPL
-#define SCLDM_REC_LPL 4
-#endif
-constexpr int kMaxLayersPerLaunchRec = SCLDM_REC_LPL;   // layer slots of the RECORDING (training) instantiation: 4, or 8 with -DSCLDM_REC_LPL=8
-// 1: every workgroup touches its share of the NEXT layer's weight stream (one 4-byte load per 128-byte line) at the start of a
-// layer, so that the stream's first-touch misses (each XCD's 4 MB L2 holds ~2 layers) are taken a layer ahead of the ring.
-#ifndef SCLDM_L2WARM
-#define SCLDM_L2WARM 0
-#endif
-// Timing proxies (deliberately WRONG results; libx_* experiment builds only): bit 0 no weight-ring refills, bit 1 no activation-fragment
-// LDS reads, bit 2 no SwiGLU transcendental work, bit 3 (round 5) the cost model of "two wave groups share one weight ring through LDS":
-// only every SECOND k-step's weight fragments are fetched from L2 (the other group's half) and every k-step reads FT extra 16-byte
-// fragments per lane from LDS (where the shared ring would live), bit 4 the LDS half of that alone (extra reads, full L2 stream).  What each costs in time AND clock under the power budget.
-#ifndef SCLDM_PROXY
-#define SCLDM_PROXY 0
-#endif
-// 1: the SwiGLU up-projection of a full chunk is ONE two-tile pass (each activation fragment read from LDS feeds two MFMAs instead of
-// one: -31 % LDS fragment reads per layer; the packer then orders a chunk's W12 units k-step by k-step).  Round 4 proxy: the fragment
-// reads cost 2 % in cycles but 7 % under the power budget (profiles/r4j_timing_proxies_random_vs_zero.txt).  With round 4's kernel the
-// two-tile pass spills 178 VGPRs (64 accumulators more are live next to the residual and the x-row registers), so it stays off.
-#ifndef SCLDM_W12_PAIR
-#define SCLDM_W12_PAIR 0
-#endif
+// profiles/r4a_ab_lpl8_l2warm.txt: +0.8 % at 4 096 cells, +2.0 % at 1 024, +1.9 % at 512 over four); four for the recording
+// (training) instantiation.
+constexpr int kMaxLayersPerLaunch = 8, kMaxLayersPerLaunchRec = 4;
 
 // Phase stamps (s_memtime) for the debug build (first layer only); compiles to nothing otherwise.
 #ifdef SCLDM_PHASE_TIMING
@@ -206,16 +169,12 @@ __host__ __device__ constexpr int units_per_layer(int n_chunks, int half = 0) {
 
 template <typename OP, int NTT, int FT>
 struct Prefetch {  // k-steps of run-ahead of the weight ring
-#ifdef SCLDM_PF
-  static constexpr int PF = OP::kIsBF16 ? SCLDM_PF : OP::kRing;
-#else
   // 32-token tiles (launches below one 64-token tile per CU: a single workgroup's walk through the layers IS the launch time) run the
   // 16-bit policies' ring 8 k-steps ahead instead of 4: with one workgroup per CU nothing else hides the L2 latency of the weight
   // stream, and the instantiation has the registers (170 -> 216 VGPRs, no spills).  Same box, interleaved, 128 cells x 50 evaluations:
   // 165.0 -> 150.6 us per launch, 9.24 -> 8.51 ms per trajectory (round 6).  64-token tiles keep 4 (247 VGPRs: 8 would spill; +-0 at
   // full occupancy, HISTORY).  Results do not depend on the depth.
   static constexpr int PF = (NTT == 1 && OP::kIsBF16) ? 8 : OP::kRing;
-#endif
 };
 
 template <typename OP, int PF, int FT>
@@ -290,13 +249,8 @@ __device__ __forceinline__ void gemm_pass(f32x16 (&acc)[FT][NTT], WStream<OP, PF
   auto step = [&](int ks, int s, bool first, bool refill = true) {
     Frag bnext[NTT];
     // B fragments of k-step ks+1 (after the last k-step this reads the row pad / next row: valid LDS, never used)
-#if SCLDM_PROXY & 2    // timing proxy 2 (WRONG RESULTS): the activation fragments are read once per pass - what the LDS fragment reads cost
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt) bnext[tt] = bcur[tt];
-#else
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) bnext[tt] = *reinterpret_cast<const Frag*>(bbase + tt * 32 * ldb + (ks + 1) * 16);
-#endif
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
 #pragma unroll
@@ -305,20 +259,10 @@ __device__ __forceinline__ void gemm_pass(f32x16 (&acc)[FT][NTT], WStream<OP, PF
         else acc[ft][tt] = OP::mma(ws.ring[s][ft], bcur[tt], first ? (init ? init[ft] : zero) : acc[ft][tt]);
       }
     }
-#if SCLDM_PROXY & 24   // timing proxies 8 / 16 (WRONG RESULTS): FT more fragment reads from LDS per k-step (a weight ring shared through LDS)
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-      typedef __attribute__((ext_vector_type(4))) unsigned px_u32x4;
-      const px_u32x4 extra = *reinterpret_cast<const px_u32x4*>(bbase + ((ft + 1) & (NTT - 1)) * 32 * ldb + ((ks + 2 + ft) & 7) * 16);
-      asm volatile("" ::"v"(extra));
-    }
-#endif
-#if !(SCLDM_PROXY & 1)   // timing proxy 1 (WRONG RESULTS): the weight ring is never refilled - what the L2 -> VGPR weight stream costs
-    if (refill && (!(SCLDM_PROXY & 8) || (ks & 1))) {
+    if (refill) {
 #pragma unroll
       for (int ft = 0; ft < FT; ++ft) ws.ring[s][ft] = ws.fetch(ft);  // refill the slot just consumed: PF k-steps ahead
     }
-#endif
     ws.advance(FT);
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) bcur[tt] = bnext[tt];
@@ -329,9 +273,7 @@ __device__ __forceinline__ void gemm_pass(f32x16 (&acc)[FT][NTT], WStream<OP, PF
     }
   };
   // peeled first ring revolution (so that ZERO needs no accumulator clearing), then the rolled loop
-#if SCLDM_SETPRIO
-  __builtin_amdgcn_s_setprio(SCLDM_SETPRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kGemmPassPrio);
   static_assert(!PARK || (KSTEPS % PF == 0 && KSTEPS >= 2 * PF), "a parking pass has a whole last revolution of its own");
 #pragma unroll
   for (int s = 0; s < (PF < KSTEPS ? PF : KSTEPS); ++s) step(s, s, ZERO && s == 0);
@@ -344,9 +286,7 @@ __device__ __forceinline__ void gemm_pass(f32x16 (&acc)[FT][NTT], WStream<OP, PF
 #pragma unroll
     for (int s = 0; s < PF; ++s) step(KSTEPS - PF + s, s, false, false);
   }
-#if SCLDM_SETPRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Up-projection pass for ONE 32-row weight tile over K = 256 (FT=2 only): the ring still moves units of two
@@ -364,42 +304,20 @@ __device__ __forceinline__ void gemm_pass_tile(f32x16 (&acc)[NTT], WStream<OP, P
   Frag bcur[NTT];
 #pragma unroll
   for (int tt = 0; tt < NTT; ++tt) bcur[tt] = *reinterpret_cast<const Frag*>(bbase + tt * 32 * ldb);
-#if SCLDM_BPF >= 2
-  // activation fragments two k-steps ahead: one k-step of this pass is only NTT MFMAs (64 cycles at NTT = 2), less than an
-  // LDS round trip with eight waves reading
-  Frag bmid[NTT];
-#pragma unroll
-  for (int tt = 0; tt < NTT; ++tt) bmid[tt] = *reinterpret_cast<const Frag*>(bbase + tt * 32 * ldb + 16);
-#endif
   auto unit = [&](int u, int s, bool first) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int ks = 2 * u + half;
       Frag bnext[NTT];
-#if SCLDM_PROXY & 2
-#pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) bnext[tt] = bcur[tt];
-#elif SCLDM_BPF >= 2
-#pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) bnext[tt] = *reinterpret_cast<const Frag*>(bbase + tt * 32 * ldb + (ks + 2) * 16);
-#else
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) bnext[tt] = *reinterpret_cast<const Frag*>(bbase + tt * 32 * ldb + (ks + 1) * 16);
-#endif
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) acc[tt] = OP::mma(ws.ring[s][half], bcur[tt], (first && half == 0) ? zero : acc[tt]);
-#if SCLDM_BPF >= 2
-#pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) { bcur[tt] = bmid[tt]; bmid[tt] = bnext[tt]; }
-#else
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) bcur[tt] = bnext[tt];
-#endif
       if (half == 1) {
-#if !(SCLDM_PROXY & 1)
         ws.ring[s][0] = ws.fetch(0);
         ws.ring[s][1] = ws.fetch(1);
-#endif
         ws.advance(2);
       }
       if (OP::kPin) {
@@ -409,9 +327,7 @@ __device__ __forceinline__ void gemm_pass_tile(f32x16 (&acc)[NTT], WStream<OP, P
       }
     }
   };
-#if SCLDM_SETPRIO
-  __builtin_amdgcn_s_setprio(SCLDM_SETPRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kGemmPassPrio);
 #pragma unroll
   for (int s = 0; s < PF; ++s) unit(s, s, s == 0);
 #pragma unroll 1
@@ -419,9 +335,7 @@ __device__ __forceinline__ void gemm_pass_tile(f32x16 (&acc)[NTT], WStream<OP, P
 #pragma unroll
     for (int s = 0; s < PF; ++s) unit(u0 + s, s, false);
   }
-#if SCLDM_SETPRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // The same up-projection pass on 16x16 tiles (v_mfma_f32_16x16x32, the 16-bit policies' mma16): a unit is ONE 32-k step of the
@@ -451,10 +365,8 @@ __device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b
       // after the last unit: unit 0 again, never used (the read stays inside the row)
       bcur[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb + ((u + 1) & (UNITS - 1)) * 32);
     }
-#if !(SCLDM_PROXY & 1)
     ws.ring[s][0] = ws.fetch(0);
     ws.ring[s][1] = ws.fetch(1);
-#endif
     ws.advance(2);
     if (OP::kPin) {
 #pragma unroll
@@ -465,9 +377,7 @@ __device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b
       __builtin_amdgcn_sched_group_barrier(0x020, 2 * OP::kFragLoads, 0);   // VMEM read
     }
   };
-#if SCLDM_SETPRIO
-  __builtin_amdgcn_s_setprio(SCLDM_SETPRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kGemmPassPrio);
 #pragma unroll
   for (int s = 0; s < PF; ++s) unit(s, s, s == 0);
 #pragma unroll 1
@@ -475,9 +385,7 @@ __device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b
 #pragma unroll
     for (int s = 0; s < PF; ++s) unit(u0 + s, s, false);
   }
-#if SCLDM_SETPRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 #ifdef SCLDM_PHASE_TIMING
@@ -595,7 +503,7 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
     return msm + (tt * 2 + sp) * kModBlock + vec * kD + (wave * FT + ft) * 32 + q * 8 + hh * 4;
   };
   f32x4 sc_n = OP::load_mod4(quad_ptr(0, sc_v)), sh_n = OP::load_mod4(quad_ptr(0, sh_v));
-  typename OP::Quad held;   // the even quad of a pair, kept until its odd neighbour is ready (SCLDM_PAIR_STORE)
+  typename OP::Quad held;   // the even quad of a pair, kept until its odd neighbour is ready
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int tt = b / (FT * 4), ft = (b / 4) % FT, q = b % 4;
@@ -604,9 +512,7 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
       sc_n = OP::load_mod4(quad_ptr(b + 1, sc_v));
       sh_n = OP::load_mod4(quad_ptr(b + 1, sh_v));
     }
-    const int f = (wave * FT + ft) * 32 + q * 8 + hh * 4;
     float y[4];
-#if SCLDM_LEAN_VALU
     // the LDS copy of a scale vector already holds 1 + scale (added once when the vectors are staged), so an element costs
     //   bf16 path:   n = v * rstd + (-mean * rstd);  y = n * S + sh                      (2 ops)
     //   parity paths: n = (v - mean) * rstd (centred first: no cancellation);  y = n * S + sh   (3 ops)
@@ -617,27 +523,16 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
 #pragma unroll
       for (int i = 0; i < 4; ++i) y[i] = fmaf((v[ft][tt][q * 4 + i] - mean[tt]) * rstd[tt], sc[i], sh[i]);
     }
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) y[i] = (v[ft][tt][q * 4 + i] - mean[tt]) * rstd[tt] * (1.0f + sc[i]) + sh[i];
-#endif
-#if SCLDM_PAIR_STORE
     const typename OP::Quad packed = OP::pack4(y[0], y[1], y[2], y[3]);
     if ((q & 1) == 0) held = packed;
     else OP::store_quad_pair(dst + (tt * 32 + c32) * ldd, (wave * FT + ft) * 32 + (q - 1) * 8, hh, held, packed);
-#else
-    OP::store_quad(dst + (tt * 32 + c32) * ldd, f, OP::pack4(y[0], y[1], y[2], y[3]));
-#endif
   }
 }
 
-#ifndef SCLDM_FWD_ONE_WG
-#define SCLDM_FWD_ONE_WG 0    // experiment builds: 1 = compile every instantiation for ONE wave per SIMD (up to 512 registers: room for -DSCLDM_PF=8 -DSCLDM_W12_PAIR=1)
-#endif
 // M16 (16-bit policies, FT = 2): the SwiGLU up-projection runs on 16x16 tiles (gemm_pass_tile16) from a stream packed for it
 // (pack_layer_val, m16); every other pass, the residual and the record stay on 32x32 tiles.  SCLDM_FWD_MFMA=32 selects M16 = false.
 template <typename OP, int NTT, int FT, bool REC = false, bool M16 = false>
-__global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG && NTT <= 2) || NTT == 1)) ? 2 : 1) void dit_forward_kernel(const FwdArgs a) {
+__global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 1) ? 2 : 1) void dit_forward_kernel(const FwdArgs a) {
   static_assert(!M16 || (FT == 2 && sizeof(typename OP::E) == 2 && sizeof(typename OP::Frag) == 16), "M16: 16-bit policies, FT = 2");
   using L = FwdLayout<OP, NTT, FT>;
   using E = typename OP::E;
@@ -871,18 +766,6 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
                                  : *reinterpret_cast<const f32x4*>(a.b_proj + li * kD + (idx - 3 * kD / 4) * 4);
   }
   float* BIAS = reinterpret_cast<float*>(HB);
-#if SCLDM_L2WARM
-  // L2 warm-up of the next layer's stream (the first layer's for the last one: the next evaluation starts there).  The 64
-  // workgroups an XCD runs at a time (consecutive blockIdx / 8) split the 1.6 MB into 128-byte lines; one dword per line.
-  unsigned warm = 0;
-  {
-    const long lbytes = a.w_layer_elems * (long)sizeof(E);
-    const char* nxt = reinterpret_cast<const char*>(a.w_stream) + (layer + 1 < a.n_layer ? (long)(li + 1) * lbytes : -(long)a.layer * lbytes);
-    const int lines = (int)(lbytes >> 7), per = (lines + 63) >> 6;
-    const int ln = ((blockIdx.x >> 3) & 63) * per + tid;
-    if (tid < per && ln < lines) warm = *reinterpret_cast<const unsigned*>(nxt + ((long)ln << 7));
-  }
-#endif
 
   f32x16 acc[FT][NTT];
   const float* bq = BIAS;
@@ -891,16 +774,11 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
   // ---- LN1 + modulate(a0 = scale, a1 = shift) -> XA (the staged adaLN vectors are published on the way) ----
   SCLDM_STAMP(21);
   ln_modulate_store<OP, NTT, FT, 22>(xr, MOD, 0, 1, a.eps, RED, XA, L::XA_LD, wave, lane, a.dbg, [&] {
-#if SCLDM_L2WARM
-    asm volatile("" :: "v"(warm));   // the warm-up load retires with the staged vectors (issued together): no later wait inherits it
-#endif
 #pragma unroll
     for (int j = 0; j < kModLd; ++j)
       if (tid + NT * j < NS * kModBlock / 4) {
-#if SCLDM_LEAN_VALU
         const int vec = ((tid + NT * j) % (kModBlock / 4)) / (kD / 4);   // which of the six vectors this float4 belongs to
         if (vec == 0 || vec == 3) mstage[j] += 1.0f;                      // a0 / a3 act as SCALES (F7): stored as 1 + scale
-#endif
         OP::store_mod4(MOD + (size_t)(tid + NT * j) * 4, mstage[j]);
       }
 #pragma unroll
@@ -1006,16 +884,10 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
 #pragma unroll
       for (int ft = 0; ft < FT; ++ft) {
         Frag QFh[NTT][2], KFh[NTT][2];
-#if SCLDM_LEAN_VALU
         const f32x16 qk_bias[2] = {bias_tile(bq + 0 * kD + fbase + ft * 32), bias_tile(bq + 1 * kD + fbase + ft * 32)};
         gemm_pass<OP, NTT, FT, 16, false, true, PF>(acc, ws, XA, L::XA_LD, lane, qk_bias);  // acc[0] = Q^T + b_q, acc[1] = K^T + b_k of head ft
         to_frags_nobias(acc[0], QFh);
         to_frags_nobias(acc[1], KFh);
-#else
-        gemm_pass<OP, NTT, FT, 16, false, true, PF>(acc, ws, XA, L::XA_LD, lane);  // acc[0] = Q^T, acc[1] = K^T of head ft
-        to_frags(acc[0], bq + 0 * kD + fbase + ft * 32, QFh);
-        to_frags(acc[1], bq + 1 * kD + fbase + ft * 32, KFh);
-#endif
         if (ft == 0) SCLDM_STAMP(2);
         if (ft == 0) SCLDM_STAMP(3);
         scores(QFh, KFh, Pf[ft]);
@@ -1038,31 +910,18 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
     gemm_pass<OP, NTT, FT, 16, true, true, PF>(acc, ws, XA, L::XA_LD, lane);
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
-#if SCLDM_LEAN_VALU
       // the V bias is added AFTER the P V product, as the initial accumulator: every query's probabilities sum to one over its
       // sample's keys (the cross-sample blocks of P are exact zeros), so P (V + 1 b^T) = P V + b per output row d
       const float* vb_row = bq + 2 * kD + fbase + ft * 32;
-#else
-      const float bv = bq[2 * kD + fbase + ft * 32 + c32];
-      const f32x16 ot0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#endif
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) {
         float t[16];
 #pragma unroll
-#if SCLDM_LEAN_VALU
         for (int r = 0; r < 16; ++r) t[r] = acc[ft][tt][r];
-#else
-        for (int r = 0; r < 16; ++r) t[r] = acc[ft][tt][r] + bv;
-#endif
         const Frag v0 = OP::pack8(t), v1 = OP::pack8(t + 8);
-#if SCLDM_LEAN_VALU
         const float* vb = vb_row;
         asm volatile("" : "+v"(vb));        // re-read per token tile: holding the bias tile across both costs 16 registers where pressure peaks
         f32x16 ot = bias_tile(vb);
-#else
-        f32x16 ot = ot0;
-#endif
         ot = OP::mma(v0, Pf[ft][tt][0], ot);  // O^T[d][query], k = keys
         ot = OP::mma(v1, Pf[ft][tt][1], ot);
         acc[ft][tt] = ot;
@@ -1076,21 +935,14 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
-#if SCLDM_PAIR_STORE
       for (int q = 0; q < 4; q += 2)
         OP::store_quad_pair(AO + (tt * 32 + c32) * L::XA_LD, fbase + ft * 32 + q * 8, hh,
                             OP::pack4(acc[ft][tt][q * 4 + 0], acc[ft][tt][q * 4 + 1], acc[ft][tt][q * 4 + 2], acc[ft][tt][q * 4 + 3]),
                             OP::pack4(acc[ft][tt][q * 4 + 4], acc[ft][tt][q * 4 + 5], acc[ft][tt][q * 4 + 6], acc[ft][tt][q * 4 + 7]));
-#else
-      for (int q = 0; q < 4; ++q)
-        OP::store_quad(AO + (tt * 32 + c32) * L::XA_LD, fbase + ft * 32 + q * 8 + hh * 4,
-                       OP::pack4(acc[ft][tt][q * 4 + 0], acc[ft][tt][q * 4 + 1], acc[ft][tt][q * 4 + 2], acc[ft][tt][q * 4 + 3]));
-#endif
   lds_barrier();  // AO complete
   SCLDM_STAMP(6);
 
   // ---- attention projection, gated residual (a2), LN2 + modulate(a3 = scale, a4 = shift) -> XA ----
-#if SCLDM_LEAN_VALU
   {
     f32x16 pbias[FT];
 #pragma unroll
@@ -1115,21 +967,6 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
 #pragma unroll
         for (int i = 0; i < 4; ++i) xr[ft][tt][q * 4 + i] = fmaf(g[i], acc[ft][tt][q * 4 + i], xr[ft][tt][q * 4 + i]);
       }
-#else
-  gemm_pass<OP, NTT, FT, 16, false, true, PF>(acc, ws, AO, L::XA_LD, lane);
-#pragma unroll
-  for (int tt = 0; tt < NTT; ++tt)
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int f = fbase + ft * 32 + q * 8 + hh * 4;
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(bp + f);
-        const f32x4 g = OP::load_mod4(MOD + (tt * 2 + sp) * kModBlock + 2 * kD + f);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xr[ft][tt][q * 4 + i] = fmaf(g[i], acc[ft][tt][q * 4 + i] + b4[i], xr[ft][tt][q * 4 + i]);
-      }
-#endif
   SCLDM_STAMP(7);
   // (the statistics barrier inside also guarantees every wave has finished reading AO before XA is rewritten)
   ln_modulate_store<OP, NTT, FT, 16>(xr, MOD, 3, 4, a.eps, RED, XA, L::XA_LD, wave, lane, a.dbg, nothing);
@@ -1145,9 +982,6 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
     constexpr int TILES = (FT == 2 && HALF) ? 1 : FT;
     // rows 0-15 of each weight tile are w1, rows 16-31 the matching w2 rows => registers r and r+8 pair up
     Quad hq[TILES][NTT][2];
-    // one 32-row tile per pass: a two-tile up-projection pass (activation fragments read once) was measured at 30 spilled
-    // VGPRs and +1 % kernel time
-    constexpr bool kPair = SCLDM_W12_PAIR != 0;
     auto swiglu_pack = [&](const f32x16 (&t_acc)[NTT], Quad (&out)[NTT][2]) {
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt)
@@ -1155,18 +989,13 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
         for (int q = 0; q < 2; ++q) {
           float h[4];
 #pragma unroll
-#if SCLDM_PROXY & 4    // timing proxy 4 (WRONG RESULTS): SwiGLU replaced by a single multiply - what its exposed VALU costs
-          for (int i = 0; i < 4; ++i) h[i] = t_acc[tt][q * 4 + i] * t_acc[tt][8 + q * 4 + i];
-#else
           for (int i = 0; i < 4; ++i) h[i] = OP::swiglu(t_acc[tt][q * 4 + i], t_acc[tt][8 + q * 4 + i]);
-#endif
           out[tt][q] = OP::pack4(h[0], h[1], h[2], h[3]);
         }
     };
     // M16: the SwiGLU output of 16-token tile j, 4 hidden units per lane (see the store below)
     Quad hq16[M16 ? TILES : 1][M16 ? 2 * NTT : 1];
     if constexpr (M16) {
-      static_assert(HALF || !kPair, "M16: one-tile up-projection passes");
 #pragma unroll
       for (int ft = 0; ft < TILES; ++ft) {
         f32x4 a1[2 * NTT], b1[2 * NTT];
@@ -1177,17 +1006,14 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
                                   OP::swiglu(a1[j][3], b1[j][3]));
       }
     } else if constexpr (FT == 2) {
-      if constexpr (HALF || !kPair) {
+      // one 32-row tile per pass: a two-tile up-projection pass (activation fragments read once, -31 % LDS fragment reads per
+      // layer) holds 64 more accumulators live next to the residual: it spills 178 VGPRs at two waves per SIMD, and cost +1 %
+      // kernel time already when it spilled 30
 #pragma unroll
-        for (int ft = 0; ft < TILES; ++ft) {
-          f32x16 a1[NTT];
-          gemm_pass_tile<OP, NTT, PF>(a1, ws, XA, L::XA_LD, lane);
-          swiglu_pack(a1, hq[ft]);
-        }
-      } else {
-        gemm_pass<OP, NTT, FT, 16, false, true, PF>(acc, ws, XA, L::XA_LD, lane);
-#pragma unroll
-        for (int ft = 0; ft < TILES; ++ft) swiglu_pack(acc[ft], hq[ft]);
+      for (int ft = 0; ft < TILES; ++ft) {
+        f32x16 a1[NTT];
+        gemm_pass_tile<OP, NTT, PF>(a1, ws, XA, L::XA_LD, lane);
+        swiglu_pack(a1, hq[ft]);
       }
     } else {
       gemm_pass<OP, NTT, FT, 16, false, true, PF>(acc, ws, XA, L::XA_LD, lane);
@@ -1207,15 +1033,7 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
         continue;
       }
 #pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) {
-#if SCLDM_PAIR_STORE
-        OP::store_quad_pair(HBc + (tt * 32 + c32) * L::HB_LD, col0, hh, hq[ft][tt][0], hq[ft][tt][1]);
-#else
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          OP::store_quad(HBc + (tt * 32 + c32) * L::HB_LD, col0 + q * 8 + hh * 4, hq[ft][tt][q]);
-#endif
-      }
+      for (int tt = 0; tt < NTT; ++tt) OP::store_quad_pair(HBc + (tt * 32 + c32) * L::HB_LD, col0, hh, hq[ft][tt][0], hq[ft][tt][1]);
     }
     if (c == 0) SCLDM_STAMP(11);
     lds_barrier();
@@ -1274,9 +1092,7 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
 #pragma unroll
     for (int j = 0; j < kFinLd; ++j) {
       const int idx = tid + NT * j, sl = idx / (2 * kD / 4), w4 = idx % (2 * kD / 4);
-#if SCLDM_LEAN_VALU
       if (w4 >= kD / 4) fstage[j] += 1.0f;   // the final layer's second chunk is its scale (layers.py:398-399)
-#endif
       if (idx < NS * 2 * kD / 4) OP::store_mod4(MOD + sl * kModBlock + w4 * 4, fstage[j]);
     }
     ln_modulate_store<OP, NTT, FT>(xr, MOD, 1, 0, a.eps, RED, XA, L::XA_LD, wave, lane, a.dbg, nothing);
@@ -1308,15 +1124,13 @@ __global__ __launch_bounds__(64 * (8 / FT), (!SCLDM_FWD_ONE_WG && ((OP::kTwoWG &
   if (a.n_here > 1) layer_body(std::integral_constant<int, 1>{});
   if (a.n_here > 2) layer_body(std::integral_constant<int, 2>{});
   if (a.n_here > 3) layer_body(std::integral_constant<int, 3>{});
-#if SCLDM_MAX_LPL > 4
-  if constexpr (!REC || SCLDM_REC_LPL == 8) {
+  if constexpr (!REC) {
     if (a.n_here > 4) layer_body(std::integral_constant<int, 4>{});
     if (a.n_here > 5) layer_body(std::integral_constant<int, 5>{});
     if (a.n_here > 6) layer_body(std::integral_constant<int, 6>{});
     if (a.n_here > 7) layer_body(std::integral_constant<int, 7>{});
   }
-#endif
-  static_assert(kMaxLayersPerLaunch == 4 || kMaxLayersPerLaunch == 8, "one layer_body call per slot");
+  static_assert(kMaxLayersPerLaunch == 8 && kMaxLayersPerLaunchRec == 4, "one layer_body call per slot");
   SCLDM_STAMP_END(14);
 }
 

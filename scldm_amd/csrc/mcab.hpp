@@ -636,19 +636,11 @@ struct DecGeneArgs {
 // waves per SIMD (two workgroups per CU; 52 KB of LDS each): the chain of one tile is strictly dependent (MFMA -> softmax
 // / LayerNorm / SiLU -> MFMA), so the matrix pipe is kept busy by OTHER waves - three per SIMD left it idle a third of the
 // time (r2 PMC: SQ_VALU_MFMA_BUSY_CYCLES 67 % of the kernel, 68 % of wave cycles waiting on the pipe).
-#ifndef SCLDM_DEC_WAVES
-#define SCLDM_DEC_WAVES 8
-#endif
-constexpr int kDecWaves = SCLDM_DEC_WAVES;
+constexpr int kDecWaves = 8;
 constexpr int kDecThreads = 64 * kDecWaves;
+constexpr int kDecMinWaves = 4;   // waves per SIMD the fp32 instantiation is compiled for
 template <class OP>
-#ifndef SCLDM_DEC_UNROLL
-#define SCLDM_DEC_UNROLL 1   // the six SwiGLU tiles of a gene tile unrolled: the next tile's up-projection MFMAs issue under this tile's SiLU (+2 % fp32 decode)
-#endif
-#ifndef SCLDM_DEC_MINW
-#define SCLDM_DEC_MINW 4
-#endif
-__global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kDecWaves / 2 : 1) : SCLDM_DEC_MINW) void dec_gene_kernel(const DecGeneArgs a) {   // two workgroups per CU
+__global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kDecWaves / 2 : 1) : kDecMinWaves) void dec_gene_kernel(const DecGeneArgs a) {   // two workgroups per CU
   constexpr bool BF = McabOp<OP>::k16;
   using H8 = typename McabOp<OP>::Frag;
   constexpr int kWF4 = BF ? 1 : 40 * 64, kKV4 = BF ? 1 : kNI * 16, kWF8 = BF ? 20 * 64 : 1, kKV8 = BF ? 6 * 64 : 1;
@@ -853,12 +845,9 @@ __global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kD
       }
     }
     // SwiGLU: six tiles of 16 hidden units, each consumed by the down-projection as soon as it exists
+    // (unrolled: the next tile's up-projection MFMAs issue under this tile's SiLU, +2 % fp32 decode)
     f32x16 mo = zero16();
-#if SCLDM_DEC_UNROLL
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (int u = 0; u < kHTiles; ++u) {
       f32x16 ht = mm8(WF, WFh, 16 + 16 * u, yn, zero16());
       ht = mm8(WF, WFh, 16 + 16 * u + 8, yn + 8, ht);
@@ -1015,15 +1004,13 @@ struct EncPoolArgs {
 // Waves per SIMD (same-box A/B, 1 024 cells x 6 147 genes): the bf16-operand kernel is VALU / latency bound and gains 11 % from
 // three waves (168 VGPRs, 24 B of scratch) over two; the fp32 kernel is half matrix-pipe bound and is 7 % faster at two waves
 // without spills (218 VGPRs) once the gather is software-pipelined.
-#ifndef SCLDM_ENC_MINW
-#define SCLDM_ENC_MINW 3
-#endif
+constexpr int kEncMinWaves = 3;
 // NW = waves per cell (round 4).  A cell is one workgroup; with four waves of 168 registers a CU holds three cells, so 1 024 cells are
 // 1.33 rounds of the chip's 768 slots - the second round a third full.  Six waves per cell (two cells per CU, 512 slots) make it two
 // full rounds of cells that each finish in 4/6 of the time; the gene tiles are dealt round-robin over the waves and merged in wave
 // order at the end, so NW changes the summation order of the online softmax merge (not its value beyond fp32 rounding).
 template <class OP, int NW = 4>
-__global__ __launch_bounds__(64 * NW, McabOp<OP>::k16 ? SCLDM_ENC_MINW : 2) void enc_pool_kernel(const EncPoolArgs a) {
+__global__ __launch_bounds__(64 * NW, McabOp<OP>::k16 ? kEncMinWaves : 2) void enc_pool_kernel(const EncPoolArgs a) {
   constexpr bool BF = McabOp<OP>::k16;
   using H8 = typename McabOp<OP>::Frag;
   __shared__ f32x4 KF[4 * 64], VF[4 * 64], QF[4 * 64];

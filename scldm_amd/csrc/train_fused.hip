@@ -10,7 +10,8 @@
 #include <vector>
 
 #include "api_common.hpp"
-// the fused backward layer, once per 16-bit operand policy (see the header of dit_backward.hpp)
+// the fused backward layer, once per 16-bit operand policy and tile size (see the header of dit_backward.hpp): 64-token tiles ...
+#define SCLDM_BWD_NTT 2
 #define SCLDM_BWD_NS bwd
 #define SCLDM_BWD_OP OpBF16
 #include "dit_backward.hpp"
@@ -21,7 +22,8 @@
 #include "dit_backward.hpp"
 #undef SCLDM_BWD_NS
 #undef SCLDM_BWD_OP
-// ... and on 32-token tiles (batches of at most 512 cells)
+#undef SCLDM_BWD_NTT
+// ... and 32-token tiles (batches of at most 512 cells)
 #define SCLDM_BWD_NTT 1
 #define SCLDM_BWD_NS bwd32
 #define SCLDM_BWD_OP OpBF16
@@ -95,11 +97,7 @@ struct WgradArgs {
   int n_jobs, T, kchunk, splits;
   float* part;
 };
-#ifndef SCLDM_WGRAD_STAGES
-#define SCLDM_WGRAD_STAGES 2
-#endif
-constexpr int kWStages = SCLDM_WGRAD_STAGES;   // register stages in flight per operand (2 or 3)
-static_assert(kWStages == 2 || kWStages == 3, "two or three register stages");
+constexpr int kWStages = 2;        // register stages in flight per operand (a third measured +-0, see wgrad_bf16_kernel)
 constexpr int kWK = 64;            // tokens per staged tile
 constexpr int kWLD = 128 + 32;     // bf16 elements per LDS row of a [token][feature] image (320 B: the 8-byte pieces of the transposing
                                    // fragment reads of a 32-lane half - 2 groups x 4 token rows - fall on eight distinct 32-byte bank ranges)
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgradArgs g) {
 
   // kWStages register stages per operand: the loads of stage i + kWStages are issued while stage i is multiplied and stage i + 1
   // (requested kWStages - 1 whole iterations earlier) is written to LDS.  Round 5: 42 % of the kernel's wave cycles are vmcnt waits
-  // (profiles/r5_pmc_train_sq1.txt), but a third stage (-DSCLDM_WGRAD_STAGES=3) measured +-0 (45.4 against 45.2 us): the loads wait on
+  // (profiles/r5_pmc_train_sq1.txt), but a third stage measured +-0 (45.4 against 45.2 us): the loads wait on
   // bandwidth (3.9 TB/s at the fabric with a 66 % L2 hit rate), not on too short a prefetch distance.  Barriers order LDS only
   // (lds_barrier): __syncthreads() would drain the loads in flight.
   OperandLoader la[kWStages], lb[kWStages];
@@ -250,8 +248,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const WgradArgs g) {
   for (int it = 0; it < n_it; it += kWStages) {
     iteration(it, std::integral_constant<int, 0>{});
     if (it + 1 < n_it) iteration(it + 1, std::integral_constant<int, 1>{});
-    if constexpr (kWStages > 2)
-      if (it + 2 < n_it) iteration(it + 2, std::integral_constant<int, 2 % kWStages>{});
   }
   if (want_rs) {   // the 16 threads (tid / 16) that share a feature chunk hold partial sums of the same eight rows
     float* red = reinterpret_cast<float*>(wgrad_smem);   // [16][128]

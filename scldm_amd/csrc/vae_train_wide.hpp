@@ -58,18 +58,11 @@ static_assert(LDS_BYTES <= 160 * 1024, "cell-side LDS image");
 
 // ---- synchronisation ----------------------------------------------------------------------------------------------------------------
 // tsync: orders LDS traffic among the 16 lanes of a token (one wave: LDS instructions of a wave complete in order, the fences stop
-// the compiler from moving them).  SCLDM_VAE_TSYNC_WG=1 builds with full barriers instead (A/B and debugging).
-#ifndef SCLDM_VAE_TSYNC_WG
-#define SCLDM_VAE_TSYNC_WG 0
-#endif
+// the compiler from moving them).
 __device__ __forceinline__ void tsync() {
-#if SCLDM_VAE_TSYNC_WG
-  __syncthreads();
-#else
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
 }
 
 // ---- lane exchanges -----------------------------------------------------------------------------------------------------------------
@@ -138,11 +131,7 @@ __device__ __forceinline__ void copy_small(float* __restrict__ dst, const float*
 }
 
 // ---- the three contractions -----------------------------------------------------------------------------------------------------------
-// y[o] = W[o][:] . x for o = j, j + 16, ...: f(m, o, value).  k-outer with the next k piece of every output row requested before
-// this piece's FMAs (one wave per SIMD: nothing else hides the LDS latency; SCLDM_VAE_LIN_PIPE=0 = one output row at a time).
-#ifndef SCLDM_VAE_LIN_PIPE
-#define SCLDM_VAE_LIN_PIPE 1
-#endif
+// y[o] = W[o][:] . x for o = j, j + 16, ...: f(m, o, value), one output row at a time
 template <int OUT, class F>
 __device__ __forceinline__ void lin32(const float* __restrict__ W, const float* __restrict__ xrow, int j, F f) {
   f32x4 x[8];
@@ -162,10 +151,10 @@ __device__ __forceinline__ void lin32(const float* __restrict__ W, const float* 
     f(m, o, s0 + s1);
   }
 }
-// the cell-side kernels' form (one wave per SIMD, registers to spare): all output rows advance together
+// the cell-side kernels' form (one wave per SIMD, registers to spare): all output rows advance together, k-outer, with the next k
+// piece of every output row requested before this piece's FMAs (nothing else hides the LDS latency there)
 template <int OUT, class F>
 __device__ __forceinline__ void lin32p(const float* __restrict__ W, const float* __restrict__ xrow, int j, F f) {
-#if SCLDM_VAE_LIN_PIPE
   constexpr int NO = OUT / 16;
   f32x4 x[8];
 #pragma unroll
@@ -192,9 +181,6 @@ __device__ __forceinline__ void lin32p(const float* __restrict__ W, const float*
   }
 #pragma unroll
   for (int m = 0; m < NO; ++m) f(m, j + 16 * m, s[m]);
-#else
-  lin32<OUT>(W, xrow, j, f);
-#endif
 }
 // acc[c] += sum over the rows o with ((o >> 3) & 1) == (j >> 3) of W[o][4 (j & 7) + c] dy[o]   (finish with half_sum4)
 template <int OUT>
@@ -213,7 +199,6 @@ __device__ __forceinline__ void lin32_t_acc(const float* __restrict__ W, const f
 // the cell-side kernels' form: the next group's five loads are requested before this group's FMAs, two accumulator chains
 template <int OUT>
 __device__ __forceinline__ void lin32_t_accp(const float* __restrict__ W, const float* __restrict__ dyrow, int j, f32x4& acc) {
-#if SCLDM_VAE_LIN_PIPE
   const int ib = j & 7, hf = j >> 3;
   constexpr int NG = OUT / 8;          // groups of four output rows: o0 = 16 (t >> 1) + 8 hf + 4 (t & 1)
   f32x4 dc = *v4(dyrow + 8 * hf), wc[4], dn = dc, wn[4];
@@ -237,9 +222,6 @@ __device__ __forceinline__ void lin32_t_accp(const float* __restrict__ W, const 
     for (int e = 0; e < 4; ++e) wc[e] = wn[e];
   }
   acc += acc2;
-#else
-  lin32_t_acc<OUT>(W, dyrow, j, acc);
-#endif
 }
 // dW[o][i] = sum_t DY[t][o] X[t][i] for o = tid >> 3 (+ 32 m), i = 4 (tid & 7) .. + 3; stored at dst[o * ld_o + i * ld_i]
 template <int OUT>
