@@ -107,7 +107,10 @@ class _RoundedMatmul(torch.autograd.Function):
         a, b = ctx.saved_tensors
         rg = round_operand(g.contiguous())
         ga = (rg @ round_operand(b).transpose(-1, -2)).sum_to_size(a.shape)
-        gb = (round_operand(a).transpose(-1, -2) @ rg).sum_to_size(b.shape)
+        if b.dim() == 2 and a.dim() > 2:    # a Linear's weight: one product over all rows (not one per cell, summed afterwards)
+            gb = round_operand(a).reshape(-1, a.shape[-1]).transpose(0, 1) @ rg.reshape(-1, rg.shape[-1])
+        else:
+            gb = (round_operand(a).transpose(-1, -2) @ rg).sum_to_size(b.shape)
         return ga, gb
 
 

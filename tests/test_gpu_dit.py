@@ -5,7 +5,11 @@ Tolerances (conftest.check_err: scale-relative max error max|a-b| / max|b| asser
 relative error floored at 1 % of max|b| printed beside it and asserted against 10 x the tolerance):
   fp32 path   (exact-fp32 MFMA): 1e-4  - BASELINE.json north_star gate
   bf16x3 path (split-bf16, three bf16 MFMAs per product sum - the reference's "high" matmul precision class): 1e-4, same gate
-  bf16 path   (bf16 operands, fp32 accumulate/LN/softmax/residual): 3e-2 (bf16 has 8 mantissa bits; 8 layers deep)
+  bf16 path   (bf16 operands, fp32 accumulate/LN/softmax/residual): the arithmetic-class gate of tests/precision_class.py -
+              rel-L2(kernel, exact) <= 1.5 x rel-L2(oracle with every matmul operand rounded to bf16, exact) on the same inputs,
+              over the whole batch, worst cell printed - AND the flat 3e-2 on the scale-relative max error that it replaced
+  fp16 path   (fp16 operands = TF32's 10 mantissa bits, the reference's own matmul precision): 1.5 x the TF32-operand oracle
+Comparisons of one kernel route with another (tile shapes, launch groupings) are bitwise, or keep their flat bounds.
 """
 import numpy as np
 import pytest
@@ -15,6 +19,7 @@ from conftest import check_err, golden_json, load_golden, max_abs_rel
 from oracle.dit import DiTConfig, dit_forward, dit_forward_with_cfg
 from oracle.transport import sample_ode_fixed
 from oracle.weights import make_state_dict
+from precision_class import class_error, class_gate, distances, exact_result, forward_case, gate_tensor
 
 pytestmark = pytest.mark.gpu
 TOL_FP32 = 1e-4
@@ -22,7 +27,11 @@ TOL_BF16 = 3e-2
 PARITY = [("fp32", TOL_FP32), ("bf16x3", TOL_FP32)]
 # bound on the floored ELEMENTWISE relative error (an element at 1 % of the output scale): fp32 measures <= 1.3e-4, split-bf16
 # <= 1.5e-3 (its scale-relative error is 1-2e-5; CFG with scale 2 doubles differences), bf16 is reported only
-FLOOR_TOL = {"fp32": 1e-3, "bf16x3": 5e-3, "bf16": float("inf")}
+FLOOR_TOL = {"fp32": 1e-3, "bf16x3": 5e-3, "bf16": float("inf"), "fp16": float("inf")}
+# the 16-bit legs: class-gated at BITS mantissa bits (precision_class.py); the flat bound beside the gate is bf16's for both (fp16
+# keeps three more bits than bf16, so it may not be further out than bf16 is allowed to be)
+BITS = {"bf16": 7, "fp16": 10}
+SIXTEEN = [("bf16", TOL_BF16), ("fp16", TOL_BF16)]
 
 
 def build(name, precision="fp32"):
@@ -53,13 +62,17 @@ def test_forward_matches_reference_golden(name, precision, tol):
     y = m(cu(g["fwd_x"]), cu(g["fwd_t"]), cond)
     assert y.shape == g["fwd_out"].shape and torch.isfinite(y).all()
     check_err(y.cpu(), g["fwd_out"], tol, f"forward {name} [{precision}] vs reference golden", FLOOR_TOL[precision])
+    if precision == "bf16":
+        xc, tc, cc = torch.from_numpy(g["fwd_x"]), torch.from_numpy(g["fwd_t"]), {k: v.cpu() for k, v in cond.items()}
+        gate_tensor(y.cpu(), g["fwd_out"], lambda: dit_forward(sd, cfg, xc, tc, cc), 7, f"forward {name} vs reference golden",
+                    tag=f"golden_fwd/{name}")
 
 
 @pytest.mark.parametrize("name", ["dit_base", "dit_joint", "dit_me2_256"])
 @pytest.mark.parametrize("tag", ["s1", "s2"])
-@pytest.mark.parametrize("precision,tol", PARITY)
+@pytest.mark.parametrize("precision,tol", PARITY + SIXTEEN)
 def test_forward_with_cfg_matches_reference_golden(name, tag, precision, tol):
-    """dit_me2_256: two mutually-exclusive classes = TWO conditional passes through the fused kernel with distinct scales
+    """The 16-bit kernels too (the only users of the 16x16x32 MFMA path), class-gated on both t paths.  dit_me2_256: two mutually-exclusive classes = TWO conditional passes through the fused kernel with distinct scales
     (nnets.py:372-376; VERDICT r1 weak #3).  The golden t is the scalar broadcast an ODE solver passes (integrators.py:103-104)."""
     g, m, cfg, sd = build(name, precision)
     cond = {k: cu(g[f"cfg_label_{k}"]) for k in cfg.class_vocab_sizes}
@@ -73,6 +86,12 @@ def test_forward_with_cfg_matches_reference_golden(name, tag, precision, tol):
     check_err(y2.cpu(), g[f"cfg_out_{tag}"], tol, f"forward_with_cfg {name}/{tag} [{precision}] dense uniform t", FLOOR_TOL[precision])
     y3 = m.forward_with_cfg(x, t[:1].expand(t.shape[0]), cond, scales)   # stride-0 view (what scldm_amd.transport passes): no sync
     assert torch.equal(y3, y2)
+    if precision in BITS:
+        xc, tc, cc = x.cpu(), t.cpu(), {k: v.cpu() for k, v in cond.items()}
+        fn = lambda: dit_forward_with_cfg(sd, cfg, xc, tc, cc, scales)
+        for path, out in (("per-sample t", y), ("dense uniform t", y2)):
+            gate_tensor(out.cpu(), g[f"cfg_out_{tag}"], fn, BITS[precision], f"forward_with_cfg {name}/{tag} {path}",
+                        tag=f"golden_cfg/{name}/{tag}")
 
 
 # ---- the reference-class fast precision: fp16 operands = TF32's 10 mantissa bits (VERDICT r2 missing #3) ------------------------
@@ -84,13 +103,10 @@ TF32_FACTOR = 1.5
 
 @pytest.mark.parametrize("name", ["dit_base", "dit_joint", "dit_me2_256"])
 def test_fp16_forward_is_in_the_references_tf32_class(name):
-    from oracle.dit import matmul_operand_bits
     g, m, cfg, sd = build(name, "fp16")
     cond_c = {k: torch.from_numpy(g[f"fwd_label_{k}"]) for k in golden_json(g, "fwd_classes")}
     x, t = torch.from_numpy(g["fwd_x"]), torch.from_numpy(g["fwd_t"])
-    with matmul_operand_bits(10):
-        y_tf32 = dit_forward(sd, cfg, x, t, cond_c)
-    e_tf32 = max_abs_rel(y_tf32, g["fwd_out"])
+    e_tf32 = class_error(lambda: dit_forward(sd, cfg, x, t, cond_c), 10, g["fwd_out"], tag=f"golden_fwd/{name}")["max_abs_rel"]
     y = m(x.cuda(), t.cuda(), {k: v.cuda() for k, v in cond_c.items()})
     e = max_abs_rel(y.cpu(), g["fwd_out"])
     print(f"[parity] forward {name} [fp16] vs reference golden: {e:.3e}; TF32-operand oracle vs the same golden: {e_tf32:.3e} (ratio {e / e_tf32:.2f})")
@@ -102,9 +118,8 @@ def test_fp16_forward_is_in_the_references_tf32_class(name):
         condc = {k: torch.from_numpy(g[f"cfg_label_{k}"]) for k in cfg.class_vocab_sizes}
         scales = golden_json(g, f"cfg_scales_{tag}")
         xc, tc = torch.from_numpy(g["cfg_x"]), torch.from_numpy(g["cfg_t"])
-        with matmul_operand_bits(10):
-            r_tf32 = dit_forward_with_cfg(sd, cfg, xc, tc, condc, scales)
-        e_tf32 = max_abs_rel(r_tf32, g[f"cfg_out_{tag}"])
+        e_tf32 = class_error(lambda: dit_forward_with_cfg(sd, cfg, xc, tc, condc, scales), 10, g[f"cfg_out_{tag}"],
+                             tag=f"golden_cfg/{name}/{tag}")["max_abs_rel"]
         yc = m.forward_with_cfg(xc.cuda(), tc.cuda(), {k: v.cuda() for k, v in condc.items()}, scales)
         e = max_abs_rel(yc.cpu(), g[f"cfg_out_{tag}"])
         print(f"[parity] forward_with_cfg {name}/{tag} [fp16]: {e:.3e}; TF32-operand oracle: {e_tf32:.3e} (ratio {e / e_tf32:.2f})")
@@ -177,7 +192,7 @@ def test_long_trajectories_at_every_precision(tag, vocab, strategy, method, step
     2.0; 100 Euler evaluations), 4 cells (8 until round 4: the float64 CPU chains were 40 % of the GPU suite's wall time), every precision
     policy, against the float64 oracle chain.  fp32 and bf16x3 stay inside the
     1e-4 gate; fp16 within 1.5 x the distance of the TF32-operand oracle (the reference's own arithmetic) from the same float64
-    chain; bf16 is reported and bounded by its own tolerance."""
+    chain; bf16 within 1.5 x the bf16-operand oracle's distance (rel-L2) and inside its flat bound."""
     from oracle.dit import matmul_operand_bits
     from scldm_amd.nnets import DiT
     kw = dict(n_embed=256, n_embed_input=16, n_layer=8, n_head=8, seq_len=16, dropout=0.0, bias=True, norm_layer="layernorm",
@@ -203,6 +218,7 @@ def test_long_trajectories_at_every_precision(tag, vocab, strategy, method, step
             e_tf32 = max_abs_rel(sample_ode_fixed(z2, f32, steps, method), ref64.float())
     finally:
         torch.set_num_threads(n_thr)
+    cls_bf16 = class_error(lambda: sample_ode_fixed(z2, f32, steps, method), 7, ref64.float(), tag=f"long/{tag}")   # one more chain, 7 bits
     condg = {k: v.cuda() for k, v in cond.items()}
     errs = {}
     for prec in ("fp32", "bf16x3", "fp16", "bf16"):
@@ -210,12 +226,15 @@ def test_long_trajectories_at_every_precision(tag, vocab, strategy, method, step
         out = m.sample_ode_cfg(z2.cuda(), condg, scales, steps, method)
         assert torch.isfinite(out).all()
         errs[prec] = max_abs_rel(out.cpu(), ref64.float())
+    rec_bf16 = distances(out.cpu(), ref64.float())
     n_eval = (steps - 1) * (2 if method == "heun" else 1)
     print(f"[parity] long trajectory {tag} ({n_eval} CFG evaluations, guidance {scale}) vs float64 oracle: "
           + ", ".join(f"{k} {v:.3e}" for k, v in errs.items()) + f"; TF32-operand oracle {e_tf32:.3e}")
     assert errs["fp32"] < TOL_FP32 and errs["bf16x3"] < TOL_FP32
     assert errs["fp16"] <= TF32_FACTOR * e_tf32
     assert errs["bf16"] < TOL_BF16
+    class_gate(rec_bf16["rel_l2"], cls_bf16["rel_l2"], f"long trajectory {tag} ({n_eval} CFG evaluations) vs float64 oracle",
+               note=f"   worst cell: kernel {max(rec_bf16['per_cell']):.3e}, oracle {max(cls_bf16['per_cell']):.3e}")
 
 
 @pytest.mark.parametrize("strategy,vocab", [("mutually_exclusive", {"clusters": 14}), ("joint", {"cell_line": 4, "gene": 30})])
@@ -342,6 +361,9 @@ def test_adaln_kernels_give_a_cell_the_same_bits_in_any_batch(precision):
         ref = sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), 3, "euler")
         got = torch.cat([whole[idx], whole[idx + B]]).cpu()
         assert max_abs_rel(got, ref) < (TOL_FP32 if precision == "bf16x3" else TOL_BF16)
+        if precision == "bf16":
+            gate_tensor(got, ref, lambda: sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), 3, "euler"),
+                        7, "adaLN block kernel, 8 of 400 cells x 3 Euler vs oracle")
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
@@ -441,34 +463,62 @@ def test_forward_with_cfg_uniformity_is_decided_on_device(name):
 
 
 @pytest.mark.parametrize("n", [1, 3, 8, 13, 37])
-@pytest.mark.parametrize("precision,tol", PARITY)
+@pytest.mark.parametrize("precision,tol", PARITY + SIXTEEN)
 def test_ragged_batches_vs_oracle(n, precision, tol):
-    """Batch sizes that do not fill a 64/128-token tile (tile padding, odd sample pairing)."""
+    """Batch sizes that do not fill a 64/128-token tile (tile padding, odd sample pairing); the 16-bit kernels (32-token tiles at
+    these sizes, 16x16x32 MFMA) are class-gated."""
     g, m, cfg, sd = build("dit_base", precision)
     rng = np.random.default_rng(n)
     x = rng.standard_normal((n, 16, 16)).astype(np.float32)
     t = rng.uniform(0, 1, n).astype(np.float32)
     lab = rng.integers(0, 14, n).astype(np.int64)
-    ref = dit_forward(sd, cfg, torch.from_numpy(x), torch.from_numpy(t), {"clusters": torch.from_numpy(lab)})
+    fn = lambda: dit_forward(sd, cfg, torch.from_numpy(x), torch.from_numpy(t), {"clusters": torch.from_numpy(lab)})
+    ref = exact_result(fn, f"ragged/{n}")
     y = m(cu(x), cu(t), {"clusters": cu(lab)})
     check_err(y.cpu(), ref, tol, f"ragged n={n} [{precision}] vs oracle", FLOOR_TOL[precision])
+    if precision in BITS:
+        gate_tensor(y.cpu(), ref, fn, BITS[precision], f"ragged n={n} vs oracle", tag=f"ragged/{n}")
 
 
 def test_bf16_vs_oracle_medium_batch():
+    """96 cells: the inputs on which tests/test_precision_class_cpu.py shows that a lost mantissa bit (ratio 2.0) and a truncating
+    pack (3.8) fall outside the class gate."""
     g, m, cfg, sd = build("dit_base", "bf16")
-    rng = np.random.default_rng(5)
-    n = 96
-    x = rng.standard_normal((n, 16, 16)).astype(np.float32)
-    t = rng.uniform(0, 1, n).astype(np.float32)
-    lab = rng.integers(0, 14, n).astype(np.int64)
-    ref = dit_forward(sd, cfg, torch.from_numpy(x), torch.from_numpy(t), {"clusters": torch.from_numpy(lab)})
+    x, t, lab = forward_case(96, 5)
+    fn = lambda: dit_forward(sd, cfg, torch.from_numpy(x), torch.from_numpy(t), {"clusters": torch.from_numpy(lab)})
+    ref = exact_result(fn, "medium96")
     y = m(cu(x), cu(t), {"clusters": cu(lab)})
     assert max_abs_rel(y.cpu(), ref) < TOL_BF16
+    gate_tensor(y.cpu(), ref, fn, 7, "forward dit_base, 96 cells vs oracle", tag="medium96")
+
+
+@pytest.mark.parametrize("n_layer", [1, 2])
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_shallow_models_are_in_their_arithmetic_class(n_layer, precision):
+    """One and two layers (a one-layer launch, and one two-layer launch), 96 cells = 48 32-token tiles: the error of a single layer
+    is what a slip in the tile mapping of one GEMM pass changes first - eight layers deep it is diluted by the rounding noise of the
+    other seven.  Class-gated at 7 / 10 bits."""
+    from scldm_amd.nnets import DiT
+    kw = dict(n_embed=256, n_embed_input=16, n_layer=n_layer, n_head=8, seq_len=16, dropout=0.0, bias=True, norm_layer="layernorm",
+              multiple_of=4, layernorm_eps=1e-8, class_vocab_sizes={"clusters": 14}, cfg_dropout_prob=0.8)
+    m = DiT(**kw)
+    sd = make_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 70 + n_layer)
+    m.load_state_dict(sd)
+    m = m.cuda().eval()
+    m.precision = precision
+    cfg = DiTConfig(n_layer=n_layer, class_vocab_sizes={"clusters": 14})
+    x, t, lab = forward_case(96, 20 + n_layer)
+    fn = lambda: dit_forward(sd, cfg, torch.from_numpy(x), torch.from_numpy(t), {"clusters": torch.from_numpy(lab)})
+    ref = exact_result(fn, f"shallow/{n_layer}")
+    with torch.no_grad():
+        y = m(cu(x), cu(t), {"clusters": cu(lab)})
+    assert torch.isfinite(y).all() and max_abs_rel(y.cpu(), ref) < TOL_BF16
+    gate_tensor(y.cpu(), ref, fn, BITS[precision], f"{n_layer}-layer model, 96 cells vs oracle", tag=f"shallow/{n_layer}")
 
 
 @pytest.mark.parametrize("name,method,steps", [("dit_base", "euler", 5), ("dit_base", "heun", 4), ("dit_joint", "euler", 4),
                                                ("dit_me2_256", "euler", 5), ("dit_me2_256", "heun", 3)])
-@pytest.mark.parametrize("precision,tol", PARITY)
+@pytest.mark.parametrize("precision,tol", PARITY + SIXTEEN)
 def test_fused_sampler_vs_oracle(name, method, steps, precision, tol):
     g, m, cfg, sd = build(name, precision)
     rng = np.random.default_rng(11)
@@ -478,9 +528,12 @@ def test_fused_sampler_vs_oracle(name, method, steps, precision, tol):
     scales = {k: 1.5 - 0.4 * i for i, k in enumerate(sorted(cfg.class_vocab_sizes))}   # distinct per class (two passes for dit_me2_256)
     z2 = torch.from_numpy(np.concatenate([z0, z0]))
     cond2 = {k: torch.from_numpy(np.concatenate([v, v])) for k, v in labs.items()}
-    ref = sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, cond2, scales), steps, method)
+    fn = lambda: sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, cond2, scales), steps, method)
+    ref = exact_result(fn, f"sampler/{name}/{method}{steps}")
     out = m.sample_ode_cfg(z2.cuda(), {k: v.cuda() for k, v in cond2.items()}, scales, steps, method)
     check_err(out.cpu(), ref, tol, f"fused sampler {name} {method} x{steps} [{precision}] vs oracle", FLOOR_TOL[precision])
+    if precision in BITS:
+        gate_tensor(out.cpu(), ref, fn, BITS[precision], f"fused sampler {name} {method} x{steps} vs oracle", tag=f"sampler/{name}/{method}{steps}")
     # the generic reference-style call chain (Sampler -> lambda -> forward_with_cfg) gives the same trajectory end
     from scldm_amd.transport import Sampler, create_transport
     fn = Sampler(create_transport("Linear", "velocity", "velocity", 1e-5, 1e-5)).sample_ode(sampling_method=method, num_steps=steps)
@@ -488,7 +541,8 @@ def test_fused_sampler_vs_oracle(name, method, steps, precision, tol):
     model_fn = lambda x, t, **kw: m.forward_with_cfg(x, t, **kw, cfg_scale=scales)
     traj = fn(z2.cuda(), model_fn, **{"condition": condc})
     assert traj.shape[0] == steps and max_abs_rel(traj[-1].cpu(), ref) < tol
-    assert max_abs_rel(traj[-1].cpu(), out.cpu()) < 1e-5
+    if precision not in BITS:      # (16-bit operands: a last-place difference of the state flips operand roundings of the next evaluation)
+        assert max_abs_rel(traj[-1].cpu(), out.cpu()) < 1e-5
 
 
 def test_bitwise_repeatability_and_batch_permutation_at_full_size():
@@ -508,8 +562,10 @@ def test_bitwise_repeatability_and_batch_permutation_at_full_size():
     assert torch.equal(y3, y1[perm])
     # spot-check 16 random cells of the big batch against the oracle
     idx = perm[:16].cpu()
-    ref = dit_forward(sd, cfg, x.cpu()[idx], t.cpu()[idx], {"clusters": lab.cpu()[idx]})
+    xs, ts, ls = x.cpu()[idx], t.cpu()[idx], lab.cpu()[idx]
+    ref = dit_forward(sd, cfg, xs, ts, {"clusters": ls})
     assert max_abs_rel(y1.cpu()[idx], ref) < TOL_BF16
+    gate_tensor(y1.cpu()[idx], ref, lambda: dit_forward(sd, cfg, xs, ts, {"clusters": ls}), 7, "16 cells of a 12288 batch vs oracle")
 
 
 def test_error_paths():
@@ -555,7 +611,7 @@ def test_headline_workload_vs_oracle(prec):
     """VERDICT r5 next #5a: the BENCH workload itself (`dentate_b4096_euler100`: bench.py's own make_model / make_inputs / seed, 4 096
     cells x 100 CFG Euler evaluations = 12 288 sample-forwards per evaluation) against the float32 oracle chain on 8 cells spread over
     the batch.  fp16 (the reference's arithmetic class) within 1.5 x the TF32-operand oracle on the same cells; bf16 (the dtype
-    BASELINE.json names, narrower than the reference) <= 3e-2."""
+    BASELINE.json names, narrower than the reference) within 1.5 x the bf16-operand oracle (rel-L2) and <= 3e-2."""
     import bench
     from oracle.dit import matmul_operand_bits
     wl = bench.WORKLOADS["dentate_b4096_euler100"]
@@ -578,6 +634,9 @@ def test_headline_workload_vs_oracle(prec):
             e_tf32 = max_abs_rel(sample_ode_fixed(zs, f32, steps, wl["method"]), ref)
     finally:
         torch.set_num_threads(n_thr)
+    if prec == "bf16":
+        gate_tensor(out[rows].cpu(), ref, lambda: sample_ode_fixed(zs, f32, steps, wl["method"]), 7,
+                    "headline workload dentate_b4096_euler100, 8 cells of 4096 vs float32 oracle chain")
     err = max_abs_rel(out[rows].cpu(), ref)
     print(f"[parity] headline workload dentate_b4096_euler100 [{prec}] 8 cells of 4096 vs float32 oracle chain: {err:.3e}   "
           f"TF32-operand oracle {e_tf32:.3e}")
@@ -621,9 +680,11 @@ def test_fused_sampler_full_size_properties(vocab, strategy, B, method, steps, s
     idx = torch.tensor([0, 7, B // 2, B - 1])
     z2 = torch.cat([z0[idx.cuda()], z0[idx.cuda()]]).cpu()
     c2 = {k: torch.cat([v[idx.cuda()], v[idx.cuda()]]).cpu() for k, v in cond.items()}
-    ref = sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), steps, method)
+    fn = lambda: sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), steps, method)
+    ref = fn()
     got = torch.cat([out1[idx.cuda()], out1[(idx + B).cuda()]]).cpu()
     assert max_abs_rel(got, ref) < TOL_BF16
+    gate_tensor(got, ref, fn, 7, f"fused sampler at full size ({strategy}, B {B}, {method} x{steps - 1}), 4 cells vs oracle chain")
 
 
 _DOPRI5_ORACLE: dict = {}
@@ -732,7 +793,11 @@ def test_odd_layer_counts(n_layer, precision, tol):
     lab = torch.randint(0, 14, (9,), generator=gen)
     with torch.no_grad():
         y = m(x.cuda(), t.cuda(), {"clusters": lab.cuda()})
-    assert max_abs_rel(y.cpu(), dit_forward(sd, cfg, x, t, {"clusters": lab})) < tol
+    fn = lambda: dit_forward(sd, cfg, x, t, {"clusters": lab})
+    ref = fn()
+    assert max_abs_rel(y.cpu(), ref) < tol
+    if precision == "bf16":
+        gate_tensor(y.cpu(), ref, fn, 7, f"{n_layer}-layer model, 9 cells vs oracle")
 
 
 def test_tile_group_launches_are_bit_identical(monkeypatch):
@@ -826,9 +891,11 @@ def test_dentate_b512_euler50_bf16_properties():
     idx = torch.arange(0, B, 64, device="cuda")
     z2 = torch.cat([z0[idx], z0[idx]]).cpu()
     c2 = {"clusters": torch.cat([cond["clusters"][idx]] * 2).cpu()}
-    ref = sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), 51, "euler")
+    fn = lambda: sample_ode_fixed(z2, lambda x, t: dit_forward_with_cfg(sd, cfg, x, t, c2, scales), 51, "euler")
+    ref = fn()
     got = torch.cat([out[idx], out[idx + B]]).cpu()
     check_err(got, ref, TOL_BF16, "dentate b512 x 50 Euler [bf16] vs oracle chain (8 cells)")
+    gate_tensor(got, ref, fn, 7, "dentate b512 x 50 Euler vs oracle chain (8 cells)")
 
 
 def test_dit_l_depth_parity_fp32():
@@ -943,7 +1010,11 @@ def test_inplace_data_updates_are_picked_up(precision):
     assert not torch.equal(y1, y0)
     sd2 = {k: v.detach().cpu() for k, v in m.state_dict().items()}
     tol = TOL_BF16 if precision == "bf16" else TOL_FP32
-    check_err(y1.cpu(), dit_forward(sd2, cfg, x.cpu(), t.cpu(), {k: v.cpu() for k, v in cond.items()}), tol, f"after .data update [{precision}]", FLOOR_TOL[precision])
+    fn = lambda: dit_forward(sd2, cfg, x.cpu(), t.cpu(), {k: v.cpu() for k, v in cond.items()})
+    ref = fn()
+    check_err(y1.cpu(), ref, tol, f"after .data update [{precision}]", FLOOR_TOL[precision])
+    if precision == "bf16":
+        gate_tensor(y1.cpu(), ref, fn, 7, "after .data update vs oracle")
     m.blocks[3].mlp.w1.weight.data[5, 7] += 1.0     # a single element of a large tensor: the fingerprint covers EVERY element
     y2 = m(x, t, cond)
     assert not torch.equal(y2, y1)
@@ -979,5 +1050,5 @@ def test_bit_repeatability_across_shapes_and_launch_groupings(precision, knobs, 
     if not any(k in knobs for k in ("SCLDM_FT", "SCLDM_X3_FT", "SCLDM_X3_NTT")) or (precision != "bf16x3" and "SCLDM_X3_NTT" in knobs):
         assert torch.equal(ys[0], ref)            # same kernel shape, other grouping: identical
     else:
-        tol = TOL_BF16 if precision in ("bf16", "fp16") else TOL_FP32
+        tol = TOL_BF16 if precision in ("bf16", "fp16") else TOL_FP32      # (kernel shape against kernel shape: a flat bound, no oracle)
         assert max_abs_rel(ys[0].cpu(), ref.cpu()) < tol   # another reduction tree: close, not identical

@@ -9,6 +9,7 @@ from conftest import golden_json, load_golden, max_abs_rel
 from oracle.dit import DiTConfig
 from oracle.train import FROZEN, grad_digest, training_grads
 from oracle.weights import make_state_dict
+from precision_class import class_error, class_gate, distances, oracle_grads, train_case
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -363,19 +364,33 @@ def _bf16_step_vs_oracle(n, n_layer=8, seed=81, fused=None, monkeypatch=None):
         monkeypatch.setenv("SCLDM_TRAIN_FUSED", "1" if fused else "0")
     m, sd, cfg = build(vocab, "joint", n_layer, seed)
     m.precision = "bf16"
-    gen = torch.Generator().manual_seed(9)
-    x1, x0 = torch.randn(n, 16, 16, generator=gen), torch.randn(n, 16, 16, generator=gen)
-    t = torch.rand(n, generator=gen)
-    cond = {k: torch.randint(0, v + 1, (n,), generator=gen) for k, v in vocab.items()}
+    x1, x0, t, cond = train_case(n, 9, vocab)
     terms = hip_training_step(m, x1, x0, t, cond)
-    loss, pred, grads, _ = training_grads(sd, cfg, x1, x0, t, cond)
-    err = {"pred": max_abs_rel(terms["pred"].detach().cpu(), pred)}
+    return _step_errors(m, terms, sd, cfg, x1, x0, t, cond, tag=f"train/{n}/{n_layer}/{seed}")
+
+
+def _step_errors(m, terms, sd, cfg, x1, x0, t, cond, tag=None, threads=16):
+    """(flat, got, cls) of a bf16 training step against autograd over the oracle: `flat` is what the flat 3e-2 is asserted on (pred:
+    scale-relative max error, every gradient: rel-L2); `got` / `cls` are the rel-L2 of the kernels and of autograd over the oracle
+    under matmul_operand_bits(7) (forward and both backward products of every matmul rounded, exactly as the fp16 test does with
+    10), per tensor, against the same exact result - the two sides of precision_class.class_gate."""
+    fn = lambda: oracle_grads(sd, cfg, x1, x0, t, cond)
+    n_thr = torch.get_num_threads()
+    torch.set_num_threads(min(threads, n_thr))
+    try:
+        exact = fn()
+    finally:
+        torch.set_num_threads(n_thr)
+    ours = {"pred": terms["pred"].detach().cpu()}
     for name, p in m.named_parameters():
-        if name in FROZEN:
-            continue
-        ref = grads[name].double()
-        err[name] = float((p.grad.cpu().double() - ref).norm() / ref.norm())
-    return err
+        if name not in FROZEN:
+            assert torch.isfinite(p.grad).all(), name
+            ours[name] = p.grad.cpu()
+    got = distances(ours, exact)
+    assert set(got) == set(exact)
+    flat = dict(got, pred=max_abs_rel(ours["pred"], exact["pred"]))
+    cls = class_error(fn, 7, exact, per="tensor", tag=tag)
+    return flat, got, cls
 
 
 @pytest.mark.parametrize("n,fused", [(48, True), (48, False), (50, True), (4, True), (5, True), (1, True), (324, True)])
@@ -385,9 +400,10 @@ def test_bf16_training_gradients_close_to_fp32_oracle(n, fused, monkeypatch):
     wgrad, train_fused.hip) - ragged batches (50, 5, 1 cells) with the last 64-token tile padded by repeats of the last cell
     whose gradient is zero; SCLDM_TRAIN_FUSED=0 keeps the generic GEMM path.  Up to 320 cells both fused kernels run on 32-token
     tiles, at 324 cells the recording forward still does and the backward layer is on 64-token tiles again (one record layout)."""
-    err = _bf16_step_vs_oracle(n, fused=fused, monkeypatch=monkeypatch)
-    bad = {k: v for k, v in err.items() if not v < 3e-2}
+    flat, got, cls = _bf16_step_vs_oracle(n, fused=fused, monkeypatch=monkeypatch)
+    bad = {k: v for k, v in flat.items() if not v < 3e-2}
     assert not bad, bad
+    class_gate(got, cls, f"bf16 training step, {n} cells x 8 layers, {'fused' if fused else 'generic'} route vs oracle autograd")
 
 
 @pytest.mark.parametrize("n,n_layer", [(48, 8), (50, 8), (5, 8), (130, 2)])
@@ -536,15 +552,19 @@ def test_fused_training_input_gradient_matches_oracle(n, monkeypatch):
     xg = x.cuda().requires_grad_(True)
     (m(xg, t.cuda(), {"clusters": lab.cuda()}, force_drop_ids=False) * wgt.cuda()).sum().backward()
     from oracle.dit import dit_forward
-    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    xo = x.clone().requires_grad_(True)
-    (dit_forward(p, cfg, xo, t, {"clusters": lab}) * wgt).sum().backward()
-    assert float((xg.grad.cpu().double() - xo.grad.double()).norm() / xo.grad.double().norm()) < 3e-2
-    gp, rp = m.pos_embed.grad.cpu().double(), p["pos_embed"].grad.double()
-    assert float((gp - rp).norm() / rp.norm()) < 3e-2
-    for name in ("input_proj.weight", "input_proj.bias", "final_layer.linear.weight", "final_layer.linear.bias"):
-        ours, ref = dict(m.named_parameters())[name].grad.cpu().double(), p[name].grad.double()
-        assert float((ours - ref).norm() / ref.norm()) < 3e-2, name
+    names = ("pos_embed", "input_proj.weight", "input_proj.bias", "final_layer.linear.weight", "final_layer.linear.bias")
+
+    def oracle():
+        p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+        xo = x.clone().requires_grad_(True)
+        (dit_forward(p, cfg, xo, t, {"clusters": lab}) * wgt).sum().backward()
+        return {"x": xo.grad, **{k: p[k].grad for k in names}}
+    exact = oracle()
+    got = distances({"x": xg.grad.cpu(), **{k: dict(m.named_parameters())[k].grad.cpu() for k in names}}, exact)
+    assert set(got) == set(exact)
+    for name, e in got.items():
+        assert e < 3e-2, (name, e)
+    class_gate(got, class_error(oracle, 7, exact, per="tensor"), f"fused training input / pos_embed / end-layer gradients, {n} cells")
 
 
 @pytest.mark.parametrize("n_embed,n_head,n_layer,n", [(512, 8, 2, 9), (512, 16, 2, 5), (1024, 16, 2, 6)])   # head_dim 64 / 32 / 64 (DiT-L width)
@@ -600,6 +620,8 @@ def test_wider_shapes_bf16_sources_close_to_fp32_oracle(n_embed, n_head, n_layer
         got[src16] = {k: p.grad.detach().cpu().double() for k, p in m.named_parameters() if p.grad is not None}
         got[src16]["pred"] = terms["pred"].detach().cpu().double()
     loss, pred, grads, _ = training_grads(sd, cfg, x1, x0, t, cond)
+    exact = {"pred": pred, **grads}
+    cls = class_error(lambda: oracle_grads(sd, cfg, x1, x0, t, cond), 7, exact, per="tensor", tag=f"wider/{n_embed}/{n_head}/{n_layer}/{n}")
     bad = {}
     for name, g in got[True].items():
         ref = pred.double() if name == "pred" else grads[name].double()
@@ -613,6 +635,9 @@ def test_wider_shapes_bf16_sources_close_to_fp32_oracle(n_embed, n_head, n_layer
           f"worst vs fp32-array route {max(float((got[True][k] - got[False][k]).norm() / got[False][k].norm()) for k in got[True]):.2e}")
     assert not bad, bad
     assert any(not torch.equal(got[True][k], got[False][k]) for k in got[True])   # the switch selects a different code path
+    for src16 in (True, False):
+        class_gate(distances(got[src16], exact), cls, f"generic bf16 training, n_embed {n_embed}, {n} cells, "
+                   f"{'bf16' if src16 else 'fp32'} operand arrays, tiles x{big}")
 
 
 def test_wider_shape_inference_cfg_and_sampler_match_oracle():
@@ -699,15 +724,17 @@ def test_fused_training_other_latent_widths(din, monkeypatch):
     wgt = torch.randn(n, 16, din, generator=gen)
     (m(x.cuda(), t.cuda(), {"clusters": lab.cuda()}, force_drop_ids=False) * wgt.cuda()).sum().backward()
     from oracle.dit import dit_forward
-    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    (dit_forward(p, cfg, x, t, {"clusters": lab}) * wgt).sum().backward()
-    bad = {}
-    for name, q in m.named_parameters():
-        ref = p[name].grad.double()
-        e = float((q.grad.cpu().double() - ref).norm() / ref.norm())
-        if not e < 3e-2:
-            bad[name] = e
+
+    def oracle():
+        p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+        (dit_forward(p, cfg, x, t, {"clusters": lab}) * wgt).sum().backward()
+        return {k: v.grad for k, v in p.items()}
+    exact = oracle()
+    got = distances({name: q.grad.cpu() for name, q in m.named_parameters()}, exact)
+    assert set(got) == {name for name, _ in m.named_parameters()}
+    bad = {k: e for k, e in got.items() if not e < 3e-2}
     assert not bad, bad
+    class_gate(got, class_error(oracle, 7, exact, per="tensor"), f"fused training, latent width {din}, {n} cells")
 
 
 def test_fused_training_buffers_are_the_small_ones():
@@ -777,19 +804,13 @@ def test_full_depth_bf16_training_gradients_close_to_fp32_oracle(n_embed, n_head
     t = torch.rand(n, generator=gen)
     cond = {k: torch.randint(0, v + 1, (n,), generator=gen) for k, v in vocab.items()}
     terms = hip_training_step(m, x1, x0, t, cond)
-    loss, pred, grads, _ = training_grads(sd, cfg, x1, x0, t, cond)
-    e_pred = float((terms["pred"].detach().cpu().double() - pred.double()).norm() / pred.double().norm())
-    bad, worst = {}, 0.0
-    for name, p in m.named_parameters():
-        if name in FROZEN:
-            continue
-        ref = grads[name].double()
-        e = float((p.grad.cpu().double() - ref).norm() / ref.norm())
-        worst = max(worst, e)
-        if not e < 3e-2:
-            bad[name] = e
+    _, got, cls = _step_errors(m, terms, sd, cfg, x1, x0, t, cond)
+    e_pred = got["pred"]
+    worst = max(v for k, v in got.items() if k != "pred")
+    bad = {k: v for k, v in got.items() if k != "pred" and not v < 3e-2}
     print(f"[parity] 24-layer bf16 training, n_embed {n_embed}, {n} cells: pred rel-L2 {e_pred:.2e}, worst gradient rel-L2 {worst:.2e}")
     assert e_pred < 3e-2 and not bad, (e_pred, bad)
+    class_gate(got, cls, f"24-layer bf16 training, n_embed {n_embed}, {n} cells vs oracle autograd")
 
 
 def test_full_depth_dit_l_gradients_at_the_batch_the_bench_kernels_run(monkeypatch):
@@ -803,7 +824,7 @@ def test_full_depth_dit_l_gradients_at_the_batch_the_bench_kernels_run(monkeypat
     import os
     vocab = {"cell_line": 4, "gene": 2024}
     n, n_embed, n_head = 130, 1024, 16
-    out = {}
+    out, classes = {}, {}
     legs = [("rescaled", (256.0 / n_embed) ** 0.5)] + ([("as drawn", 1.0)] if os.environ.get("SCLDM_TEST_UNRESCALED") == "1" else [])
     for tag, sc in legs:
         m, sd, cfg = build(vocab, "joint", 24, 95, n_embed=n_embed, n_head=n_head)
@@ -816,26 +837,17 @@ def test_full_depth_dit_l_gradients_at_the_batch_the_bench_kernels_run(monkeypat
         t = torch.rand(n, generator=gen)
         cond = {k: torch.randint(0, v + 1, (n,), generator=gen) for k, v in vocab.items()}
         terms = hip_training_step(m, x1, x0, t, cond)
-        n_thr = torch.get_num_threads()
-        torch.set_num_threads(min(32, n_thr))
-        try:
-            loss, pred, grads, _ = training_grads(sd, cfg, x1, x0, t, cond)
-        finally:
-            torch.set_num_threads(n_thr)
-        e_pred = float((terms["pred"].detach().cpu().double() - pred.double()).norm() / pred.double().norm())
-        errs = {}
-        for name, p in m.named_parameters():
-            if name in FROZEN:
-                continue
-            assert torch.isfinite(p.grad).all(), name
-            ref = grads[name].double()
-            errs[name] = float((p.grad.cpu().double() - ref).norm() / ref.norm())
+        _, got, cls = _step_errors(m, terms, sd, cfg, x1, x0, t, cond, threads=32)     # (the exact chain; the 7-bit one runs on 16)
+        e_pred = got["pred"]
+        errs = {k: v for k, v in got.items() if k != "pred"}
         out[tag] = (e_pred, max(errs.values()), max(errs, key=errs.get))
+        classes[tag] = (got, cls)
         del m
         torch.cuda.empty_cache()
     for tag, (ep, eg, worst) in out.items():
         print(f"[parity] 24-layer DiT-L bf16 training at {n} cells, fixture {tag}: pred rel-L2 {ep:.2e}, worst gradient rel-L2 {eg:.2e} ({worst})")
     assert out["rescaled"][0] < 3e-2 and out["rescaled"][1] < 3e-2, out
+    class_gate(*classes["rescaled"], f"24-layer DiT-L bf16 training at {n} cells vs oracle autograd")
 
 
 def test_batched_weight_gradients_of_a_dit_l_layer(monkeypatch):
@@ -868,6 +880,9 @@ def test_batched_weight_gradients_of_a_dit_l_layer(monkeypatch):
         if not (e < 3e-2 and e2 < 1e-3):
             bad[name] = (e, e2)
     assert not bad, bad
+    cls = class_error(lambda: oracle_grads(sd, cfg, x1, x0, t, cond), 7, grads, per="tensor")
+    for batch in (True, False):
+        class_gate(distances(got[batch], grads), cls, f"DiT-L layer weight gradients, {n} cells, {'batched' if batch else 'split-K'} route")
     main = [k for k in got[True] if k.endswith(("attn.c_attn.weight", "attn.c_proj.weight", "mlp.w1.weight", "mlp.w2.weight", "mlp.c_proj.weight"))]
     assert any(not torch.equal(got[True][k], got[False][k]) for k in main)       # the switch selects a different code path
 

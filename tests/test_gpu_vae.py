@@ -7,6 +7,7 @@ import torch
 from conftest import check_err, golden_json, load_golden, max_abs_rel
 from oracle.vae import VAEConfig, decode, encode
 from oracle.weights import make_state_dict
+from precision_class import class_error, class_gate, rel_l2
 from test_abi_cpu import _build_vae
 
 pytestmark = pytest.mark.gpu
@@ -257,6 +258,9 @@ def test_bf16_decode_close_to_fp32():
     assert float(((nb.mu - ref.mu).norm() / ref.mu.norm())) < 1e-2
     assert torch.allclose(nb.mu.sum(1, keepdim=True), lib.view(-1, 1), rtol=1e-4)
     assert max_abs_rel(nb.mu.cpu(), g["mu"]) < 3e-2
+    t = torch.from_numpy
+    cls = class_error(lambda: decode(sd, cfg, t(g["z"]), t(g["genes"]), t(g["library_size"]))[0], 7, g["mu"], tag="vae_2000/decode")
+    class_gate(rel_l2(nb.mu, g["mu"]), cls["rel_l2"], "vae_2000 decode mu vs reference golden")
 
 
 def test_bf16_encode_close_to_fp32():
@@ -266,6 +270,9 @@ def test_bf16_encode_close_to_fp32():
     vae.precision = "bf16"
     z = vae.encode(cu(g["counts"]), cu(g["genes"]), counts, genes)
     assert max_abs_rel(z.cpu(), ref.cpu()) < 3e-2 and max_abs_rel(z.cpu(), g["z"]) < 3e-2
+    t = torch.from_numpy
+    cls = class_error(lambda: encode(sd, cfg, t(g["counts_subset"]), t(g["genes_subset"])), 7, g["z"], tag="vae_2000/encode")
+    class_gate(rel_l2(z, g["z"]), cls["rel_l2"], "vae_2000 encode vs reference golden")
 
 
 def _fresh_vae(G, seed):
@@ -487,6 +494,11 @@ def test_unshared_theta_head_draw_and_training_guard():
         vae.precision = prec
         nbp = vae.decode(z, genes, lib)
         assert max_abs_rel(nbp.theta.cpu(), g["theta"]) < tol and max_abs_rel(nbp.mu.cpu(), g["mu"]) < tol
+        if prec == "bf16":
+            t = torch.from_numpy
+            cls = class_error(lambda: dict(zip(("mu", "theta"), decode(sd, cfg, t(g["z"]), t(g["genes"]), t(g["library_size"])))), 7,
+                              {"mu": g["mu"], "theta": g["theta"]}, per="tensor")
+            class_gate({"mu": rel_l2(nbp.mu, g["mu"]), "theta": rel_l2(nbp.theta, g["theta"])}, cls, "vae_unshared decode vs reference golden")
     vae.precision = "fp32"
     c1 = vae.decode_sample(z, genes, lib, seed=11)
     assert torch.equal(c1, vae.decode_sample(z, genes, lib, seed=11)) and (c1 >= 0).all()
