@@ -518,7 +518,8 @@ int scldm_nb_sample(const float* mu, const float* theta, float* out, size_t n, u
  *             parameter for EVERY tensor named in `g` (same struct and layouts as scldm_vae_weights, pointers writable; overwritten,
  *             not accumulated; enc_pos_embed is ignored: frozen in the reference, nnets.py:103-106).  Parameters are read LIVE from
  *             `w`.  The two embedding tables' gradients (gene_embedding, theta) are scatter-added with float atomics (like torch's
- *             embedding backward); every other gradient is a deterministic two-stage sum.
+ *             embedding backward); every other gradient is a deterministic two-stage sum.  scldm_vae_train_backward_ordered below
+ *             forms the two tables by a fixed-order sum instead: every gradient is then bit-equal run to run.
  * mu / theta / z passed to the backward are the forward's outputs.  Buffers: scldm_vae_train_saved_bytes / _workspace_bytes. */
 size_t scldm_vae_train_saved_bytes(const scldm_vae* h, int B);
 size_t scldm_vae_train_workspace_bytes(const scldm_vae* h, int B, int S, int G);
@@ -545,6 +546,34 @@ int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const 
                                 const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
                                 const float* dz, void* saved, void* ws, int precision, void* stream);
 int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf /* device, caller-owned, may be NULL */);
+
+/* ORDERED table gradients: scldm_vae_train_backward_ex with the gradients of gene_embedding and theta formed without float atomics.
+ * Replaces torch's embedding backward under the autograd of TransformerVAE.forward (src/scldm/vae.py:29-56; the gene-embedding lookups
+ * of layers.py:111-118 and the theta lookup of stochastic_layers.py:108-110) when the trainer asks for `deterministic:`
+ * (experiments/configs/training/default.yaml:14).  The kernels store every slot's contribution in `rows` (device,
+ * scldm_vae_train_rows_bytes; written completely by each call, needs no initialisation) and a reduction adds, for each table row, the
+ * entries the caller's index lists for it, in the listed order.
+ *   entries: decoder slot (cell, slot) is entry cell * G + slot; encoder token (cell, tok) is entry B * G + cell * S + tok.
+ *   order  : device, n_entries entry indices grouped by table row (the row of a decoder entry is genes[cell][slot], of an encoder entry
+ *            genes_subset[cell][tok]).  The order inside a row IS the summation order; any fixed order is legal (scldm_amd.vae.table_order
+ *            lists ascending entry indices).  Entries may be omitted - their contribution is then dropped: omit only encoder tokens with
+ *            a zero count, whose contribution is exactly zero (the atomic path skips them too).
+ *   seg    : device, n_genes + 2 offsets into `order`: table row r owns order[seg[r] .. seg[r + 1]); a row with an empty segment
+ *            receives exact zeros.
+ *   theta  : uses the same index - its reduction walks the same segments and takes the decoder entries (those below B * G) only; no
+ *            second pair of arrays.
+ * Guarantee: the same inputs give bit-equal gradients for EVERY tensor run to run, on one build and one GPU model.  No equality
+ * across SCLDM_VAE_GENE_WGS / SCLDM_VAE_POOL_WGS settings (they change other partial sums too), and none with the atomic mode beyond
+ * rounding (same addends, another order); every gradient but the two tables is bit-equal between the modes.  SCLDM_PREC_FP32 and
+ * SCLDM_PREC_FP16, the found-inf flag and the two-stream overlap are those of scldm_vae_train_backward_ex; the reduction runs after
+ * both producers of `rows`.  NULL order (with n_entries > 0) / seg / rows, or n_entries outside [0, B * G + B * S]: SCLDM_ERR_SHAPE.
+ * Entries outside [0, B * G + B * S) are skipped by the reduction, never dereferenced. */
+size_t scldm_vae_train_rows_bytes(const scldm_vae* h, int B, int S, int G);
+int scldm_vae_train_backward_ordered(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                     const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
+                                     const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
+                                     const float* dz, void* saved, void* ws, int precision, const int32_t* order, const int32_t* seg,
+                                     int n_entries, void* rows, void* stream);
 
 /* log_nb_positive (src/scldm/distributions.py:6-42) elementwise over n values, and its gradient w.r.t. mu and theta given the
  * upstream gradient of the log-likelihood (either output may be NULL):

@@ -9,7 +9,11 @@
 // decoder chain, the two 16-token cell sides, the encoder pooling) are in vae_train_wide.hpp.
 // Sums over TOKENS (weight gradients, the per-cell dK / dV of the decoder's cross attention, the encoder's dQ) are written as ONE
 // partial per workgroup, and a final pass adds the partials in index order (deterministic).  Only the two embedding-table
-// gradients (gene_embedding, theta: scatter by gene id) use float atomics, like torch's own embedding backward.
+// gradients (gene_embedding, theta: scatter by gene id) use float atomics by default, like torch's own embedding backward.  The
+// ORDERED mode (scldm_vae_train_backward_ordered) replaces them: the ROWS instantiations store each slot's contribution at the
+// slot's entry index and table_rows_reduce_kernel adds the entries of a table row in the order of the caller's index.  It guarantees
+// run-to-run bit equality of every gradient on one build and one GPU model - not equality across SCLDM_VAE_GENE_WGS / _POOL_WGS
+// settings, which change other partial sums too.
 // Forward activations are recomputed from the saved inputs (per-gene chains) or from one saved (16, 32) state per trunk layer.
 #pragma once
 #include "common.hpp"
@@ -185,7 +189,10 @@ __global__ __launch_bounds__(64) void enc_q_bwd_kernel(const float* __restrict__
 // fp16's subnormal range (gradient error 1.7 x the TF32-operand oracle's on vae_train_small); [1024, 2048) keeps them normal and
 // leaves 32 x headroom for d y = dl w_head + ... (|w_head| < 1).  An overflow still sets the found-inf flag.
 constexpr int kDlScaleLog2 = 10;
-template <bool SCALE>
+// ROWS (ordered table gradients): `g_theta` is the (B, G) row buffer instead of the table - dtheta theta goes to g_theta[cell * G + slot]
+// (0 where dtheta is NULL; every slot is written, the buffer needs no memset), `genes` is not read, and table_rows_reduce_kernel adds
+// the slots of a table row in a fixed order.
+template <bool SCALE, bool ROWS = false>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ theta, const float* __restrict__ dmu,
                                                        const float* __restrict__ dtheta, const float* __restrict__ lib,
                                                        const int64_t* __restrict__ genes, int G, float inv_temp, float* __restrict__ dl,
@@ -207,7 +214,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     dl[base + g] = d;
     b += d;
     if constexpr (SCALE) m = fmaxf(m, fabsf(d));
-    if (dtheta) {
+    if constexpr (ROWS) {
+      g_theta[base + g] = dtheta ? dtheta[base + g] * theta[base + g] : 0.f;
+    } else if (dtheta) {
       const float dt = dtheta[base + g] * theta[base + g];
       if (dt != 0.f) atomicAdd(g_theta + genes[base + g], dt);
     }
@@ -251,7 +260,7 @@ struct DecBwdArgs {
   const float* kv;         // (B, 16, 64): K | V of the cell's latent tokens
   const float *ln1q_w, *ln1q_b, *wq, *wp, *ln2_w, *ln2_b, *head_w;
   MlpW mlp;
-  float* g_emb;            // (n_genes + 1, 32), atomically accumulated
+  float* g_emb;            // (n_genes + 1, 32), atomically accumulated; ROWS instantiations: the (B * G, 32) row buffer of the ordered mode
   float* part;             // (B * chunks, DP_SIZE)
   float* dkv_part;         // (B * chunks, 16, 64)
   int G, tiles;
@@ -345,7 +354,7 @@ struct EncPoolBwdArgs {
   const float* lse2;       // (B, 4, 16): log2-domain log-sum-exp of the scaled scores
   const float* dao;        // (B, 16, 32)
   const float* dgq;        // (B, 4, 16)
-  float* g_emb;
+  float* g_emb;            // enc_pool_bwd_rows_kernel: the (B * S, 32) row buffer of the ordered mode
   float* part;             // (B * chunks, EP_SIZE)
   int S, tiles;
   float eps;
@@ -383,6 +392,60 @@ __global__ __launch_bounds__(64) void fold_dq_kernel(const float* __restrict__ p
   if (idx >= 16 * 32) return;
   const int i = idx >> 5, d = idx & 31, h = d >> 3;
   dQ[idx] = sum_partials(part + EP_DQ + (h * 16 + i) * 32 + d, n_part, stride);
+}
+
+// =================================================================================================================================
+// Ordered table gradients (scldm_vae_train_backward_ordered): g[r][f] = sum over order[seg[r] .. seg[r + 1]) of rows[entry][f], in the
+// order the caller's index lists the entries - no float atomics, so the two embedding tables are bit-reproducible run to run like every
+// other gradient.  256 threads = 8 interleaved running sums (sum u takes the entries u, u + 8, ... of the segment, four loads in
+// flight, added in index order) x 32 columns, combined in the fixed tree of sum_partials.  A table row with an empty segment is
+// written as exact zeros: the tables need no memset.
+//   F = 32 (table_rows_reduce_kernel, gene_embedding): one workgroup per table row, column = feature; rows = the decoder slots' and
+//           the encoder tokens' 32-float contributions (entry = cell * G + slot, or B * G + cell * S + token).
+//   F = 1  (table_scalars_reduce_kernel, theta): one workgroup per 32 table rows, column = table row; rows = one float per decoder
+//           slot, and only the entries below `n_valid` = B * G (the decoder slots of the same index) are taken.
+// Entries outside [0, n_valid) and offsets outside [0, n_order] are skipped / clamped, never dereferenced.
+// (Two plain kernels over one body, not two instantiations of a template kernel: with the template, head_bwd_kernel<false> of the default
+// mode compiled to one instruction more - tools/kernel_isa_digest.py.)
+// =================================================================================================================================
+template <int F>
+__device__ __forceinline__ void table_rows_reduce(float (&part)[8][33], const float* __restrict__ rows, const int32_t* __restrict__ order,
+                                                  const int32_t* __restrict__ seg, int n_table, int n_order, int n_valid,
+                                                  float* __restrict__ dst) {
+  const int u = threadIdx.x >> 5, c = threadIdx.x & 31;
+  const int r = F == 32 ? (int)blockIdx.x : (int)blockIdx.x * 32 + c;
+  const int f = F == 32 ? c : 0;
+  float s = 0.f;
+  if (r < n_table) {
+    const int beg = min(max(seg[r], 0), n_order), end = min(max(seg[r + 1], beg), n_order);
+    auto val = [&](int i) {
+      const int e = i < end ? order[i] : -1;
+      return (unsigned)e < (unsigned)n_valid ? rows[(size_t)e * F + f] : 0.f;
+    };
+    for (int i = beg + u; i < end; i += 32) {
+      const float v0 = val(i), v1 = val(i + 8), v2 = val(i + 16), v3 = val(i + 24);
+      s += v0;
+      s += v1;
+      s += v2;
+      s += v3;
+    }
+  }
+  part[u][c] = s;
+  __syncthreads();
+  if (u == 0 && r < n_table)
+    dst[(size_t)r * F + f] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) + ((part[4][c] + part[5][c]) + (part[6][c] + part[7][c]));
+}
+__global__ __launch_bounds__(256) void table_rows_reduce_kernel(const float* __restrict__ rows, const int32_t* __restrict__ order,
+                                                                const int32_t* __restrict__ seg, int n_table, int n_order, int n_valid,
+                                                                float* __restrict__ dst) {
+  __shared__ float part[8][33];
+  table_rows_reduce<32>(part, rows, order, seg, n_table, n_order, n_valid, dst);
+}
+__global__ __launch_bounds__(256) void table_scalars_reduce_kernel(const float* __restrict__ rows, const int32_t* __restrict__ order,
+                                                                   const int32_t* __restrict__ seg, int n_table, int n_order, int n_valid,
+                                                                   float* __restrict__ dst) {
+  __shared__ float part[8][33];
+  table_rows_reduce<1>(part, rows, order, seg, n_table, n_order, n_valid, dst);
 }
 
 // =================================================================================================================================

@@ -99,6 +99,18 @@ int check_train(const scldm_vae* h, const scldm_vae_weights* w, int B, int S, in
   return SCLDM_OK;
 }
 
+// row buffers of the ordered table gradients: the decoder slots' then the encoder tokens' 32-float gene-embedding contributions
+// (contiguous: entry e of the caller's index is row e), then one theta contribution per decoder slot
+struct Rows { float *emb, *theta; size_t bytes; };
+Rows carve_rows(int B, int S, int G, void* base) {
+  Carver c{reinterpret_cast<char*>(base)};
+  Rows r;
+  r.emb = c.take(((size_t)B * G + (size_t)B * S) * 32);
+  r.theta = c.take((size_t)B * G);
+  r.bytes = c.off;
+  return r;
+}
+
 MlpW mlp_of(const float* w1, const float* w2, const float* wct, int H) { return MlpW{w1, w2, wct, H}; }
 
 BlockWArr blocks_of(const scldm_vae_block* b, int L, const float* wct0, int H) {
@@ -198,10 +210,12 @@ extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset,
                                     SCLDM_PREC_FP32, stream_);
 }
 
-extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
-                                           const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
-                                           const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
-                                           const float* dz, void* saved_, void* ws_, int precision, void* stream_) {
+namespace {
+// the backward of both table-gradient modes: atomic (rows_ == nullptr; scldm_vae_train_backward_ex) or ordered
+int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                        const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G, const float* mu,
+                        const float* theta, const float* z, const float* dmu, const float* dtheta, const float* dz, void* saved_, void* ws_,
+                        int precision, const int32_t* order, const int32_t* seg, int n_entries, void* rows_, void* stream_) {
   int rc = check_train_precision(precision);
   if (rc) return rc;
   rc = check_train(h, w, B, S, G);
@@ -218,8 +232,12 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   Ws k = carve_ws(h, B, S, G, ws_);
   float* g_emb = const_cast<float*>(g->gene_embedding);
   float* g_theta = const_cast<float*>(g->theta);
-  HIP_TRY(hipMemsetAsync(g_emb, 0, (size_t)(c.n_genes + 1) * 32 * 4, st));
-  HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
+  const bool ordered = rows_ != nullptr;
+  const Rows rw = carve_rows(B, S, G, rows_);
+  if (!ordered) {   // (the ordered reduction writes every table row, the untouched ones as zeros)
+    HIP_TRY(hipMemsetAsync(g_emb, 0, (size_t)(c.n_genes + 1) * 32 * 4, st));
+    HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
+  }
   if (f16 && h->found_inf) HIP_TRY(hipMemsetAsync(h->found_inf, 0, sizeof(float), st));
 
   // ---- transposed c_proj copies (the streaming SwiGLU reads columns of c_proj as rows): enc cross, dec cross, enc layers, dec layers
@@ -253,6 +271,9 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
       HIP_TRY(hipFuncSetAttribute((const void*)wide::enc_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::PB_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::enc_pool_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::PB_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
     }
   }
@@ -291,7 +312,10 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   LAUNCH_CHECK();
   if (overlap) HIP_TRY(hipEventRecord(h->ev_join, s2));
   // ---- NB head, then the per-gene decoder chain
-  if (f16) head_bwd_kernel<true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, k.dl_scale);
+  if (ordered) {
+    if (f16) head_bwd_kernel<true, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, k.dl_scale);
+    else head_bwd_kernel<false, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, nullptr);
+  } else if (f16) head_bwd_kernel<true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, k.dl_scale);
   else head_bwd_kernel<false><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, nullptr);
   LAUNCH_CHECK();
   DecBwdArgs ga{};
@@ -299,12 +323,14 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   ga.ln1q_w = w->dec_cross.ln1q_w; ga.ln1q_b = w->dec_cross.ln1q_b; ga.wq = w->dec_cross.attn_q; ga.wp = w->dec_cross.attn_proj;
   ga.ln2_w = w->dec_cross.ln2_w; ga.ln2_b = w->dec_cross.ln2_b; ga.head_w = w->head_w;
   ga.mlp = mlp_of(w->dec_cross.w1, w->dec_cross.w2, wct(1), H);
-  ga.g_emb = g_emb; ga.part = k.p_gene; ga.dkv_part = k.p_dkv; ga.G = G; ga.tiles = k.tilesD; ga.eps = eps;
+  ga.g_emb = ordered ? rw.emb : g_emb; ga.part = k.p_gene; ga.dkv_part = k.p_dkv; ga.G = G; ga.tiles = k.tilesD; ga.eps = eps;
   if (f16) {
     ga.dl_scale = k.dl_scale;
     ga.found_inf = h->found_inf;
-    wide::dec_gene_bwd_mfma2_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
-  } else wide::dec_gene_bwd_mfma2_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+    if (ordered) wide::dec_gene_bwd_mfma2_kernel<true, true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+    else wide::dec_gene_bwd_mfma2_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+  } else if (ordered) wide::dec_gene_bwd_mfma2_kernel<false, true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
+  else wide::dec_gene_bwd_mfma2_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
   LAUNCH_CHECK();
   if (overlap) {
     HIP_TRY(hipEventRecord(h->ev_gene, st));
@@ -317,9 +343,18 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
   EncPoolBwdArgs pa{};
   pa.counts = counts_subset; pa.genes = genes_subset; pa.emb = w->gene_embedding;
   pa.ln1_w = w->enc_cross.ln1_w; pa.ln1_b = w->enc_cross.ln1_b; pa.wkv = w->enc_cross.attn_kv; pa.Q = k.Q; pa.lse2 = sv.lse2;
-  pa.dao = k.dao; pa.dgq = k.dgq; pa.g_emb = g_emb; pa.part = k.p_pool; pa.S = S; pa.tiles = k.tilesE; pa.eps = eps;
-  wide::enc_pool_bwd_kernel<<<dim3(k.chunksE, B), wide::kThreads, wide::PB_BYTES, st>>>(pa);
+  pa.dao = k.dao; pa.dgq = k.dgq; pa.g_emb = ordered ? rw.emb + (size_t)B * G * 32 : g_emb; pa.part = k.p_pool; pa.S = S; pa.tiles = k.tilesE; pa.eps = eps;
+  if (ordered) wide::enc_pool_bwd_rows_kernel<<<dim3(k.chunksE, B), wide::kThreads, wide::PB_BYTES, st>>>(pa);
+  else wide::enc_pool_bwd_kernel<<<dim3(k.chunksE, B), wide::kThreads, wide::PB_BYTES, st>>>(pa);
   LAUNCH_CHECK();
+  if (ordered) {
+    // both producers of the row buffers (head + per-gene kernel, pooling) ran on `st`: the two table sums follow them in stream order.
+    // The theta table walks the same segments and takes the decoder entries (those below B * G) only.
+    const int n_table = c.n_genes + 1, n_dec = B * G;
+    table_rows_reduce_kernel<<<n_table, 256, 0, st>>>(rw.emb, order, seg, n_table, n_entries, n_dec + B * S, g_emb);
+    table_scalars_reduce_kernel<<<cdiv(n_table, 32), 256, 0, st>>>(rw.theta, order, seg, n_table, n_entries, n_dec, g_theta);
+    LAUNCH_CHECK();
+  }
 
   // ---- partial sums -> parameter gradients
   auto G_ = [](const float* p) { return const_cast<float*>(p); };
@@ -382,6 +417,35 @@ extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights
     LAUNCH_CHECK();
   }
   return SCLDM_OK;   // (join_side: `st` waits for the second stream)
+}
+}  // namespace
+
+extern "C" size_t scldm_vae_train_rows_bytes(const scldm_vae* h, int B, int S, int G) {
+  if (!h || B < 1 || S < 1 || G < 1) return 0;
+  return carve_rows(B, S, G, nullptr).bytes;
+}
+
+extern "C" int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                           const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G,
+                                           const float* mu, const float* theta, const float* z, const float* dmu, const float* dtheta,
+                                           const float* dz, void* saved_, void* ws_, int precision, void* stream_) {
+  return train_backward_impl(h, w, g, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, dmu, dtheta, dz, saved_, ws_,
+                             precision, nullptr, nullptr, 0, nullptr, stream_);
+}
+
+extern "C" int scldm_vae_train_backward_ordered(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g,
+                                                const float* counts_subset, const int64_t* genes_subset, int B, int S, const int64_t* genes,
+                                                const float* library_size, int G, const float* mu, const float* theta, const float* z,
+                                                const float* dmu, const float* dtheta, const float* dz, void* saved_, void* ws_, int precision,
+                                                const int32_t* order, const int32_t* seg, int n_entries, void* rows, void* stream_) {
+  if (!seg || !rows || (!order && n_entries != 0)) return fail(SCLDM_ERR_SHAPE, "scldm_vae_train_backward_ordered: null order / seg / rows");
+  if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1 (got %d, %d, %d)", B, S, G);
+  const long long n_max = (long long)B * G + (long long)B * S;
+  if (n_max > 0x7fffffffLL - 64) return fail(SCLDM_ERR_SHAPE, "B * (G + S) = %lld entries exceed the int32 entry index", n_max);
+  if (n_entries < 0 || n_entries > n_max)
+    return fail(SCLDM_ERR_SHAPE, "n_entries %d outside [0, B * G + B * S = %lld]", n_entries, n_max);
+  return train_backward_impl(h, w, g, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, dmu, dtheta, dz, saved_, ws_,
+                             precision, order, seg, n_entries, rows, stream_);
 }
 
 extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,

@@ -764,7 +764,8 @@ __global__ __launch_bounds__(kThreads) void enc_cell_bwd_kernel(const EncCellTra
 // Sums over tokens (d c_attn 64 x 32, dQ 64 x 8, LN_1's vectors) are contracted per wave over its four tokens into 41 registers
 // per lane that live across the whole token range; the four waves are added through LDS in wave order at the end (deterministic).
 // grid = (chunks, B); partial per workgroup: EP_* of vae_train.hpp (only the block-diagonal entries of EP_DQ are written - the only
-// ones fold_dq_kernel reads).  Gene-embedding gradient by atomics.
+// ones fold_dq_kernel reads).  Gene-embedding gradient by atomics, or (enc_pool_bwd_rows_kernel, the ordered mode) stored per token
+// at a.g_emb[(cell * S + token) * 32 + f] - zeros where the atomic path skips (log1p(count) == 0), so the buffer needs no memset.
 // =================================================================================================================================
 constexpr int kP64 = 68;                                   // floats per 64-wide row
 constexpr int PB_W = 0, PB_Q = PB_W + 64 * kP, PB_DAO = PB_Q + 16 * kP, PB_LSE = PB_DAO + 16 * kP, PB_DG = PB_LSE + 64, PB_WAVE = PB_DG + 64;
@@ -781,121 +782,17 @@ __device__ __forceinline__ float quad_sum(float v) {
 }
 __device__ __forceinline__ f32x4 quad_sum4(f32x4 v) { return f32x4{quad_sum(v[0]), quad_sum(v[1]), quad_sum(v[2]), quad_sum(v[3])}; }
 
+// The ordered variant is a second plain kernel over the same body text (vae_train_pool_bwd.inc), not a template flag, and it is defined
+// FIRST: the default mode's device code is to stay what it was, and tools/kernel_isa_digest.py showed it move otherwise - as a template
+// (another linkage) this kernel compiled to 1 561 instead of 1 831 instructions and enc_cell_bwd_kernel to 8 574 instead of 8 365; with
+// the variant defined after it, to 1 622.  In this order the default kernel's instructions are those of the tree before the variant.
+__global__ __launch_bounds__(kThreads) void enc_pool_bwd_rows_kernel(const EncPoolBwdArgs a) {
+  constexpr bool ROWS = true;
+#include "vae_train_pool_bwd.inc"
+}
 __global__ __launch_bounds__(kThreads) void enc_pool_bwd_kernel(const EncPoolBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float S[];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, tk = lane >> 4, j = lane & 15;
-  const int chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
-  constexpr float kS2 = 1.4426950408889634f * 0.35355339059327373f;   // log2(e) / sqrt(8)
-  constexpr float kScale = 0.35355339059327373f;
-  {
-    RowCopy<64> cw;
-    cw.load(a.wkv, 64, tid);
-    cw.store(S + PB_W, tid);
-    for (int idx = tid; idx < 512; idx += kThreads) {
-      S[PB_Q + (idx >> 5) * kP + (idx & 31)] = a.Q[idx];
-      S[PB_DAO + (idx >> 5) * kP + (idx & 31)] = a.dao[(size_t)cell * 512 + idx];
-    }
-    if (tid < 64) { S[PB_LSE + tid] = a.lse2[(size_t)cell * 64 + tid]; S[PB_DG + tid] = a.dgq[(size_t)cell * 64 + tid]; }
-  }
-  __syncthreads();
-  float* __restrict__ Wv = S + PB_WAVE + wave * PW_SIZE;
-  const float lw0 = a.ln1_w[j], lw1 = a.ln1_w[j + 16], lb0 = a.ln1_b[j], lb1 = a.ln1_b[j + 16];
-  const int begin = chunk * a.tiles * 64, end = min(a.S, begin + a.tiles * 64);
-  const int h = j >> 2, iq = j & 3;
-  f32x4 gw[8];          // d c_attn[o = (lane >> 3) + 8 m][4 (lane & 7) ..]
-  f32x4 gqa = z4(), gqb = z4();   // dQ[(head, query) = lane][d = 0 .. 7 of that head]
-  float gln = 0.f;      // lanes < 32: LN_1 weight gradient of feature lane; lanes >= 32: bias gradient of feature lane - 32
-#pragma unroll
-  for (int m = 0; m < 8; ++m) gw[m] = z4();
-  for (int s0 = begin + wave * 4; s0 < end; s0 += 16) {
-    const int s = s0 + tk;
-    const bool valid = s < end;
-    const size_t si = (size_t)cell * a.S + (valid ? s : end - 1);
-    const long long gene = a.genes[si];
-    const float lc = log1pf(a.counts[si]);
-    const float* e = a.emb + (size_t)gene * 32;
-    const Ln n = ln_own(e[j] * lc, e[j + 16] * lc, a.eps);
-    Wv[PW_XN + tk * kP + j] = fmaf(n.h0, lw0, lb0);
-    Wv[PW_XN + tk * kP + j + 16] = fmaf(n.h1, lw1, lb1);
-    tsync();
-    lin32<64>(S + PB_W, Wv + PW_XN + tk * kP, j, [&](int, int o, float v) { Wv[PW_KV + tk * kP64 + o] = v; });
-    tsync();
-    {
-      const f32x4 ka = *v4(Wv + PW_KV + tk * kP64 + 8 * h), kb = *v4(Wv + PW_KV + tk * kP64 + 8 * h + 4);
-      const f32x4 va = *v4(Wv + PW_KV + tk * kP64 + 32 + 8 * h), vb = *v4(Wv + PW_KV + tk * kP64 + 32 + 8 * h + 4);
-      f32x4 dka = z4(), dkb = z4(), dva = z4(), dvb = z4();
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = 4 * iq + q;
-        const f32x4 qa = *v4(S + PB_Q + i * kP + 8 * h), qb = *v4(S + PB_Q + i * kP + 8 * h + 4);
-        const f32x4 da = *v4(S + PB_DAO + i * kP + 8 * h), db = *v4(S + PB_DAO + i * kP + 8 * h + 4);
-        const float sc = dot4(qa, ka) + dot4(qb, kb), dp = dot4(da, va) + dot4(db, vb);
-        const float pp = valid ? __builtin_amdgcn_exp2f(sc * kS2 - S[PB_LSE + h * 16 + i]) : 0.f;
-        const float ds = pp * (dp - S[PB_DG + h * 16 + i]) * kScale;
-        Wv[PW_DSV + tk * kP64 + h * 16 + i] = ds;
-        dka = fma4(ds, qa, dka); dkb = fma4(ds, qb, dkb);
-        dva = fma4(pp, da, dva); dvb = fma4(pp, db, dvb);
-      }
-      dka = quad_sum4(dka); dkb = quad_sum4(dkb); dva = quad_sum4(dva); dvb = quad_sum4(dvb);
-      const f32x4 mine = iq == 0 ? dka : iq == 1 ? dkb : iq == 2 ? dva : dvb;
-      *v4(Wv + PW_DKV + tk * kP64 + (iq >> 1) * 32 + 8 * h + 4 * (iq & 1)) = mine;
-    }
-    tsync();
-    {
-      f32x4 acc = z4();
-      lin32_t_acc<64>(S + PB_W, Wv + PW_DKV + tk * kP64, j, acc);
-      acc = half_sum4(acc);
-      if (j < 8) *v4(Wv + PW_TX + tk * kP + 4 * j) = acc;
-    }
-    {   // token-axis contractions over this wave's four tokens
-      const int i4 = lane & 7, oo = lane >> 3, hq = lane >> 4;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const f32x4 xv = *v4(Wv + PW_XN + t * kP + 4 * i4);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) gw[m] = fma4(Wv[PW_DKV + t * kP64 + oo + 8 * m], xv, gw[m]);
-        const float ds = Wv[PW_DSV + t * kP64 + lane];
-        gqa = fma4(ds, *v4(Wv + PW_KV + t * kP64 + 8 * hq), gqa);
-        gqb = fma4(ds, *v4(Wv + PW_KV + t * kP64 + 8 * hq + 4), gqb);
-      }
-    }
-    tsync();
-    const float g0 = Wv[PW_TX + tk * kP + j], g1 = Wv[PW_TX + tk * kP + j + 16];
-    Wv[PW_T1 + tk * kP + j] = g0 * n.h0;
-    Wv[PW_T1 + tk * kP + j + 16] = g1 * n.h1;
-    float o0, o1;
-    ln_back(n, g0 * lw0, g1 * lw1, o0, o1);
-    if (valid && lc != 0.f) {
-      float* ge = a.g_emb + (size_t)gene * 32;
-      atomicAdd(ge + j, o0 * lc);
-      atomicAdd(ge + j + 16, o1 * lc);
-    }
-    tsync();
-    {
-      const float* src = (lane < 32 ? Wv + PW_T1 : Wv + PW_TX) + (lane & 31);
-      gln += (src[0] + src[kP]) + (src[2 * kP] + src[3 * kP]);
-    }
-    tsync();
-  }
-  // the four waves' sums -> one partial
-  __syncthreads();
-  {
-    float* R = S + wave * PB_ACC;
-    const int i4 = lane & 7, oo = lane >> 3;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) *v4(R + (oo + 8 * m) * 32 + 4 * i4) = gw[m];
-    *v4(R + 2048 + lane * 8) = gqa;
-    *v4(R + 2048 + lane * 8 + 4) = gqb;
-    R[2560 + lane] = gln;
-  }
-  __syncthreads();
-  float* P = a.part + (size_t)(cell * nch + chunk) * EP_SIZE;
-  for (int idx = tid; idx < PB_ACC; idx += kThreads) {
-    const float v = ((S[idx] + S[PB_ACC + idx]) + S[2 * PB_ACC + idx]) + S[3 * PB_ACC + idx];
-    if (idx < 2048) P[EP_WKV + idx] = v;
-    else if (idx < 2560) { const int e = idx - 2048, hi = e >> 3, dd = e & 7; P[EP_DQ + hi * 32 + 8 * (hi >> 4) + dd] = v; }
-    else P[EP_LN1W + idx - 2560] = v;
-  }
+  constexpr bool ROWS = false;
+#include "vae_train_pool_bwd.inc"
 }
 
 // =================================================================================================================================
@@ -966,7 +863,10 @@ __device__ __forceinline__ f16x4 h4(float a, float b, float c, float d) { return
 __device__ __forceinline__ f32x4 mfma16h(f16x4 x, f16x4 y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(x, y, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma32h(f16x8 x, f16x8 y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); }
 
-template <bool F16>
+// ROWS (the ordered mode): dE of a decoded gene is stored at a.g_emb[(cell * G + slot) * 32 + f] instead of
+// being added atomically to the table - zeros where the atomic path skips (dlogit == 0), so the buffer needs no memset; F16 rescales
+// and checks the stored values as it does the added ones.
+template <bool F16, bool ROWS = false>
 __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const DecBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int tid = threadIdx.x, tok = tid >> 4, j = tid & 15, chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
@@ -1344,7 +1244,23 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
       vs[0] = fmaf(t0, n1.h0, vs[0]); vs[1] = fmaf(t1, n1.h1, vs[1]); vs[2] += t0; vs[3] += t1;
       float o0, o1;
       ln_back(n1, t0 * l1w0, t1 * l1w1, o0, o1);
-      if (valid && dlog != 0.f) {
+      if constexpr (ROWS) {
+        if (valid) {
+          float v0 = 0.f, v1 = 0.f;
+          if (dlog != 0.f) {
+            v0 = d0 + o0;
+            v1 = d1 + o1;
+            if constexpr (F16) {
+              v0 *= 1.0f / dl_sc;
+              v1 *= 1.0f / dl_sc;
+              bad |= !(__builtin_isfinite(v0) && __builtin_isfinite(v1));
+            }
+          }
+          float* row = a.g_emb + ((size_t)cell * a.G + g0 + tok) * 32;
+          row[j] = v0;
+          row[j + 16] = v1;
+        }
+      } else if (valid && dlog != 0.f) {
         float* ge = a.g_emb + (size_t)gene * 32;
         float v0 = d0 + o0, v1 = d1 + o1;
         if constexpr (F16) {

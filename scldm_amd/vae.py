@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
@@ -11,6 +12,30 @@ from . import _lib
 from .layers import InputTransformerVAE, swiglu_hidden
 from .nnets import Decoder, Encoder, _require_cuda_f32, _stream_ptr
 from .stochastic_layers import NegativeBinomial, NegativeBinomialTransformerLayer
+
+
+def table_order(genes: torch.Tensor, genes_subset: torch.Tensor, counts_subset: torch.Tensor, n_rows: int):
+    """Index of the ordered table gradients (scldm_vae_train_backward_ordered, include/scldm_hip.h): `(order, seg)`, both int32 on
+    the inputs' device.  Entry cell * G + slot is decoder slot (cell, slot) of `genes` (B, G); entry B * G + cell * S + tok is encoder
+    token (cell, tok) of `genes_subset` (B, S).  `order` lists the entries sorted by table row (the gene id), ascending entry index
+    inside a row (a stable sort); `seg` holds n_rows + 1 offsets, table row r owning order[seg[r]:seg[r + 1]].  Encoder tokens with a
+    zero count are left out: their contribution is exactly zero and the atomic path skips them too.  Integer plumbing through torch
+    (sort / searchsorted), on CPU tensors as well; it allocates, so it cannot run under stream capture."""
+    B, G = genes.shape
+    S = genes_subset.shape[1]
+    if genes_subset.shape[0] != B or counts_subset.shape != genes_subset.shape:
+        raise ValueError(f"expected genes (B,G) and genes_subset / counts_subset (B,S); got {tuple(genes.shape)}, "
+                         f"{tuple(genes_subset.shape)}, {tuple(counts_subset.shape)}")
+    if B * (G + S) > 2 ** 31 - 65:
+        raise ValueError(f"B * (G + S) = {B * (G + S)} entries exceed the int32 entry index")
+    dev = genes.device
+    keys = torch.cat([genes.reshape(-1), genes_subset.reshape(-1)]).to(torch.long)
+    keep = torch.cat([torch.ones(B * G, dtype=torch.bool, device=dev), counts_subset.reshape(-1) != 0])
+    entries = torch.arange(B * (G + S), device=dev)[keep]
+    keys, perm = torch.sort(keys[keep], stable=True)
+    order = entries[perm].to(torch.int32)
+    seg = torch.searchsorted(keys, torch.arange(n_rows + 1, device=dev)).to(torch.int32)      # seg[r] = entries with a row below r
+    return order, seg
 
 
 class _VAETrainFn(torch.autograd.Function):
@@ -80,12 +105,23 @@ class _VAETrainFn(torch.autograd.Function):
         w, keep_w = cache["w"]
         g, keep_g = cache["g"]
         ptr = lambda t: None if t is None else t.data_ptr()
+        args = (h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(), lib.data_ptr(), G,
+                mu.data_ptr(), theta.data_ptr(), z.data_ptr(), ptr(dmu), ptr(dtheta), ptr(dz), ctx.saved.data_ptr(), ctx.ws.data_ptr(),
+                ctx.prec)
+        ordered = bool(module.deterministic) or module.__dict__.get("_env_deterministic", False) or torch.are_deterministic_algorithms_enabled()
         with torch.cuda.device(dev):
-            _lib.check(L.scldm_vae_train_backward_ex(h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S,
-                                                     genes.data_ptr(), lib.data_ptr(), G, mu.data_ptr(), theta.data_ptr(), z.data_ptr(),
-                                                     ptr(dmu), ptr(dtheta), ptr(dz), ctx.saved.data_ptr(), ctx.ws.data_ptr(), ctx.prec,
-                                                     _stream_ptr()),
-                       "scldm_vae_train_backward_ex")
+            if ordered:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the ordered (deterministic) VAE training backward cannot be captured into a graph: building "
+                                       "the table index allocates; capture the default (atomic) mode or run this step eagerly")
+                order, seg = table_order(genes, genes_subset, counts_subset, module.input_layer.gene_embedding.weight.shape[0])
+                rows = torch.empty(L.scldm_vae_train_rows_bytes(h, B, S, G), dtype=torch.uint8, device=dev)
+                _lib.check(L.scldm_vae_train_backward_ordered(*args, order.data_ptr(), seg.data_ptr(), order.numel(), rows.data_ptr(),
+                                                              _stream_ptr()),
+                           "scldm_vae_train_backward_ordered")
+            else:
+                _lib.check(L.scldm_vae_train_backward_ex(*args, _stream_ptr()), "scldm_vae_train_backward_ex")
+        module.last_table_gradient_mode = "ordered" if ordered else "atomic"
         ctx.saved = ctx.ws = None
         views = _unflatten_dense_tensors(flat, params)      # one C++ call instead of 175 slices + views
         out = [v if ctx.needs_input_grad[5 + i] else None for i, v in enumerate(views)]
@@ -93,6 +129,14 @@ class _VAETrainFn(torch.autograd.Function):
 
 
 class TransformerVAE(nn.Module):
+    # Gradients of the two embedding tables (gene_embedding, theta) in training: False = float atomics (torch's own embedding
+    # backward does the same), True = a fixed-order segmented sum (scldm_vae_train_backward_ordered): with it EVERY gradient is
+    # bit-equal run to run on one build and one GPU model - what the reference trainer's `deterministic:` asks for
+    # (experiments/configs/training/default.yaml:14).  Also on with SCLDM_VAE_DETERMINISTIC=1 (read when the native handle is
+    # created) or while torch.are_deterministic_algorithms_enabled().  Ordered steps cannot be captured into a graph.
+    deterministic: bool = False
+    last_table_gradient_mode: str | None = None      # "ordered" / "atomic": the mode of the last backward
+
     def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer,
                  input_layer: InputTransformerVAE):
         super().__init__()
@@ -131,6 +175,7 @@ class TransformerVAE(nn.Module):
             with torch.cuda.device(emb.device):
                 _lib.check(L.scldm_vae_create(C.byref(cfg), C.byref(h)), "scldm_vae_create")
             self._handle = h
+            self.__dict__["_env_deterministic"] = os.environ.get("SCLDM_VAE_DETERMINISTIC", "0") == "1"
         params = list(self.parameters())
         key = tuple(p.data_ptr() for p in params)
         ver = tuple(p._version for p in params)
@@ -155,7 +200,7 @@ class TransformerVAE(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _weights_fp=None, _ws=None, _keep=None)
-        for k in ("_train_cache", "_found_inf", "_found_inf_handle"):    # (the flag is registered with the handle that does not travel)
+        for k in ("_train_cache", "_found_inf", "_found_inf_handle", "_env_deterministic"):    # (the flag is registered with the handle that does not travel)
             state.pop(k, None)
         return state
 
