@@ -18,7 +18,15 @@ namespace scldm {
 // Hidden indices >= H are zero (exact padding of 684 -> 768).
 // m16 (FT=2, 16-bit policies; dit_forward.hpp: gemm_pass_tile16): the W12 units of a chunk (and of the trailing half chunk) are
 // 16-row x 32-k fragments instead - unit vv = k-step (vv & 7) of 32 of tile vv >> 3, fragment 0 = w1[hid], fragment 1 = w2[hid],
-// hid = c*128 + (w*2 + tile)*16 + (l&15), k = 32*(vv & 7) + (l>>4)*8 + j.  Same units, same bytes; every other unit is unchanged.
+// hid = c*128 + (w*2 + tile)*16 + (l&15), k = 32*(vv & 7) + (l>>4)*8 + j.  Same units, same bytes.
+// m16 also moves whole 64-row passes to 16x16 tiles (dit_forward.hpp: gemm_pass16; one switch per pass, kM16Proj / kM16Down):
+// a 32-k step of such a pass is two consecutive units; pass-local unit v holds k-step v >> 1 and row pair
+// v & 1, its fragment ft the row tile R4 = 2 (v & 1) + ft: lane l, element j = row 16 R4 + (l&15) of the wave's 64 rows,
+// k = 32 (v >> 1) + (l>>4)*8 + j.
+//   c_proj (units 48-63): wave rows w*64 + 16 R4 + (l&15)
+//   mlp.c_proj (chunk units 16-23, half-chunk units 8-11): k is the hidden index c*128 + 32 (v >> 1) + (l>>4)*8 + j, exact
+//   zeros for hid >= H
+// Every other unit is unchanged.
 // ------------------------------------------------------------------------------------------------
 // One element of a layer's packed stream (index documented above); FT = 32-row tiles per wave.
 // s1 / s2: factors applied to the w1 / w2 rows (OP::kW1Scale / kW2Scale of the stream's precision policy)
@@ -32,8 +40,15 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
   const int gu = (int)(idx / unit_elems), w = gu / UL, u = gu % UL;
   const int r = l & 31, k8 = (l >> 5) * 8 + j;
   const int frow = (w * FT + ft) * 32 + r;  // output feature row of this wave's tile
+  // m16 passes on 16x16 tiles (gemm_pass16): pass-local unit v, fragment ft -> row 16 (2 (v & 1) + ft) + (l & 15) of the wave's
+  // 64 rows, k = 32 (v >> 1) + 8 (l >> 4) + j
+  const int r16 = l & 15, k16 = (l >> 4) * 8 + j;
+  auto row64 = [&](int v) { return 16 * (2 * (v & 1) + ft) + r16; };
   float val;
-  if (u < 32 && FT == 2) {
+  if (u >= 48 && u < 64 && m16 && kM16Proj) {
+    const int v = u - 48;
+    val = Wproj[(size_t)(w * 64 + row64(v)) * 256 + (v >> 1) * 32 + k16];
+  } else if (u < 32 && FT == 2) {
     // Q and K of ONE head per pass: units 0-15 = head 0, 16-31 = head 1; inside a unit fragment 0 is the head's Q tile and
     // fragment 1 its K tile of the same k-step (an ordinary two-tile gemm_pass whose "feature tiles" are Q_h and K_h)
     const int head = u >> 4, ks = u & 15;
@@ -54,6 +69,9 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
       const int ks = 2 * vh + ft, hid = hid0 + w * 16 + (r & 15);
       const float* src = (r < 16) ? W1 : W2;
       val = (hid < H) ? src[(size_t)hid * 256 + ks * 16 + k8] * ((r < 16) ? s1 : s2) : 0.f;
+    } else if (m16 && kM16Down) {
+      const int v = vh - 8, hid = hid0 + (v >> 1) * 32 + k16;
+      val = (hid < H) ? Wcp[(size_t)(w * 64 + row64(v)) * H + hid] : 0.f;
     } else {
       const int hid = hid0 + (vh - 8) * 16 + k8;
       val = (hid < H) ? Wcp[(size_t)frow * H + hid] : 0.f;
@@ -70,6 +88,9 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
       const int hid = c * kHC + (w * FT + tile) * 16 + (r & 15);
       const float* src = (r < 16) ? W1 : W2;
       val = (hid < H) ? src[(size_t)hid * 256 + ks * 16 + k8] * ((r < 16) ? s1 : s2) : 0.f;
+    } else if (m16 && kM16Down) {
+      const int v = vv - 16, hid = c * kHC + (v >> 1) * 32 + k16;
+      val = (hid < H) ? Wcp[(size_t)(w * 64 + row64(v)) * H + hid] : 0.f;
     } else {
       const int hid = c * kHC + (vv - 16) * 16 + k8;
       val = (hid < H) ? Wcp[(size_t)frow * H + hid] : 0.f;

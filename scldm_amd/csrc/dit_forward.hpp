@@ -1,12 +1,12 @@
-// Fused adaLN-Zero DiT layer for gfx950: one launch = one transformer block over all sample-forwards
-// (the first launch also does the input projection, the last one the final layer).  Inside a layer the
-// fp32 residual lives in registers: it is read once and written once per layer.
+// Fused adaLN-Zero DiT for gfx950: one launch = up to kMaxLayersPerLaunch consecutive transformer blocks over all
+// sample-forwards (eight for the inference kernels: the whole reference network, input projection and final layer
+// included; four for the recording kernels).  The fp32 residual lives in registers across the layers of a launch: it
+// is read from / written to the hand-off buffer only at a launch boundary.
 //
-// Why one launch per layer and not one persistent launch for the whole network: every workgroup streams
-// the layer's full 1.7 MB of weights; with all CUs of an XCD on the SAME layer that stream is served by the
-// 4 MB L2.  A whole-network persistent variant was measured (round 1): workgroups drift across layers, the
-// 13.6 MB weight set falls out of L2 and the GEMM phases slow down 1.8x.  Kernel boundaries are the cheapest
-// lockstep on this chip.
+// Every workgroup streams each layer's full 1.7 MB of weights; the workgroups of a launch start together and walk the
+// layers at the same pace, so the stream is served mostly by the XCD's 4 MB L2 (layers per launch, measured:
+// profiles/r4a_ab_lpl8_l2warm.txt).  A whole-network PERSISTENT variant was measured in round 1: its workgroups drift
+// across layers, the 13.6 MB weight set falls out of L2 and the GEMM phases slow down 1.8x.
 //
 // Replaces the reference's (eager, ~230 launches per forward)
 //   DiT.forward trunk                     src/scldm/nnets.py:290-296
@@ -64,6 +64,12 @@ constexpr int kDbgStamps = 32;
 // softmax / SiLU VALU work measured -2 % kernel time (389 -> 381 us, same session); priority held across the whole layer
 // except LayerNorm measured +1 % instead.
 constexpr int kGemmPassPrio = 1;
+// Which GEMM passes of the M16 instantiations (16-bit policies, FT = 2) run on 16x16x32 MFMA tiles besides the SwiGLU
+// up-projection; the weight packer (dit_aux.hpp: pack_layer_val, m16) reads the same constants, so a pass is moved or left
+// behind by its switch alone.  A moved pass hands its result back in the 32x32 accumulator layout (relayout16), so nothing
+// downstream of it changes.  Measurements, and the Q/K and V passes left on 32x32 tiles (they spill): DESIGN section 4.1 / 8.
+constexpr bool kM16Proj = true;    // attention c_proj
+constexpr bool kM16Down = true;    // SwiGLU down-projection (W3)
 // layer slots instantiated in the fused kernel (code size grows with it: ~30 KB of ISA per slot): EIGHT for the inference
 // kernels - the whole reference network in one launch, no residual hand-off through HBM at all (same-box interleaved A/B,
 // profiles/r4a_ab_lpl8_l2warm.txt: +0.8 % at 4 096 cells, +2.0 % at 1 024, +1.9 % at 512 over four); four for the recording
@@ -388,6 +394,93 @@ __device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b
   __builtin_amdgcn_s_setprio(0);
 }
 
+// A whole 64-row pass on 16x16 tiles (FT = 2, 16-bit policies): t[R4][j] (+)= W-tile(R4) * B-tile(j) over KSTEPS32 * 32 k-values,
+// R4 = the wave's four 16-row tiles, j = token tile of 16.  Same ring, units and bytes as gemm_pass; a 32-k step consumes two
+// consecutive units: unit v = k-step v >> 1, row pair rp = v & 1, fragment f = row tile 2 rp + f; lane l, element e = row
+// 16 R4 + (l & 15), k = 32 (v >> 1) + 8 (l >> 4) + e (pack_layer_val, m16).  The B fragments are read once per 32-k step and
+// refilled in place behind the second unit's MFMAs (a second set is 16 VGPRs: gemm_pass_tile16).  Every output element is one
+// accumulator chain over k in natural order, 8-element groups, the bias as the initial C operand: the bits of gemm_pass.
+// ZERO: tile (R4, *) starts from init[R4] (a per-row bias tile: rows 4 (l >> 4)..+3 of the row tile) or from zero.  The pass's
+// first 32-k step spans TWO units, and `first` holds for both: unit 0 initialises row tiles 0 and 1, unit 1 row tiles 2 and 3.
+template <typename OP, int NTT, int KSTEPS32, bool ZERO, int PF>
+__device__ __forceinline__ void gemm_pass16(f32x4 (&t)[4][2 * NTT], WStream<OP, PF, 2>& ws, const typename OP::E* __restrict__ bsm,
+                                            int ldb, int lane, const f32x4* init = nullptr) {
+  using Frag = typename OP::Frag;
+  constexpr int UNITS = 2 * KSTEPS32, NJ = 2 * NTT;
+  // a pass shorter than the ring (the trailing half chunk's down-projection) is legal only as the LAST pass of the stream
+  static_assert(PF % 2 == 0 && (UNITS % PF == 0 || UNITS < PF), "whole ring revolutions (or a final short pass) of unit pairs");
+  static_assert((KSTEPS32 & (KSTEPS32 - 1)) == 0, "the read-ahead of the last k-step wraps with a mask");
+  const typename OP::E* bbase = bsm + (lane & 15) * ldb + (lane >> 4) * 8;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  Frag b[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) b[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb);
+  auto kstep = [&](int k, int s, bool first) {   // s = ring slot of unit 2 k
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      t[0][j] = OP::mma16(ws.ring[s][0], b[j], first ? (init ? init[0] : zero) : t[0][j]);
+      t[1][j] = OP::mma16(ws.ring[s][1], b[j], first ? (init ? init[1] : zero) : t[1][j]);
+    }
+    ws.ring[s][0] = ws.fetch(0);
+    ws.ring[s][1] = ws.fetch(1);
+    ws.advance(2);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      t[2][j] = OP::mma16(ws.ring[s + 1][0], b[j], first ? (init ? init[2] : zero) : t[2][j]);
+      t[3][j] = OP::mma16(ws.ring[s + 1][1], b[j], first ? (init ? init[3] : zero) : t[3][j]);
+      // after the last k-step: k-step 0 again, never used (the read stays inside the row)
+      b[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb + ((k + 1) & (KSTEPS32 - 1)) * 32);
+    }
+    ws.ring[s + 1][0] = ws.fetch(0);
+    ws.ring[s + 1][1] = ws.fetch(1);
+    ws.advance(2);
+    if (OP::kPin) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NJ, 0);               // MFMA
+      __builtin_amdgcn_sched_group_barrier(0x020, 2 * OP::kFragLoads, 0);   // VMEM read
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                  // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, OP::kFragLoads, 0);     // DS read
+      }
+      __builtin_amdgcn_sched_group_barrier(0x020, 2 * OP::kFragLoads, 0);   // VMEM read
+    }
+  };
+  __builtin_amdgcn_s_setprio(kGemmPassPrio);
+#pragma unroll
+  for (int s = 0; s < (PF < UNITS ? PF : UNITS); s += 2) kstep(s / 2, s, ZERO && s == 0);
+#pragma unroll 1
+  for (int u0 = PF; u0 < UNITS; u0 += PF) {
+#pragma unroll
+    for (int s = 0; s < PF; s += 2) kstep((u0 + s) / 2, s, false);
+  }
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// Two 16x16 C/D tiles T0, T1 (lane l: col l & 15, rows 4 (l >> 4)..+3) that cover the same 16 rows 16 R.. and the two 16-column
+// halves of a 32x32 tile -> quads 2 R and 2 R + 1 of that tile's C/D layout (lane l: col l & 31; register r: row
+// 8 (r >> 2) + 4 (l >> 5) + (r & 3)).  Per register two in-place lane swaps: the 16-lane groups [a0 a1 a2 a3], [b0 b1 b2 b3]
+// become [a0 b0 a2 b2], [a1 b1 a3 b3] (v_permlane16_swap: odd groups of the first <-> even groups of the second) and then
+// [a0 b0 a1 b1], [a2 b2 a3 b3] (v_permlane32_swap).  tests/test_mfma16_relayout_cpu.py restates the lane algebra.
+__device__ __forceinline__ void relayout16(const f32x4& T0, const f32x4& T1, f32x16& dst, int R) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(T0[i]), __float_as_uint(T1[i]), false, false);
+    const auto r = __builtin_amdgcn_permlane32_swap(s[0], s[1], false, false);
+    dst[(2 * R) * 4 + i] = __uint_as_float(r[0]);
+    dst[(2 * R + 1) * 4 + i] = __uint_as_float(r[1]);
+  }
+}
+// the tiles of a gemm_pass16 -> the [2][NTT] accumulator set of the same pass on 32x32 tiles
+template <int NTT>
+__device__ __forceinline__ void relayout16_all(const f32x4 (&t)[4][2 * NTT], f32x16 (&acc)[2][NTT]) {
+#pragma unroll
+  for (int ft = 0; ft < 2; ++ft)
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt)
+#pragma unroll
+      for (int R = 0; R < 2; ++R) relayout16(t[2 * ft + R][2 * tt], t[2 * ft + R][2 * tt + 1], acc[ft][tt], R);
+}
+
 #ifdef SCLDM_PHASE_TIMING
 #define SCLDM_LN_STAMP(i)                                                                              \
   do {                                                                                                 \
@@ -529,8 +622,9 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
   }
 }
 
-// M16 (16-bit policies, FT = 2): the SwiGLU up-projection runs on 16x16 tiles (gemm_pass_tile16) from a stream packed for it
-// (pack_layer_val, m16); every other pass, the residual and the record stay on 32x32 tiles.  SCLDM_FWD_MFMA=32 selects M16 = false.
+// M16 (16-bit policies, FT = 2): the SwiGLU up-projection (gemm_pass_tile16) and the passes switched on by kM16Proj / kM16Down
+// (gemm_pass16 + relayout16) run on 16x16 tiles from a stream packed for them (pack_layer_val, m16); the other passes, the
+// attention core, the residual and the record stay on 32x32 tiles.  SCLDM_FWD_MFMA=32 selects M16 = false.
 template <typename OP, int NTT, int FT, bool REC = false, bool M16 = false>
 __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 1) ? 2 : 1) void dit_forward_kernel(const FwdArgs a) {
   static_assert(!M16 || (FT == 2 && sizeof(typename OP::E) == 2 && sizeof(typename OP::Frag) == 16), "M16: 16-bit policies, FT = 2");
@@ -573,10 +667,10 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
   auto xw_ptr = [&]() { return a.x + ((size_t)(tile_id * NW + wave) * (4 * FT * NTT) * 64 + (threadIdx.x & 63)) * 4; };
 
   // The residual stream (this wave's features x TM tokens, accumulator layout; scalars: it never feeds an MFMA and
-  // whole-vector values would be copied around by the compiler).  With FT=2 the allocator parks ~1/3 of it in scratch
-  // during attention / MLP.  Parking it explicitly in the hand-off buffer and re-reading it ahead of the preceding GEMM
-  // was measured SLOWER (451 vs 396 us): vmcnt retires in order, so every wait on a weight-ring load issued after
-  // the slow residual loads/stores also waits for them.
+  // whole-vector values would be copied around by the compiler).  The shipped instantiations keep all of it in
+  // registers (no spills, no scratch: profiles/r10_fwd_mfma16_passes_resources.txt).  Parking it explicitly in the
+  // hand-off buffer and re-reading it ahead of the preceding GEMM was measured SLOWER (451 vs 396 us): vmcnt retires in
+  // order, so every wait on a weight-ring load issued after the slow residual loads/stores also waits for them.
   float xr[FT][NTT][16];
   auto load_x = [&](float (&dst)[FT][NTT][16]) {
     const float* xw = xw_ptr();
@@ -943,7 +1037,14 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
   SCLDM_STAMP(6);
 
   // ---- attention projection, gated residual (a2), LN2 + modulate(a3 = scale, a4 = shift) -> XA ----
-  {
+  if constexpr (M16 && kM16Proj) {
+    f32x4 t[4][2 * NTT];
+    f32x4 pb[4];
+#pragma unroll
+    for (int R4 = 0; R4 < 4; ++R4) pb[R4] = *reinterpret_cast<const f32x4*>(bp + fbase + R4 * 16 + (lane >> 4) * 4);
+    gemm_pass16<OP, NTT, 8, true, PF>(t, ws, AO, L::XA_LD, lane, pb);   // c_proj(attention) + bias
+    relayout16_all<NTT>(t, acc);
+  } else {
     f32x16 pbias[FT];
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft)
@@ -976,6 +1077,9 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
 
   // ---- SwiGLU MLP, hidden processed in chunks of 128 (NW waves x FT tiles x 16 hidden) staged through HB ----
   f32x16 accp[FT][NTT];
+  // M16 down-projection: the accumulators stay 16x16 tiles across all chunks and are laid out as accp once, after the last chunk
+  constexpr bool kDown16 = M16 && kM16Down;
+  f32x4 t3[kDown16 ? 4 : 1][kDown16 ? 2 * NTT : 1];
   // one SwiGLU chunk; HALF (compile time) = the trailing 64-unit chunk: one W12 tile per wave, K = 64 down-projection
   auto do_chunk = [&](auto half_tag, int c) {
     constexpr bool HALF = decltype(half_tag)::value;
@@ -1039,12 +1143,18 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
     lds_barrier();
     if (c == 0) SCLDM_STAMP(12);
     constexpr int KS = HALF ? 4 : 8;
-    if (c == 0) gemm_pass<OP, NTT, FT, KS, false, true, PF>(accp, ws, HBc, L::HB_LD, lane);
-    else gemm_pass<OP, NTT, FT, KS, false, false, PF>(accp, ws, HBc, L::HB_LD, lane);
+    if constexpr (kDown16) {
+      if (c == 0) gemm_pass16<OP, NTT, KS / 2, true, PF>(t3, ws, HBc, L::HB_LD, lane);
+      else gemm_pass16<OP, NTT, KS / 2, false, PF>(t3, ws, HBc, L::HB_LD, lane);
+    } else {
+      if (c == 0) gemm_pass<OP, NTT, FT, KS, false, true, PF>(accp, ws, HBc, L::HB_LD, lane);
+      else gemm_pass<OP, NTT, FT, KS, false, false, PF>(accp, ws, HBc, L::HB_LD, lane);
+    }
     if (c == 0) SCLDM_STAMP(13);
   };
   for (int c = 0; c < a.n_chunks; ++c) do_chunk(std::false_type{}, c);
   if (a.half_chunk) do_chunk(std::true_type{}, a.n_chunks);
+  if constexpr (kDown16) relayout16_all<NTT>(t3, accp);
   SCLDM_STAMP(9);
 
   // another layer follows in this launch: its weight ring starts now (the ring registers are free after the last pass),
