@@ -632,6 +632,31 @@ size_t scldm_sinkhorn_workspace_bytes(int n, int m);
 int scldm_wasserstein_sinkhorn(const float* x0, int n, const float* x1, int m, int D, int power, float reg, long long num_iter_max,
                                float stop_thr, double* cost_out, long long* iters_out, int* status_out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics of the validation step (src/scldm/models.py:315-331: zeros accuracy, mse, pcc) and of the generation
+ * evaluation (:892-928: r2_mean, r2_var) in one fused streaming pass over pred (n_pred,G) and truth (n_true,G), device fp32.
+ * U = log1p(pred / pred_div * target_sum), V = log1p(truth / true_div * target_sum); a NULL divisor vector means the
+ * row's own sum; target_sum <= 0 means the inputs are already scaled (U = pred, V = truth; the divisors are ignored).
+ *   MSE        mean (U - V)^2
+ *   PCC        nanmean over genes of the Pearson correlation over cells (NaN where a variance is 0 or n < 2), clamped to [-1, 1]
+ *   ZEROS      mean ((pred == 0) == (truth == 0)) on the untransformed inputs
+ *   R2_MEAN    r2(U.mean(0), V.mean(0)), r2(preds, target) = 1 - sum (target - preds)^2 / sum (target - mean(target))^2
+ *   R2_VAR     the same on the unbiased per-gene variances (NaN for n < 2)
+ *   PCC_VALID  number of genes whose correlation is not NaN
+ * n_pred != n_true: MSE, PCC and ZEROS are NaN (PCC_VALID 0); the r2 values need no paired rows.  A zero divisor gives the
+ * NaN / inf of the expression above, and they propagate.  out: SCLDM_EVAL_N device doubles.  pcc_per_gene: device (G) fp32
+ * or NULL.  gene_stats: device (4,G) fp32 = mean_p, var_p, mean_t, var_t, or NULL.  Every sum runs in a fixed order that
+ * depends on (n_pred, n_true, G) alone: results are bit-reproducible.  No host synchronisation, no allocation.
+ * scldm_log1p_normalize writes log1p(x / div * target_sum) (div NULL: the row's own sum; target_sum <= 0: a copy).
+ * ------------------------------------------------------------------------------------------------ */
+enum { SCLDM_EVAL_MSE = 0, SCLDM_EVAL_PCC = 1, SCLDM_EVAL_ZEROS = 2, SCLDM_EVAL_R2_MEAN = 3, SCLDM_EVAL_R2_VAR = 4,
+       SCLDM_EVAL_PCC_VALID = 5, SCLDM_EVAL_N = 6 };
+size_t scldm_eval_workspace_bytes(int n_pred, int n_true, int G);
+int scldm_eval_count_metrics(const float* pred, int n_pred, const float* truth, int n_true, int G, const float* pred_div,
+                             const float* true_div, float target_sum, double* out, float* pcc_per_gene, float* gene_stats,
+                             void* ws, void* stream);
+int scldm_log1p_normalize(const float* x, int n, int G, const float* div, float target_sum, float* out, void* stream);
+
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the
  * production library returns SCLDM_ERR_STATE. */
