@@ -254,6 +254,49 @@ int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ulabels, int 
                      int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method,
                      int precision, void* ws, void* stream);
 
+/* Fixed-grid SDE sampling: the stochastic face of the reference's Sampler (transport.py:269-322, integrators.py:7-75) for the Linear
+ * path with a velocity model, as one call.  With v = forward_with_cfg(x, t): score = (t v - x) / (1 - t), SDE drift
+ * f = v + D(t) score, and D(t) by diffusion_form (norm = diffusion_norm; path.py:52-77):
+ *   SIGMA, LINEAR: norm (1 - t)   CONSTANT: norm   DECREASING: 0.25 (norm cos(pi t) + 1)^2   INC_DEC: norm sin^2(pi t)
+ * Grid: t = linspace(0, t1, num_steps) in fp32, t1 = 1 - last_step_size (last_step NONE forces last_step_size 0), dt = t[1] - t[0];
+ * steps run at t[0] .. t[num_steps - 2], each with ONE normal draw w of the state's shape:
+ *   euler: x <- x + dt f(x, t) + sqrt(2 D dt) w
+ *   heun:  xhat = x + sqrt(2 D(t) dt) w; K1 = f(xhat, t); K2 = f(xhat + dt K1, t + dt); x <- xhat + dt / 2 (K1 + K2)
+ * then one more evaluation at t1 without noise - MEAN: x + last_step_size f(x, t1); TWEEDIE: x + (1 - t1) v (the reference's
+ * x / t1 + (1 - t1)^2 / t1 score, simplified); EULER: x + last_step_size v; NONE: x unchanged, no evaluation.
+ * num_steps - 1 (+ 1) evaluations for euler, 2 (num_steps - 1) (+ 1) for heun; every update is x' = a_x x + a_v v + a_w w with
+ * host-side scalars and rides in the kernel that blends the CFG passes.
+ * z (2B,S,Din) is updated in place (first B rows unconditional, last B guided; labels / passes as scldm_sample_ode, same workspace:
+ * scldm_dit_workspace_bytes(h, 2B + n_pass B, 1 + n_pass n_urows, 2B)).
+ * noise: NULL, or device (num_steps - 1, 2B, S*Din) normals used INSTEAD of the generator (step-major).
+ * Generator: Philox4x32-10 keyed by `seed`; the value of an element depends on (seed, step, global row, column) only, where the
+ *   global state is (2, cells_total, S*Din) and this call holds cells [cell_offset, cell_offset + B) of it: shards of one solve draw
+ *   the noise the whole solve would have drawn.  The seed is a launch argument: a captured graph replays the SAME noise.
+ * traj: NULL, or device (num_steps, 2B, S*Din) receiving every state the reference's list holds (num_steps - 1 step results, then
+ *   the last-step result, which is also left in z).
+ * SCLDM_ERR_SHAPE (nothing is launched) for the corners where the reference returns NaN under this transport - form SBDM (D is
+ * infinite at t = 0), heun with last_step NONE (score at t = 1), MEAN / TWEEDIE with last_step_size 0 (score at t = 1) - and for
+ * num_steps < 2, last_step_size outside [0, 1), cells_total < cell_offset + B, unknown method / form / last step. */
+#define SCLDM_SDE_FORM_SIGMA 0
+#define SCLDM_SDE_FORM_LINEAR 1
+#define SCLDM_SDE_FORM_CONSTANT 2
+#define SCLDM_SDE_FORM_DECREASING 3
+#define SCLDM_SDE_FORM_INC_DEC 4   /* the reference spells it "inccreasing-decreasing" */
+#define SCLDM_SDE_FORM_SBDM 5      /* the reference's default; rejected (see above) */
+#define SCLDM_SDE_LAST_NONE 0
+#define SCLDM_SDE_LAST_MEAN 1
+#define SCLDM_SDE_LAST_TWEEDIE 2
+#define SCLDM_SDE_LAST_EULER 3
+int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                     const uint32_t* pass_mask, const float* pass_scale, int num_steps, int method, int diffusion_form,
+                     float diffusion_norm, int last_step, float last_step_size, const float* noise, unsigned long long seed,
+                     long long cell_offset, long long cells_total, float* traj, int precision, void* ws, void* stream);
+
+/* The normals scldm_sample_sde draws at `step` for rows [cell_offset, cell_offset + n_rows_local) of CFG half `half` (0: the
+ * unconditional rows, 1: the guided rows) of a (2, cells_total, e) state.  out: device (n_rows_local, e), 16-byte aligned; e % 4 == 0. */
+int scldm_sde_noise(float* out, long long n_rows_local, int e, unsigned long long seed, int step, int half, long long cell_offset,
+                    long long cells_total, void* stream);
+
 /* Options of a handle (read by the calls that follow).
  * SCLDM_OPT_CFG1_DIRECT (default 0): with ONE conditional pass of guidance scale exactly 1.0 and a scalar t (scldm_sample_ode,
  *   scldm_dit_forward_cfg with t_stride 0), DiT.forward_with_cfg's guided half u2 + 1.0 * (c2 - u2) (nnets.py:368,376) is c2 up to

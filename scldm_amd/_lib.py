@@ -16,6 +16,8 @@ PREC_FP32, PREC_BF16, PREC_BF16X3, PREC_FP16 = 0, 1, 2, 3
 METHOD_EULER, METHOD_HEUN = 0, 1
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "fp16": PREC_FP16}
 METHODS = {"euler": METHOD_EULER, "heun": METHOD_HEUN}
+SDE_FORMS = {"sigma": 0, "linear": 1, "constant": 2, "decreasing": 3, "inccreasing-decreasing": 4, "SBDM": 5}   # SCLDM_SDE_FORM_*
+SDE_LAST_STEPS = {None: 0, "Mean": 1, "Tweedie": 2, "Euler": 3}                                                  # SCLDM_SDE_LAST_*
 OPT_CFG1_DIRECT = 1
 OPT_TAIL_SPLIT = 2   # scldm_dit_set_option (include/scldm_hip.h)
 
@@ -134,6 +136,10 @@ def lib() -> C.CDLL:
                                         C.c_int, C.POINTER(C.c_uint32), c_float_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_sample_ode.argtypes = [C.c_void_p, C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.POINTER(C.c_uint32), c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_sample_sde.argtypes = [C.c_void_p, C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), c_float_p,
+                                   C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_longlong,
+                                   C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_sde_noise.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
     L.scldm_mfma_sustained_tflops.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.scldm_dit_block_timing_enable.argtypes = [C.c_void_p, C.c_int]
     L.scldm_dit_block_timing_enable.restype = None
@@ -222,7 +228,7 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_train_prepare", "scldm_dit_train_set_grad_events", "scldm_dit_train_forward", "scldm_dit_train_backward", "scldm_fm_mix", "scldm_fm_loss", "scldm_fm_loss_bwd", "scldm_vae_create", "scldm_vae_destroy", "scldm_vae_load_weights", "scldm_vae_refresh_weights", "scldm_vae_kernel_timing_enable", "scldm_vae_kernel_timing",
            "scldm_vae_workspace_bytes", "scldm_vae_encode", "scldm_vae_decode", "scldm_vae_decode_sample", "scldm_vae_train_saved_bytes", "scldm_vae_train_workspace_bytes", "scldm_vae_train_forward", "scldm_vae_train_backward", "scldm_vae_train_forward_ex", "scldm_vae_train_backward_ex", "scldm_vae_train_set_found_inf", "scldm_vae_train_rows_bytes", "scldm_vae_train_backward_ordered", "scldm_nb_loglik", "scldm_nb_loglik_bwd", "scldm_nb_sample", "scldm_tokenize_expressed", "scldm_csr_count", "scldm_csr_fill", "scldm_mmd_workspace_bytes",
            "scldm_mmd_kernel_sum", "scldm_sinkhorn_workspace_bytes", "scldm_wasserstein_sinkhorn", "scldm_eval_workspace_bytes",
-           "scldm_eval_count_metrics", "scldm_log1p_normalize"]
+           "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise"]
 
 
 def check(rc: int, what: str) -> None:

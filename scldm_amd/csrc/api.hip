@@ -14,6 +14,7 @@
 #include "dit_forward.hpp"
 #include "dit_handle.hpp"
 #include "ode_rk.hpp"
+#include "sde.hpp"
 
 using namespace scldm;
 
@@ -925,6 +926,40 @@ extern "C" int scldm_dit_forward_cfg(scldm_dit* h, const float* x, const float* 
   return cfg_eval(h, pl, x, t, t_stride, w, out, precision, st);
 }
 
+// Whole-solve conditioning (see scldm_sample_ode): every evaluation's adaLN vectors in one row launch and one projection, into the handle's
+// buffer; *mod_all stays NULL when the per-evaluation launches are to be used (over budget, no room, or the buffer would have to grow
+// inside a stream capture).  temb: the (n_evals, 256) timestep embeddings of the solve.
+static int cond_all_prepare(scldm_dit* h, const CfgPlan& pl, const float* temb, int n_evals, int prec, hipStream_t st, float** mod_all_out) {
+  int rc;
+  float* mod_all = nullptr;
+  const size_t rows_all = (size_t)n_evals * pl.n_rows;
+  const size_t b_mod = align256(rows_all * h->mod_w * 4), b_silu = align256((rows_all + 1) * 256 * 4), b_split = align256((rows_all + 31) / 32 * 32 * 256 * 4);
+  if (b_mod <= ((size_t)1 << 30)) {
+    const size_t need = b_mod + b_silu + b_split;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap);
+    if (h->cond_all_bytes < need && cap == hipStreamCaptureStatusNone) {   // (no allocation inside a stream capture: the per-evaluation launches)
+      HIP_TRY(hipStreamSynchronize(st));     // (an earlier solve on this stream may still read the buffer that is replaced)
+      if (h->cond_all) (void)hipFree(h->cond_all);
+      h->cond_all = nullptr;
+      h->cond_all_bytes = 0;
+      if (hipMalloc(&h->cond_all, need) == hipSuccess) h->cond_all_bytes = need;
+      else (void)hipGetLastError();          // no room: the per-evaluation launches
+    }
+    if (h->cond_all_bytes >= need) {
+      mod_all = reinterpret_cast<float*>(h->cond_all);
+      float* silu_all = reinterpret_cast<float*>(reinterpret_cast<char*>(h->cond_all) + b_mod);
+      void* split_all = reinterpret_cast<char*>(h->cond_all) + b_mod + b_silu;
+      CondRowsArgs ca = cond_rows_args(h, pl, temb, silu_all, nullptr);
+      cond_rows_kernel<<<dim3(pl.n_rows, n_evals), 256, 0, st>>>(ca);
+      LAUNCH_CHECK();
+      if ((rc = launch_adaln(h, silu_all, mod_all, (int)rows_all, st, nullptr, prec, split_all))) return rc;
+    }
+  }
+  *mod_all_out = mod_all;
+  return SCLDM_OK;
+}
+
 // torch.linspace(0, 1, steps) in fp32 (integrators.py:95): symmetric fill from both ends.
 static float linspace01(int idx, int steps) {
   const float step = 1.0f / (float)(steps - 1);
@@ -987,32 +1022,8 @@ extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ul
   // vocabulary, 51 rows x 200 Heun evaluations = 564 MB for hlca; a batch of 1 024 distinct joint labels would need 5.7 GB and keeps the
   // per-evaluation launches).
   float* mod_all = nullptr;
-  if (pre && !ahead && h->cond_all_on && n_evals > 1) {
-    const size_t rows_all = (size_t)n_evals * pl.n_rows;
-    const size_t b_mod = align256(rows_all * h->mod_w * 4), b_silu = align256((rows_all + 1) * 256 * 4), b_split = align256((rows_all + 31) / 32 * 32 * 256 * 4);
-    if (b_mod <= ((size_t)1 << 30)) {
-      const size_t need = b_mod + b_silu + b_split;
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(st, &cap);
-      if (h->cond_all_bytes < need && cap == hipStreamCaptureStatusNone) {   // (no allocation inside a stream capture: the per-evaluation launches)
-        HIP_TRY(hipStreamSynchronize(st));     // (an earlier solve on this stream may still read the buffer that is replaced)
-        if (h->cond_all) (void)hipFree(h->cond_all);
-        h->cond_all = nullptr;
-        h->cond_all_bytes = 0;
-        if (hipMalloc(&h->cond_all, need) == hipSuccess) h->cond_all_bytes = need;
-        else (void)hipGetLastError();          // no room: the per-evaluation launches
-      }
-      if (h->cond_all_bytes >= need) {
-        mod_all = reinterpret_cast<float*>(h->cond_all);
-        float* silu_all = reinterpret_cast<float*>(reinterpret_cast<char*>(h->cond_all) + b_mod);
-        void* split_all = reinterpret_cast<char*>(h->cond_all) + b_mod + b_silu;
-        CondRowsArgs ca = cond_rows_args(h, pl, w.temb, silu_all, nullptr);
-        cond_rows_kernel<<<dim3(pl.n_rows, n_evals), 256, 0, st>>>(ca);
-        LAUNCH_CHECK();
-        if ((rc = launch_adaln(h, silu_all, mod_all, (int)rows_all, st, nullptr, precision, split_all))) return rc;
-      }
-    }
-  }
+  if (pre && !ahead && h->cond_all_on && n_evals > 1)
+    if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
   int e_idx = 0;   // running evaluation index
   // one evaluation: (ahead) queue the conditioning of the next one on the second stream, wait for this one's, run the trunk
   auto eval = [&](const float* zin, float tval, float* dz, float* euler_z, float euler_h) -> int {
@@ -1052,6 +1063,182 @@ extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ul
     }
     LAUNCH_CHECK();
   }
+  return SCLDM_OK;
+}
+
+// ---- SDE sampling (sde.hpp) -----------------------------------------------------------------------------------------------------------
+// torch.linspace(0, t1, steps) in fp32: linspace01's symmetric fill for any end point (step = (t1 - 0) / (steps - 1) in fp32)
+static float linspace0(int idx, int steps, float t1) {
+  const float step = t1 / (float)(steps - 1);
+  return (idx < steps / 2) ? step * (float)idx : t1 - step * (float)(steps - idx - 1);
+}
+// D(t) of path.py:52-77 for the Linear path (sigma_t = 1 - t), in double from the fp32 t the model sees
+static double sde_diffusion(int form, double norm, double t) {
+  const double pi = 3.14159265358979323846;
+  switch (form) {
+    case SCLDM_SDE_FORM_SIGMA:
+    case SCLDM_SDE_FORM_LINEAR: return norm * (1.0 - t);
+    case SCLDM_SDE_FORM_CONSTANT: return norm;
+    case SCLDM_SDE_FORM_DECREASING: { const double c = norm * cos(pi * t) + 1.0; return 0.25 * c * c; }
+    default: { const double s = sin(pi * t); return norm * s * s; }   // SCLDM_SDE_FORM_INC_DEC
+  }
+}
+
+extern "C" int scldm_sde_noise(float* out, long long n_rows_local, int e, unsigned long long seed, int step, int half, long long cell_offset,
+                               long long cells_total, void* stream_) {
+  if (!out || ((uintptr_t)out & 15)) return fail(SCLDM_ERR_SHAPE, "scldm_sde_noise: out must be a 16-byte aligned device pointer");
+  if (n_rows_local < 1 || e < 4 || e % 4) return fail(SCLDM_ERR_SHAPE, "scldm_sde_noise: n_rows_local >= 1 and e a positive multiple of 4 (got %lld, %d)", n_rows_local, e);
+  if (step < 0 || (half != 0 && half != 1)) return fail(SCLDM_ERR_SHAPE, "scldm_sde_noise: step >= 0 and half 0 | 1 (got %d, %d)", step, half);
+  if (cell_offset < 0 || cells_total < cell_offset + n_rows_local)
+    return fail(SCLDM_ERR_SHAPE, "scldm_sde_noise: cells_total (%lld) < cell_offset (%lld) + n_rows_local (%lld)", cells_total, cell_offset, n_rows_local);
+  const long long n4 = n_rows_local * (e / 4);
+  if (n4 > 0x7fffffffll) return fail(SCLDM_ERR_SHAPE, "scldm_sde_noise: at most 2^33 elements per call");
+  const sde::NoiseGeom g{seed, cell_offset, cells_total, (uint32_t)step};
+  sde::sde_noise_kernel<<<cdiv(n4, 256), 256, 0, (hipStream_t)stream_>>>(out, n_rows_local, e, half, g);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+
+extern "C" int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                                const uint32_t* pass_mask, const float* pass_scale, int num_steps, int method, int diffusion_form,
+                                float diffusion_norm, int last_step, float last_step_size, const float* noise, unsigned long long seed,
+                                long long cell_offset, long long cells_total, float* traj, int precision, void* ws_, void* stream_) {
+  int rc = check_ready(h, precision);
+  if (rc) return rc;
+  if (!z || !ws_) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
+  if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
+  if (diffusion_form == SCLDM_SDE_FORM_SBDM)
+    return fail(SCLDM_ERR_SHAPE, "diffusion_form SBDM starts at t = 0 under the Linear path, where D = (1 - t) / t is infinite (the reference returns NaN); "
+                "use sigma, linear, constant, decreasing or inccreasing-decreasing");
+  if (diffusion_form < SCLDM_SDE_FORM_SIGMA || diffusion_form > SCLDM_SDE_FORM_INC_DEC) return fail(SCLDM_ERR_SHAPE, "unknown diffusion form %d", diffusion_form);
+  if (last_step < SCLDM_SDE_LAST_NONE || last_step > SCLDM_SDE_LAST_EULER) return fail(SCLDM_ERR_SHAPE, "unknown last step %d", last_step);
+  if (method == SCLDM_METHOD_HEUN && last_step == SCLDM_SDE_LAST_NONE)
+    return fail(SCLDM_ERR_SHAPE, "Heun without a last step evaluates the score at t = 1 in its final K2 (the reference returns NaN / inf); "
+                "use last_step Mean, Tweedie or Euler, or the Euler method");
+  if (num_steps < 2) return fail(SCLDM_ERR_SHAPE, "num_steps must be >= 2 (grid points)");
+  if (last_step == SCLDM_SDE_LAST_NONE) last_step_size = 0.f;   // transport.py:290-291
+  if (!(last_step_size >= 0.f && last_step_size < 1.f)) return fail(SCLDM_ERR_SHAPE, "last_step_size must be in [0, 1) (got %g)", (double)last_step_size);
+  if ((last_step == SCLDM_SDE_LAST_MEAN || last_step == SCLDM_SDE_LAST_TWEEDIE) && last_step_size == 0.f)
+    return fail(SCLDM_ERR_SHAPE, "last_step Mean / Tweedie with last_step_size 0 evaluates the score at t = 1; give a positive last_step_size or use last_step Euler / None");
+  if (cell_offset < 0 || cells_total < cell_offset + B) return fail(SCLDM_ERR_SHAPE, "cells_total (%lld) < cell_offset (%lld) + B (%d)", cells_total, cell_offset, B);
+  if (((uintptr_t)z & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)traj & 15)) return fail(SCLDM_ERR_SHAPE, "z, noise and traj must be 16-byte aligned");
+  CfgPlan pl;
+  if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
+  hipStream_t st = (hipStream_t)stream_;
+  Ws w = carve(h, ws_, pl.n_fwd, pl.n_rows, 2 * B);
+  const int e_row = 16 * h->cfg.n_embed_input;
+  const size_t n = (size_t)2 * B * e_row;
+  if (n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state too large (at most 2^33 elements)");
+  const bool heun = method == SCLDM_METHOD_HEUN, has_last = last_step != SCLDM_SDE_LAST_NONE;
+  const int n_steps = num_steps - 1;
+  const int n_evals = (heun ? 2 : 1) * n_steps + (has_last ? 1 : 0);
+  // the fp32 grid of integrators.py:23-24 and every evaluation's time
+  const float t1 = (float)(1.0 - (double)last_step_size);
+  const float dt = linspace0(1, num_steps, t1) - linspace0(0, num_steps, t1);
+  std::vector<float> tl;
+  tl.reserve(n_evals);
+  for (int i = 0; i < n_steps; ++i) {
+    const float t = linspace0(i, num_steps, t1);
+    tl.push_back(t);
+    if (heun) tl.push_back(t + dt);
+  }
+  if (has_last) tl.push_back(t1);
+  for (int i = 0; i < (int)tl.size() - (has_last ? 1 : 0); ++i)
+    if (!(tl[i] < 1.0f)) return fail(SCLDM_ERR_SHAPE, "evaluation %d of the solve sits at t = %g >= 1, where the score is singular", i, (double)tl[i]);
+  fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, cell_row, 2 * B, 1, B, pl.U, pl.P, nullptr, pl.direct);
+  LAUNCH_CHECK();
+  float* tscal = w.silu + (size_t)pl.n_rows * 256;   // device scalar t (solves beyond kMaxTembEvals): the spare row after the silu rows
+  const bool pre = n_evals <= kMaxTembEvals;
+  float* mod_all = nullptr;
+  if (pre) {
+    // the list of times sits at the head of the trunk's residual buffer: the embedding launch below has read it before the first trunk
+    // launch of this call overwrites it (stream order)
+    float* tlist = w.h;
+    for (int c0 = 0; c0 < n_evals; c0 += sde::kTChunk) {
+      sde::TChunk ch{};
+      const int m = std::min(sde::kTChunk, n_evals - c0);
+      for (int j = 0; j < m; ++j) ch.t[j] = tl[c0 + j];
+      sde::set_tlist_kernel<<<1, sde::kTChunk, 0, st>>>(tlist + c0, ch, m);
+    }
+    sde::t_embed_list_kernel<<<n_evals, 256, 0, st>>>(tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
+    LAUNCH_CHECK();
+    if (h->cond_all_on && n_evals > 1)
+      if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
+  }
+  sde::BlendArgs ba{};
+  ba.v = w.v;
+  ba.B = B;
+  ba.e = e_row;
+  ba.P = pl.P;
+  ba.direct = pl.direct ? 1 : 0;
+  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) ba.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
+  ba.g = sde::NoiseGeom{seed, cell_offset, cells_total, 0u};
+  int e_idx = 0;
+  // one evaluation at zin, then out = a_x zin + a_v r (+ a_w w of step `step` when a_w != 0)
+  auto eval = [&](const float* zin, float* out, float a_x, float a_v, float a_w, int step, float* traj_out) -> int {
+    const int e = e_idx++;
+    Ws we = w;
+    if (mod_all) we.mod = mod_all + (size_t)e * pl.n_rows * h->mod_w;
+    else {
+      if (!pre) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tl[e]);
+      int rc2 = cfg_cond(h, pl, tscal, 0, w, precision, st, pre ? w.temb + (size_t)e * 256 : nullptr);
+      if (rc2) return rc2;
+    }
+    int rc2 = trunk(h, zin, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, we.mod, w.ridx, w.h, w.v, precision, st);
+    if (rc2) return rc2;
+    ba.x = zin;
+    ba.out = out;
+    ba.traj = traj_out;
+    ba.a_x = a_x;
+    ba.a_v = a_v;
+    ba.a_w = a_w;
+    ba.noise_mode = a_w == 0.f ? sde::kNoiseNone : noise ? sde::kNoiseArray : sde::kNoisePhilox;
+    ba.noise = noise ? noise + (size_t)step * n : nullptr;
+    ba.g.step = (uint32_t)step;
+    sde::cfg_blend_sde_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(ba);
+    LAUNCH_CHECK();
+    return SCLDM_OK;
+  };
+  // f = c_v v + c_x x at time t (double; rounded once where it enters a kernel argument)
+  auto drift_coef = [&](float t, double* c_v, double* c_x) {
+    const double D = sde_diffusion(diffusion_form, diffusion_norm, t), om = 1.0 - (double)t;
+    *c_v = 1.0 + D * (double)t / om;
+    *c_x = -D / om;
+  };
+  for (int i = 0; i < n_steps; ++i) {
+    const float t = linspace0(i, num_steps, t1);
+    const float a_w = (float)sqrt(2.0 * sde_diffusion(diffusion_form, diffusion_norm, t) * (double)dt);
+    float* tr = traj ? traj + (size_t)i * n : nullptr;
+    double c_v, c_x;
+    drift_coef(t, &c_v, &c_x);
+    if (!heun) {   // x <- x + dt f(x, t) + sqrt(2 D dt) w
+      if ((rc = eval(z, z, (float)(1.0 + (double)dt * c_x), (float)((double)dt * c_v), a_w, i, tr))) return rc;
+    } else {
+      if (a_w != 0.f) {   // xhat = x + sqrt(2 D(t) dt) w
+        sde::PerturbArgs pa{z, noise ? noise + (size_t)i * n : nullptr, B, e_row, noise ? sde::kNoiseArray : sde::kNoisePhilox, a_w, ba.g};
+        pa.g.step = (uint32_t)i;
+        sde::sde_perturb_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(pa);
+      }
+      if ((rc = eval(z, w.dz, (float)c_x, (float)c_v, 0.f, i, nullptr))) return rc;          // K1 = f(xhat, t)
+      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.ztmp, dt, n);                      // xp = xhat + dt K1
+      drift_coef(t + dt, &c_v, &c_x);
+      if ((rc = eval(w.ztmp, w.k2, (float)c_x, (float)c_v, 0.f, i, nullptr))) return rc;      // K2 = f(xp, t + dt)
+      heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.k2, 0.5f * dt, n);                 // x = xhat + dt / 2 (K1 + K2)
+      if (tr) HIP_TRY(hipMemcpyAsync(tr, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    LAUNCH_CHECK();
+  }
+  float* tr = traj ? traj + (size_t)n_steps * n : nullptr;
+  if (has_last) {
+    double c_v, c_x;
+    drift_coef(t1, &c_v, &c_x);
+    float a_x = 1.f, a_v = last_step_size;                                   // Euler: x + last_step_size v
+    if (last_step == SCLDM_SDE_LAST_MEAN) {                                  // x + last_step_size f(x, t1)
+      a_x = (float)(1.0 + (double)last_step_size * c_x);
+      a_v = (float)((double)last_step_size * c_v);
+    } else if (last_step == SCLDM_SDE_LAST_TWEEDIE) a_v = (float)(1.0 - (double)t1);   // x / t1 + (1 - t1)^2 / t1 score = x + (1 - t1) v
+    if ((rc = eval(z, z, a_x, a_v, 0.f, n_steps, tr))) return rc;
+  } else if (tr) HIP_TRY(hipMemcpyAsync(tr, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // the reference appends the unchanged state
   return SCLDM_OK;
 }
 

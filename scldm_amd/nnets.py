@@ -904,6 +904,87 @@ class DiT(nn.Module):
         del keep
         return z
 
+    # ------------------------------------------------------------------ fused SDE sampler (transport.py:269-322 + integrators.py:7-75)
+    def sde_noise(self, seed: int, step: int, B: int, cell_offset: int = 0, cells_total: int | None = None) -> torch.Tensor:
+        """The (2B, S, C) normals `sample_sde_cfg(seed=seed)` draws at `step` for cells [cell_offset, cell_offset + B) of a solve over
+        `cells_total` cells (scldm_sde_noise): a value depends on (seed, step, global row, column) only."""
+        total = B + cell_offset if cells_total is None else cells_total
+        e = self.seq_len * self.n_embed_input
+        out = torch.empty(2 * B, self.seq_len, self.n_embed_input, device=self.pos_embed.device, dtype=torch.float32)
+        L = _lib.lib()
+        with torch.cuda.device(out.device):
+            for half in range(2):
+                _lib.check(L.scldm_sde_noise(out[half * B:].data_ptr(), B, e, int(seed) & (2 ** 64 - 1), step, half, cell_offset, total,
+                                             _stream_ptr()), "scldm_sde_noise")
+        return out
+
+    @torch.no_grad()
+    def sample_sde_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
+                       num_steps: int = 250, sampling_method: str = "euler", diffusion_form: str = "sigma", diffusion_norm: float = 1.0,
+                       last_step: str | None = "Mean", last_step_size: float = 0.04, *, seed: int | None = None,
+                       noise: torch.Tensor | None = None, cell_offset: int = 0, cells_total: int | None = None,
+                       return_trajectory: bool = False):
+        """The reference's `Sampler.sample_sde` over `forward_with_cfg`, entirely on device (scldm_sample_sde): Euler-Maruyama / stochastic
+        Heun steps over linspace(0, 1 - last_step_size, num_steps) with diffusion D(t) of `diffusion_form`, then the noise-free
+        `last_step` ("Mean", "Tweedie", "Euler" or None).  `z` is the doubled state cat([z0, z0]) (2B,S,C), `condition` the doubled
+        label dict, `num_steps` grid points.  Returns the final state, or with `return_trajectory` the (num_steps, 2B, S, C) stack of
+        every state the reference's list holds (its last entry is the final state).
+
+        Noise: `noise` (num_steps-1, 2B, S, C) is used as given (one slice per step); otherwise a counter-based generator keyed by `seed`
+        draws it in registers (`seed=None`: one drawn from torch's host generator).  A value depends on (seed, step, global row, column)
+        only: with `cell_offset` / `cells_total` a shard of a larger solve draws exactly the noise the whole solve would have drawn for
+        its cells.  Under graph capture the seed is baked into the captured launches, so a replay repeats its noise.
+        `diffusion_form="SBDM"` and "heun" with `last_step=None` raise ValueError (NaN in the reference under this transport)."""
+        method = str(sampling_method).lower()
+        if method not in _lib.METHODS:
+            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'euler' and 'heun' are")
+        if diffusion_form not in _lib.SDE_FORMS:
+            raise NotImplementedError(f"Diffusion form {diffusion_form} not implemented")
+        if last_step not in _lib.SDE_LAST_STEPS:
+            raise NotImplementedError(f"last_step={last_step!r}: one of {list(_lib.SDE_LAST_STEPS)}")
+        z = _require_cuda_f32("z", z).clone()
+        n = z.shape[0]
+        B = n // 2
+        if n != 2 * B or z.shape[1:] != (self.seq_len, self.n_embed_input):
+            raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+        total = B + cell_offset if cells_total is None else int(cells_total)
+        if cell_offset < 0 or total < cell_offset + B:
+            raise ValueError(f"cells_total ({total}) must cover cell_offset ({cell_offset}) + B ({B})")
+        if noise is not None:
+            noise = _require_cuda_f32("noise", noise)
+            if tuple(noise.shape) != (num_steps - 1, *z.shape):
+                raise ValueError(f"expected noise {(num_steps - 1, *z.shape)}, got {tuple(noise.shape)}")
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = int(seed) & (2 ** 64 - 1)
+        if self.training or not self.fused_shape:
+            # one forward_with_cfg per evaluation over the same updates x' = a_x x + a_v v + a_w w: shapes outside the fused family and
+            # modules left in training mode (as sample_ode_cfg)
+            from .transport import Sampler, create_transport
+            fwd = self._generic_forward_with_cfg if not self.fused_shape else self.forward_with_cfg
+            draws = iter(range(num_steps - 1))
+            draw = lambda x: noise[next(draws)] if noise is not None else self.sde_noise(seed, next(draws), B, cell_offset, total)
+            fn = Sampler(create_transport()).sample_sde(sampling_method=method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm,
+                                                        last_step=last_step, last_step_size=last_step_size, num_steps=num_steps)
+            xs = fn(z, lambda x, t: fwd(x, t.contiguous() if not self.fused_shape else t, condition, cfg_scale), _draw=draw)
+            return torch.stack(xs) if return_trajectory else xs[-1]
+        self._need_null_row("CFG sampling (the unconditional pass)")
+        L, h = self._native()
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+        ws = self._workspace(L, 2 * B + n_pass * B, 1 + n_pass * n_u, 2 * B)
+        traj = torch.empty(num_steps, *z.shape, device=z.device, dtype=torch.float32) if return_trajectory and num_steps >= 2 else None
+        with torch.cuda.device(z.device):
+            rc = L.scldm_sample_sde(h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass, masks,
+                                    scales, num_steps, _lib.METHODS[method], _lib.SDE_FORMS[diffusion_form], float(diffusion_norm),
+                                    _lib.SDE_LAST_STEPS[last_step], float(last_step_size), noise.data_ptr() if noise is not None else None,
+                                    seed, cell_offset, total, traj.data_ptr() if traj is not None else None, self._prec(), ws, _stream_ptr())
+        if rc == -1:    # SCLDM_ERR_SHAPE: the rejected combinations and ranges, with the library's message
+            raise ValueError(L.scldm_last_error().decode())
+        _lib.check(rc, "scldm_sample_sde")
+        del keep
+        return traj if return_trajectory else z
+
     # ------------------------------------------------------------------ bench hook
     def layers_per_launch(self) -> int:
         L, h = self._native()

@@ -19,8 +19,13 @@ def shard_bounds(n: int, rank: int, world: int) -> tuple[int, int]:
 
 @torch.no_grad()
 def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | None, guidance_weight: dict[str, float] | None,
-                   num_steps: int = 101, sampling_method: str = "euler") -> torch.Tensor:
-    """z0 (B,S,C) noise -> final latents (2B,S,C): rows [0,B) unconditional, rows [B,2B) guided (models.py:801-812)."""
+                   num_steps: int = 101, sampling_method: str = "euler", sde: dict | None = None) -> torch.Tensor:
+    """z0 (B,S,C) noise -> final latents (2B,S,C): rows [0,B) unconditional, rows [B,2B) guided (models.py:801-812).
+
+    `sde`: None integrates the ODE (`DiT.sample_ode_cfg`); a dict selects the stochastic sampler instead and holds the keyword arguments
+    of `DiT.sample_sde_cfg` beyond the grid and the method (diffusion_form, diffusion_norm, last_step, last_step_size, seed, noise, and
+    for a shard of a larger solve - the `sample_fn` of `sample_latents_sharded` - cell_offset / cells_total, so that every shard draws
+    the noise the whole solve would have drawn for its cells)."""
     if guidance_weight is not None and condition is not None:
         assert set(guidance_weight.keys()) == set(condition.keys()), (
             f"Guidance weight keys {set(guidance_weight.keys())} must match condition keys {set(condition.keys())}")
@@ -31,17 +36,19 @@ def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | N
                 raise ValueError(f"Condition '{k}' length ({len(v)}) must match batch size ({B})")
     z2 = torch.cat([z0, z0], dim=0)
     cond2 = None if condition is None else {k: torch.cat([v, v], dim=0) for k, v in condition.items()}
+    if sde is not None:
+        return dit.sample_sde_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, **sde)
     return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method)
 
 
 @torch.no_grad()
 def sample_cells(dit, vae, condition, guidance_weight, batch_size: int, genes: torch.Tensor, size_factors: torch.Tensor | None,
                  num_steps: int = 101, sampling_method: str = "euler", z0: torch.Tensor | None = None, draw_counts: bool = True,
-                 size_factor_sampler: "SizeFactorSampler | None" = None, seed: int | None = None):
+                 size_factor_sampler: "SizeFactorSampler | None" = None, seed: int | None = None, sde: dict | None = None):
     """Reference `LatentDiffusion.sample` (models.py:766-819): returns (counts or NB distribution, latents) with
     2*batch_size rows, unconditional first.  Log size factors are either given or drawn on device by a
     `SizeFactorSampler` (models.py:785 -> _sample_log_size_factors).  `seed`: the negative-binomial draw's (default: from torch's
-    host generator)."""
+    host generator).  `sde`: as `sample_latents` (None: the ODE sampler)."""
     if size_factors is None:
         if size_factor_sampler is None:
             raise ValueError("pass size_factors or a size_factor_sampler")
@@ -51,7 +58,7 @@ def sample_cells(dit, vae, condition, guidance_weight, batch_size: int, genes: t
     dev = dit.pos_embed.device
     if z0 is None:
         z0 = torch.randn((batch_size, dit.seq_len, vae.encoder.latent_embedding), device=dev)
-    z = sample_latents(dit, z0, condition, guidance_weight, num_steps, sampling_method)
+    z = sample_latents(dit, z0, condition, guidance_weight, num_steps, sampling_method, sde=sde)
     genes2 = torch.cat([genes, genes], dim=0)
     lib = torch.exp(size_factors).view(-1, 1)
     lib2 = torch.cat([lib, lib], dim=0)

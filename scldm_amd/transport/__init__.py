@@ -1,7 +1,7 @@
 """Flow-matching transport with the reference's API (src/scldm/transport/), Linear path + velocity model.
 
-`create_transport(...)`, `Transport.training_losses`, `Sampler(transport).sample_ode(...)` keep the reference
-signatures (transport/__init__.py:6-12, transport.py:110,324-332).  Differences, by design:
+`create_transport(...)`, `Transport.training_losses`, `Sampler(transport).sample_ode(...)` / `.sample_sde(...)` keep the
+reference signatures (transport/__init__.py:6-12, transport.py:110,269-332).  Differences, by design:
   * only (path_type="Linear", prediction="velocity") exists - the one combination every reference config
     uses (ldm_base.yaml:30-35); anything else raises NotImplementedError;
   * the reference hands stepping to third-party torchdiffeq (integrators.py:111, default dopri5); here the
@@ -73,12 +73,41 @@ class _FlowMatchLoss(torch.autograd.Function):
         return dpred, None
 
 
+SDE_DIFFUSION_FORMS = ("sigma", "linear", "constant", "decreasing", "inccreasing-decreasing")   # (the reference's spelling, path.py:69)
+SDE_LAST_STEPS = (None, "Mean", "Tweedie", "Euler")
+
+
+class LinearPath:
+    """The Linear path x_t = t x1 + (1 - t) x0 (path.py:14-151: alpha_t = t, sigma_t = 1 - t) - the members the SDE sampler reads."""
+
+    def compute_diffusion(self, x, t, form="constant", norm=1.0):
+        """D(t) of path.py:52-77, broadcast against x.  "SBDM" is not offered: under this path it is (1 - t) / t, infinite at the
+        t0 = 0 the sampler starts from; "constant" returns a tensor (the reference's Python float breaks its own `th.sqrt`)."""
+        te = _expand_like(t, x)
+        if form in ("sigma", "linear"):
+            return norm * (1 - te)
+        if form == "constant":
+            return torch.full_like(te, float(norm))
+        if form == "decreasing":
+            return 0.25 * (norm * torch.cos(torch.pi * te) + 1) ** 2
+        if form == "inccreasing-decreasing":
+            return norm * torch.sin(torch.pi * te) ** 2
+        raise NotImplementedError(f"Diffusion form {form} not implemented")
+
+    def get_score_from_velocity(self, velocity, x, t):
+        """score = (alpha/alpha' v - x) / (sigma^2 - alpha/alpha' sigma' sigma) = (t v - x) / (1 - t)  (path.py:79-95)."""
+        te = _expand_like(t, x)
+        sigma = 1 - te
+        return (te * velocity - x) / (sigma ** 2 + te * sigma)
+
+
 class Transport:
     def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps):
         if path_type is not PathType.LINEAR or model_type is not ModelType.VELOCITY:
             raise NotImplementedError("only the Linear path with a velocity model is on the hot path (ldm_base.yaml:30-35)")
         self.model_type, self.path_type, self.loss_type = model_type, path_type, loss_type
         self.train_eps, self.sample_eps = train_eps, sample_eps
+        self.path_sampler = LinearPath()
 
     def check_interval(self, *a, **k):
         return 0, 1  # velocity + Linear integrates over exactly [0, 1] (transport.py:86-90)
@@ -131,6 +160,10 @@ class Transport:
 
         return body_fn
 
+    def get_score(self):
+        """score_fn(x, t, model, **kw) of a velocity model (transport.py:185-202)."""
+        return lambda x, t, model, **kw: self.path_sampler.get_score_from_velocity(model(x, t, **kw), x, t)
+
 
 def create_transport(path_type="Linear", prediction="velocity", loss_weight=None, train_eps=None, sample_eps=None):
     """Same call as scldm.transport.create_transport; eps are forced to 0 for velocity+Linear (transport/__init__.py:55-57)."""
@@ -160,6 +193,7 @@ class Sampler:
     def __init__(self, transport: Transport):
         self.transport = transport
         self.drift = transport.get_drift()
+        self.score = transport.get_score()
 
     def _sample_dopri5(self, num_steps: int, atol: float, rtol: float):
         """Adaptive Dormand-Prince 5(4) - what `torchdiffeq.odeint(method="dopri5")` computes for the reference's default
@@ -308,6 +342,91 @@ class Sampler:
                 out.append(dense_eval(coeff, (next_t - t0) / (t1 - t0)))
             _sample.last_stats = {"evaluations": n_eval_now(), "rejected": len(rejected), "accepted_steps": accepted, "rejected_steps": rejected}
             return torch.stack(out)
+
+        return _sample
+
+    def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
+                   num_steps=250):
+        """Returns fn(init, model, **model_kwargs) -> list of `num_steps` states: the reference's stochastic sampler
+        (transport.py:269-322, integrators.py:7-75) for the Linear path with a velocity model - Euler-Maruyama ("Euler") or stochastic
+        Heun ("Heun") steps over linspace(0, 1 - last_step_size, num_steps), then a noise-free last step ("Mean", "Tweedie", "Euler"
+        or None).  Signature and defaults are the reference's.  Any callable, CPU or GPU tensors; the noise is drawn as the reference
+        draws it (`torch.randn(x.size()).to(x)` once per step, in order), so the same `torch.manual_seed` gives the same stream.
+        One model call per evaluation (the reference makes two identical ones for drift and score), t as a stride-0 (B,) view.
+        A scldm_amd DiT runs the whole solve on device through `DiT.sample_sde_cfg` instead.
+
+        Three corners of the reference return NaN under this transport and raise here: diffusion_form="SBDM" - the DEFAULT - is
+        (1 - t) / t at the t0 = 0 the solve starts from; "Heun" with last_step=None and "Mean" / "Tweedie" with last_step_size=0
+        evaluate the score at t = 1."""
+        method = str(sampling_method).lower()
+        if method not in ("euler", "heun"):
+            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'Euler' and 'Heun' are")
+        if diffusion_form == "SBDM":
+            raise ValueError("diffusion_form='SBDM' (the reference's default) is (1 - t) / t under the Linear path: infinite at the t = 0 the "
+                             f"solve starts from, the reference returns NaN; choose one of {SDE_DIFFUSION_FORMS}")
+        if diffusion_form not in SDE_DIFFUSION_FORMS:
+            raise NotImplementedError(f"Diffusion form {diffusion_form} not implemented")
+        if last_step not in SDE_LAST_STEPS:
+            raise NotImplementedError(f"last_step={last_step!r}: one of {SDE_LAST_STEPS}")
+        if method == "heun" and last_step is None:
+            raise ValueError("sampling_method='Heun' with last_step=None evaluates the score at t = 1 in its final K2 (NaN / inf in the "
+                             "reference); use last_step 'Mean', 'Tweedie' or 'Euler', or sampling_method='Euler'")
+        if last_step is None:
+            last_step_size = 0.0
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (grid points)")
+        if not 0.0 <= last_step_size < 1.0:
+            raise ValueError(f"last_step_size must be in [0, 1), got {last_step_size}")
+        if last_step in ("Mean", "Tweedie") and last_step_size == 0.0:
+            raise ValueError(f"last_step={last_step!r} with last_step_size=0 evaluates the score at t = 1; give a positive last_step_size")
+        path = self.transport.path_sampler
+        t1 = 1 - last_step_size
+        ts = torch.linspace(0, t1, num_steps)
+        dt = ts[1] - ts[0]
+
+        def evaluate(x, tval, model, model_kwargs):
+            """(v, sde drift v + D score) at one time."""
+            tv = torch.as_tensor(tval, dtype=torch.float32).to(x.device).reshape(()).expand(x.shape[0])
+            v = model(x, tv, **model_kwargs)
+            assert v.shape == x.shape, "Output shape from SDE solver must match input shape"
+            D = path.compute_diffusion(x, tv, form=diffusion_form, norm=diffusion_norm)
+            return v, v + D * path.get_score_from_velocity(v, x, tv), tv
+
+        @torch.no_grad()
+        def _sample(init, model, _draw=None, **model_kwargs):
+            # _draw (internal): x -> the step's normals, in place of the host generator (DiT.sample_sde_cfg's per-evaluation route)
+            import contextlib
+            from ..nnets import weights_unchanged
+            x, xs = init, []
+            with contextlib.ExitStack() as stack:
+                for i in range(num_steps - 1):
+                    ti = ts[i]
+                    w = torch.randn(x.size()).to(x) if _draw is None else _draw(x)
+                    dw = w * torch.sqrt(dt)
+                    tv = ti.to(x.device).expand(x.shape[0])
+                    D = path.compute_diffusion(x, tv, form=diffusion_form, norm=diffusion_norm)
+                    if method == "euler":
+                        _, f, _ = evaluate(x, ti, model, model_kwargs)
+                        x = x + f * dt.to(x.device) + torch.sqrt(2 * D) * dw
+                    else:
+                        xhat = x + torch.sqrt(2 * D) * dw
+                        _, k1, _ = evaluate(xhat, ti, model, model_kwargs)
+                        _, k2, _ = evaluate(xhat + dt.to(x.device) * k1, ti + dt, model, model_kwargs)
+                        x = xhat + 0.5 * dt.to(x.device) * (k1 + k2)
+                    if i == 0:    # the first evaluation checked the packed weights against the parameters: the rest of the solve skips that pass
+                        stack.enter_context(weights_unchanged())
+                    xs.append(x)
+                if last_step is not None:
+                    v, f, _ = evaluate(x, torch.tensor(t1, dtype=torch.float32), model, model_kwargs)
+                    if last_step == "Mean":
+                        x = x + f * last_step_size
+                    elif last_step == "Tweedie":      # x / t1 + (1 - t1)^2 / t1 score  =  x + (1 - t1) v
+                        x = x + (1 - t1) * v
+                    else:
+                        x = x + v * last_step_size
+                xs.append(x)
+            assert len(xs) == num_steps, "Samples does not match the number of steps"
+            return xs
 
         return _sample
 
