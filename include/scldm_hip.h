@@ -396,6 +396,43 @@ int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w, const scl
                              const int64_t* const* labels, const float* dout, int n, float* dx, int precision, void* saved,
                              void* ws, void* stream);
 
+/* The input-gradient-only backward: d loss / d x into dx (n,S,Din, required) against the record of the matching train_forward call,
+ * and nothing else - the contract of scldm_dit_train_backward minus `grads`.  No weight-gradient GEMM, no bias / adaLN / embedding /
+ * timestep-MLP gradient is formed (fused base-shape route: a second family of the backward layer kernel that writes d x only; generic
+ * route: the parameter-gradient launches are skipped).  dx has the bits of scldm_dit_train_backward's dx on the same record.  What a
+ * log-likelihood evaluation or an input VJP needs.  fp16: loss-scaled like the training backward (the handle's scale state advances).
+ * Its workspace is smaller on the fused route (no operand-pair or partial buffers); a buffer of that size also serves the
+ * train_forward call that writes the record. */
+size_t scldm_dit_train_workspace_bytes_dx_for(const scldm_dit* h, int n, int precision);
+int scldm_dit_train_backward_dx(scldm_dit* h, const scldm_dit_weights* w, const float* x, const int64_t* const* labels,
+                                const float* dout, int n, float* dx, int precision, void* saved, void* ws, void* stream);
+
+/* Exact log-likelihood of latents under the probability flow (Sampler.sample_ode_likelihood, src/scldm/transport/transport.py:371-430)
+ * over forward_with_cfg, as launches only (no host read).  Capture: with SCLDM_PREC_FP32 / _BF16X3 everything runs on `stream` and
+ * the call can be captured as it is; with bf16 / fp16 operands on the fused base shape every evaluation's scldm_dit_train_forward forks
+ * its weight re-pack onto a side stream, so a captured graph has parallel branches.  fp16: each evaluation's backward runs under the
+ * handle's training loss scale and advances that state; an overflow there is not retried - check logp for non-finite values.  Solver time s runs 0 -> 1 on the grid
+ * s_i = i / n_steps (euler: one evaluation per step; heun: two, the second at s_{i+1}); the model is evaluated at t = 1 - s, the
+ * state moves by -v and delta_logp accumulates logp_grad = eps . (dv/dx)^T eps with one fresh Rademacher probe eps per evaluation
+ * (Hutchinson; the VJP is scldm_dit_train_backward_dx over the 2B + n_pass * B rows of the evaluation).
+ *   z (2B,S,Din): in - the doubled state cat([x, x]) (first B rows: unconditional field, last B: guided field); out - the noise-end
+ *       latents.  Labels / passes as scldm_sample_ode.  16-byte aligned.
+ *   logp (2B): prior_logp(z_end) - delta_logp, prior_logp(z) = -S Din / 2 log 2 pi - sum z^2 / 2.
+ *   probe: NULL (the generator: Philox keyed by (seed, evaluation, half, global cell, column), so a shard [cell_offset,
+ *       cell_offset + B) of cells_total cells draws what the whole solve would), or (n_evaluations, 2B, S Din) values used instead.
+ *   dlogp_traj: NULL, or (n_evaluations, 2B) receiving every logp_grad.
+ *   saved: scldm_dit_train_saved_bytes_for(h, (2 + n_pass) B, precision) bytes; ws: scldm_logp_workspace_bytes bytes.
+ * SCLDM_ERR_SHAPE with nothing launched for n_steps < 1, an unknown method, cells_total < cell_offset + B. */
+size_t scldm_logp_workspace_bytes(const scldm_dit* h, int B, int n_pass, int precision);
+int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                   const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method,
+                   const float* probe, unsigned long long seed, long long cell_offset, long long cells_total, float* logp,
+                   float* dlogp_traj, int precision, void* saved, void* ws, void* stream);
+/* The probe scldm_logp_ode draws at `evaluation` for rows [cell_offset, cell_offset + n_rows_local) of CFG half `half` of a
+ * (2, cells_total, e) state: values in {-1, +1}.  out: device (n_rows_local, e), 16-byte aligned; e % 4 == 0. */
+int scldm_logp_probe(float* out, long long n_rows_local, int e, unsigned long long seed, int evaluation, int half, long long cell_offset,
+                     long long cells_total, void* stream);
+
 /* Flow-matching training step around the model call (Transport.training_losses, src/scldm/transport/transport.py:110-150 with
  * ICPlan.plan, path.py:148-151): the eager reference spends ~20 elementwise launches here per step.
  *   scldm_fm_mix:      xt = t*x1 + (1-t)*x0 (each product and the sum rounded separately, as eager torch does), ut = x1 - x0;

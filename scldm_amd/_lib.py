@@ -160,6 +160,16 @@ def lib() -> C.CDLL:
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.scldm_dit_train_backward.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.POINTER(DitWeights), C.c_void_p, c_void_pp,
                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scldm_dit_train_workspace_bytes_dx_for.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.scldm_dit_train_workspace_bytes_dx_for.restype = C.c_size_t
+    L.scldm_dit_train_backward_dx.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scldm_logp_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.scldm_logp_workspace_bytes.restype = C.c_size_t
+    L.scldm_logp_ode.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                 C.POINTER(C.c_uint32), c_float_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_longlong, C.c_longlong,
+                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scldm_logp_probe.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
     L.scldm_fm_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -228,7 +238,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_train_prepare", "scldm_dit_train_set_grad_events", "scldm_dit_train_forward", "scldm_dit_train_backward", "scldm_fm_mix", "scldm_fm_loss", "scldm_fm_loss_bwd", "scldm_vae_create", "scldm_vae_destroy", "scldm_vae_load_weights", "scldm_vae_refresh_weights", "scldm_vae_kernel_timing_enable", "scldm_vae_kernel_timing",
            "scldm_vae_workspace_bytes", "scldm_vae_encode", "scldm_vae_decode", "scldm_vae_decode_sample", "scldm_vae_train_saved_bytes", "scldm_vae_train_workspace_bytes", "scldm_vae_train_forward", "scldm_vae_train_backward", "scldm_vae_train_forward_ex", "scldm_vae_train_backward_ex", "scldm_vae_train_set_found_inf", "scldm_vae_train_rows_bytes", "scldm_vae_train_backward_ordered", "scldm_nb_loglik", "scldm_nb_loglik_bwd", "scldm_nb_sample", "scldm_tokenize_expressed", "scldm_csr_count", "scldm_csr_fill", "scldm_mmd_workspace_bytes",
            "scldm_mmd_kernel_sum", "scldm_sinkhorn_workspace_bytes", "scldm_wasserstein_sinkhorn", "scldm_eval_workspace_bytes",
-           "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise"]
+           "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise",
+           "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe"]
 
 
 def check(rc: int, what: str) -> None:

@@ -19,10 +19,19 @@
 // instantiation), SCLDM_BWD_OP (OpBF16, or OpFP16 = the reference's TF32 mantissa; its gradients are loss-scaled by the caller,
 // train_api.hip) and SCLDM_BWD_NTT (32-token row tiles per workgroup, below) before each inclusion.  Nothing below depends on the
 // element type beyond OP.
+//
+// SCLDM_BWD_DXONLY (optional, default 0): 1 = the input-gradient-only family (log-likelihood / input VJP): the kernel writes d x and
+// nothing else - no operand-pair stores, no dmod stores (the adaLN vectors depend on t and the labels, not on x) and none of the
+// per-sample reductions in front of them.  Everything on the way to d x keeps its operands and its k order; the values that are no
+// longer stored are still formed (pair_sink below), so that every producer shared with the d x chain compiles to the training
+// instantiation's instructions and d x has its bits.
 #include "bwd_layout.hpp"
 #include "dit_forward.hpp"
 #if !defined(SCLDM_BWD_NS) || !defined(SCLDM_BWD_OP) || !defined(SCLDM_BWD_NTT)
 #error "define SCLDM_BWD_NS, SCLDM_BWD_OP and SCLDM_BWD_NTT before including dit_backward.hpp"
+#endif
+#ifndef SCLDM_BWD_DXONLY
+#define SCLDM_BWD_DXONLY 0
 #endif
 
 namespace scldm {
@@ -37,6 +46,7 @@ using Quad = OP::Quad;
 // reads per k-step on the same weight stream; the record and the gradient keep the 64-token geometry, a workgroup reads its half).
 constexpr int NTT = SCLDM_BWD_NTT, NW = 8, NT = 64 * NW, TM = 32 * NTT, NS = 2 * NTT;
 static_assert(NTT == 1 || NTT == 2, "the record is laid out in 64-token tiles");
+constexpr bool DXONLY = SCLDM_BWD_DXONLY != 0;   // d x only: every store but d x (and what feeds only those stores) is compiled out
 constexpr int PF = 8;   // k-steps of weight-ring run-ahead: one wave gets two MFMAs (64 cycles) out of a fragment, an L2 round trip is ~10 of those
 // Register residency (round 5): the gradient is read once and written once per layer, the record's residual read once.
 // d x_out stays in registers across the SwiGLU chunks, d x_mid from the LayerNorm-2 backward to the LayerNorm-1 backward, x_in from
@@ -127,6 +137,13 @@ __device__ __forceinline__ void pair_store(const PairDst& d, unsigned imm, const
   g_u32x4* gp = (g_u32x4*)(d.base + (d.voff + imm));
   *gp = v;
 }
+// The d x family drops every such store, but keeps the stored VALUE alive up to here: with a consumer gone the compiler selects other
+// instructions for the producers it shared with the d x chain (fp16: v_fma_mixlo_f16 - one rounding from the exact product - in place of
+// a multiply and a conversion - two roundings), and d x would no longer have the training instantiation's bits.
+__device__ __forceinline__ void pair_sink(const u32x4 v) {
+  asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+}
+__device__ __forceinline__ void value_sink(float v) { asm volatile("" ::"v"(v)); }
 // quads q (q0) and q+1 (q1) of a 32-feature tile -> 16 bytes per lane (features f8 + 8*hh .. +7 of the lane's token), stored
 // to the LDS image row and, when g.on, to the same position of the plain global operand array
 __device__ __forceinline__ void put_pair(E* lrow, const PairDst& g, int f8, int hh, const Quad& q0, const Quad& q1) {
@@ -137,6 +154,7 @@ __device__ __forceinline__ void put_pair(E* lrow, const PairDst& g, int f8, int 
   const u32x4 v = u32x4{a.u[0], a.u[1], b.u[0], b.u[1]};
   if (lrow) *reinterpret_cast<u32x4*>(lrow + f8 + 8 * hh) = v;
   if (g.on) pair_store(g, (unsigned)f8 * 2u, v);
+  else if constexpr (SCLDM_BWD_DXONLY != 0) pair_sink(v);
 }
 // a whole accumulator tile (32 features x 32 tokens of token tile tt) -> image columns [col0, col0 + 32) / operand array columns
 // [g's first column, + 32)
@@ -151,6 +169,7 @@ __device__ __forceinline__ void put_tile(const float (&t)[16], E* lrow, const Pa
     const u32x4 v = u32x4{a.u[0], a.u[1], b.u[0], b.u[1]};
     if (lrow) *reinterpret_cast<u32x4*>(lrow + col0 + q * 8 + 8 * hh) = v;
     if (g.on) pair_store(g, (unsigned)(q * 8) * 2u, v);
+    else if constexpr (SCLDM_BWD_DXONLY != 0) pair_sink(v);
   }
 }
 
@@ -280,13 +299,21 @@ __global__ __launch_bounds__(NT, 1) void dit_backward_kernel(const BwdArgs a) {
   static_assert(kBwdChunks * kBwdChunk == 3 * kD, "the hidden operand arrays share the dqkv row pitch");
   auto pair_dst = [&](const E* base, int ld, int tt, int first) {
     const int l = lane_now();
-    return PairDst{uniform_ptr(base + (size_t)(tok0 + tt * 32) * ld + first), (unsigned)opaque(((l & 31) * ld + 8 * (l >> 5)) * 2), true};
+    if constexpr (DXONLY) return PairDst{nullptr, 0u, false};
+    else return PairDst{uniform_ptr(base + (size_t)(tok0 + tt * 32) * ld + first), (unsigned)opaque(((l & 31) * ld + 8 * (l >> 5)) * 2), true};
   };
   // adaLN vector `vec` of the lane's sample, the four features of register quad q
   auto mod4 = [&](const ModE* mb, int tt, int vec, int q) { return OP::load_mod4(mb + tt * 2 * kModBlock + vec * kD + q * 8); };
   // sum over the 16 tokens of each sample of a per-(feature, token) quantity -> dmod[sample][vec][feature]
-  gchar* const p_dmod = uniform_ptr(a.dmod + (size_t)smp0 * a.mod_stride + a.mod_off + fb);
+  gchar* const p_dmod = DXONLY ? nullptr : uniform_ptr(a.dmod + (size_t)smp0 * a.mod_stride + a.mod_off + fb);
   auto dmod_store = [&](const float (&v)[NTT][16], int vec) {
+    if constexpr (DXONLY) {   // no per-sample sums, no store; the summands stay alive (see pair_sink)
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) value_sink(v[tt][r]);
+      return;
+    }
     const int ld = lane_now();
     const unsigned dmod_voff = (unsigned)opaque(((((ld & 31) >> 4)) * a.mod_stride + (ld >> 5) * 4) * 4);
 #pragma unroll

@@ -864,15 +864,25 @@ extern "C" int scldm_dit_train_set_grad_events(scldm_dit* h, void* const* events
   return SCLDM_OK;
 }
 
-extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* g, const float* x,
-                                        const int64_t* const* labels, const float* dout, int n, float* dx_out, int precision,
-                                        void* saved_, void* ws, void* stream_) {
+// dx_only: the input-gradient-only backward (scldm_dit_train_backward_dx) - the same data-gradient chain, kernel for kernel and with
+// the same split-K scratch partition, without any launch that produces only parameter gradients and without the side-stream forks
+// that would carry them; `g` is NULL then and replaced by a table of NULL pointers, which is never written through.
+static int train_backward_impl(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* g, const float* x,
+                               const int64_t* const* labels, const float* dout, int n, float* dx_out, int precision,
+                               void* saved_, void* ws, void* stream_, const bool dx_only) {
   // the gradient-ready events belong to THIS call only: whatever way it returns, none of the raw hipEvent_t handles survives on the
   // handle (the caller may destroy them right after; a later backward without set_grad_events must not record into them)
   struct DropEvents { scldm_dit* h; ~DropEvents() { if (h) h->grad_events.clear(); } } drop_events_scope{h};
   precision = train_precision(h, n, precision);
   TRY(check_common(h, w, n, precision, saved_, ws));
-  if (!g || !x || !dout) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if ((!g && !dx_only) || !x || !dout || (dx_only && !dx_out)) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if (dx_only) {
+    static float* const no_layer[1024] = {};
+    static const scldm_dit_grads no_grads = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             no_layer, no_layer, no_layer, no_layer, no_layer, no_layer, no_layer, no_layer, no_layer, no_layer};
+    if (h->cfg.n_layer > 1024) return fail(SCLDM_ERR_SHAPE, "the input-gradient-only backward supports up to 1024 layers");
+    g = &no_grads;
+  }
   hipStream_t st = (hipStream_t)stream_;
   const scldm_dit_config& cfg = h->cfg;
   const int L = cfg.n_layer, din = cfg.n_embed_input, H = cfg.hidden_dim, kD = cfg.n_embed, kNH = cfg.n_head;
@@ -884,7 +894,32 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   const bool use_fused = fused::eligible(h, n, precision);
   const long T_pad = (long)((n + 3) / 4 * 4) * kS;   // tokens incl. the padding of the last 64-token tile (tile layouts)
   const fused::Record rec = use_fused ? fused::carve_record(h, n, s.layer[0].x_in) : fused::Record{};
-  const fused::Scratch fs = use_fused ? fused::carve_scratch(h, n, reinterpret_cast<char*>(ws) + k.bytes) : fused::Scratch{};
+  const fused::Scratch fs = use_fused ? fused::carve_scratch(h, n, reinterpret_cast<char*>(ws) + k.bytes, dx_only) : fused::Scratch{};
+  if (dx_only && use_fused) {
+    // fused base shape: final layer (d x only) -> the d x layer kernels -> input projection's data gradient.  fp16: the same loss
+    // scaling as the training backward (a power of two chosen on device from max |dout|), un-scaled on dx_out alone.
+    const bool f16_dx = precision == SCLDM_PREC_FP16;
+    if (f16_dx) {
+      TRY(fused::scale_dout(h, dout, (long)T * din, fs, st));
+      dout = fs.dout_s;
+    }
+    if (fused::edge_kernels_available(h)) {
+      TRY(fused::final_backward_dx(h, rec.x + (size_t)L * T_pad * kD, s.mod, dout, w->fin_w, n, fs.dx, st));
+    } else {   // other input widths: the GEMM-based final layer of the training backward, without its weight gradient
+      const int of_dx = L * 6 * kD;
+      TRY(fused::to_plain(rec.x + (size_t)L * T_pad * kD, s.x_last, n, st));
+      TRY(ln_fwd(st, kD, s.x_last, s.mod, (long)mw, of_dx + kD, of_dx, cfg.layernorm_eps, T, s.h_f, s.st_f));
+      TRY(linear_dgrad(st, dout, din, w->fin_w, (int)T, din, kD, k.dh, kD, false, k));
+      TRY(ln_bwd(st, kD, n, k.dh, s.x_last, s.st_f, s.mod, (long)mw, of_dx + kD, of_dx, k.dx, 0, k.dmod));
+      TRY(fused::to_tile(k.dx, fs.dx, n, st));
+    }
+    TRY(fused::backward_join(h, st));
+    TRY(fused::backward_layers_dx(h, s.mod, n, rec, fs, st, precision));
+    TRY(fused::to_plain(fs.dx, k.dx, n, st));
+    TRY(linear_dgrad(st, k.dx, kD, w->in_w, (int)T, kD, din, dx_out, din, false, k));
+    if (f16_dx) TRY(fused::unscale_dx(h, dx_out, (long)T * din, fs, st));
+    return SCLDM_OK;
+  }
   // ---- final layer ----
   const int of = L * 6 * kD;
   const bool edge = use_fused && fused::edge_kernels_available(h);   // both ends of the backward as single kernels on the tile layout
@@ -903,7 +938,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
       TRY(fused::to_plain(rec.x + (size_t)L * T_pad * kD, s.x_last, n, st));
       TRY(ln_fwd(st, kD, s.x_last, s.mod, (long)mw, of + kD, of, cfg.layernorm_eps, T, s.h_f, s.st_f));
     }
-    TRY(linear_wgrad(st, dout, din, s.h_f, kD, (int)T, din, kD, g->fin_w, k, g->fin_b));
+    if (!dx_only) TRY(linear_wgrad(st, dout, din, s.h_f, kD, (int)T, din, kD, g->fin_w, k, g->fin_b));
     TRY(linear_dgrad(st, dout, din, w->fin_w, (int)T, din, kD, k.dh, kD, false, k));
     TRY(ln_bwd(st, kD, n, k.dh, s.x_last, s.st_f, s.mod, (long)mw, of + kD, of, k.dx, 0, k.dmod));
     if (use_fused) TRY(fused::to_tile(k.dx, fs.dx, n, st));
@@ -966,7 +1001,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   hipStream_t sw = st;
   bool side_busy = false;
   auto fork = [&]() -> int {
-    if (!overlap) return SCLDM_OK;
+    if (!overlap || dx_only) return SCLDM_OK;   // (d x only: nothing runs beside the chain)
     side_busy = true;
     return fused::fork_side(h, st, 2, &sw);
   };
@@ -976,6 +1011,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     return fused::join_side(h, st, 2);
   };
   auto wgrad = [&](const float* dyp, int lddy, const float* xs, int ldx, int out_f, int in_f, float* dW, float* db) {
+    if (dx_only) return (int)SCLDM_OK;
     if (batched) {   // recorded; launched with the layer's other weight gradients (wgrad_batch below)
       wj[n_wj++] = WgradJobH{reinterpret_cast<const __bf16*>(dyp), lddy, reinterpret_cast<const __bf16*>(xs), ldx, out_f, in_f, dW, db};
       return (int)SCLDM_OK;
@@ -998,6 +1034,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   // gradient-ready events (scldm_dit_train_set_grad_events): `st` is ordered after every kernel that writes the gradients an event
   // stands for when it is recorded.  Events the route cannot time individually fire at the end of the call.
   auto fire = [&](int kind, int layer) -> int {
+    if (dx_only) return SCLDM_OK;   // (no parameter gradient is produced: nothing to announce)
     if (f16 && kind != SCLDM_GRAD_END) return SCLDM_OK;   // (loss-scaled backward: nothing is final before the un-scaling pass at the end)
     for (auto& e : h->grad_events)
       if (!e.fired && (kind == SCLDM_GRAD_END || (e.kind == kind && (kind == SCLDM_GRAD_LAYER ? e.layer >= layer : e.layer <= layer)))) {
@@ -1094,7 +1131,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
     else TRY(attn_bwd(st, kD, kNH, n, (const float*)a.qkv, k.dao, k.dqkv));
     TRY(fork());
     TRY(wgrad(k.dqkv, 3 * kD, a.h1, kD, 3 * kD, kD, g->attn_w[l], g->attn_b[l]));
-    if (batch_side) {   // the layer's five weight gradients, one launch on the side stream; the chain goes on beside it
+    if (batch_side && !dx_only) {   // the layer's five weight gradients, one launch on the side stream; the chain goes on beside it
       hipStream_t sb = st;
       TRY(fused::fork_side(h, st, 2, &sb));
       TRY(wgrad_batch(sb, wj, n_wj, T, kb.part, kb.part_floats));
@@ -1102,7 +1139,7 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
       n_wj = 0;
     }
     TRY(dgrad(k.dqkv, 3 * kD, w->attn_w[l], wh.attn_w, wt.attn_w, 3 * kD, kD, k.dh, false, g16));
-    if (batched && !batch_side) {   // ... or on the same stream (the next layer overwrites their operands after it)
+    if (batched && !batch_side && !dx_only) {   // ... or on the same stream (the next layer overwrites their operands after it)
       TRY(wgrad_batch(st, wj, n_wj, T, k.part, k.part_floats));
       n_wj = 0;
     }
@@ -1116,6 +1153,10 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   }
   TRY(join_batch());
   TRY(join());
+  if (dx_only) {   // generic route: the input projection's data gradient is all that is left (no conditioning backward)
+    TRY(linear_dgrad(st, k.dx, kD, w->in_w, (int)T, kD, din, dx_out, din, false, k));
+    return SCLDM_OK;
+  }
   if (!use_fused) TRY(fire(SCLDM_GRAD_LAYER, 0));
 
   // ---- input projection + pos_embed ----
@@ -1236,6 +1277,24 @@ extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w
   TRY(fire(SCLDM_GRAD_END, 0));
   h->grad_events.clear();
   return SCLDM_OK;
+}
+
+extern "C" int scldm_dit_train_backward(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* g, const float* x,
+                                        const int64_t* const* labels, const float* dout, int n, float* dx_out, int precision,
+                                        void* saved_, void* ws, void* stream_) {
+  return train_backward_impl(h, w, g, x, labels, dout, n, dx_out, precision, saved_, ws, stream_, false);
+}
+
+extern "C" int scldm_dit_train_backward_dx(scldm_dit* h, const scldm_dit_weights* w, const float* x, const int64_t* const* labels,
+                                           const float* dout, int n, float* dx, int precision, void* saved_, void* ws, void* stream_) {
+  return train_backward_impl(h, w, nullptr, x, labels, dout, n, dx, precision, saved_, ws, stream_, true);
+}
+
+extern "C" size_t scldm_dit_train_workspace_bytes_dx_for(const scldm_dit* h, int n, int precision) {
+  if (!h || n < 1) return 0;
+  precision = train_precision(h, n, precision);
+  const bool f = fused::eligible(h, n, precision);
+  return carve_scratch(h, n, nullptr, f).bytes + (f ? fused::carve_scratch(h, n, nullptr, true).bytes : 0);
 }
 
 extern "C" int scldm_fm_mix(const float* x1, const float* x0, const float* t, float* xt, float* ut, int n, int e, void* stream_) {

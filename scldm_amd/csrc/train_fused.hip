@@ -46,7 +46,6 @@ namespace {
 constexpr int kSplits = 16;         // most token-axis splits of the weight-gradient GEMMs the partial buffer is sized for
 constexpr int kSplitsDefault = 8;   // measured per layer at 1 024 cells: 4 splits 75 us, 8: 57 us, 16: 64 us + a longer reduction (SCLDM_WGRAD_SPLITS)
 constexpr int kHP = kBwdChunks * kBwdChunk;   // padded hidden width of the operand arrays (768)
-constexpr int kOverlapTiles = 160;            // <= this many 64-token tiles (640 cells): weight gradients of layer l beside the backward of layer l - 1
 
 struct Carver {
   char* base;
@@ -577,13 +576,19 @@ static size_t part_floats(const scldm_dit* h) {
   return (size_t)kSplits * (3 * kD * kD + kD * kD + 3 * H * kD + 3 * kD + kD);
 }
 
-Scratch carve_scratch(const scldm_dit* h, int n, void* base) {
+Scratch carve_scratch(const scldm_dit* h, int n, void* base, bool dx_only) {
   const size_t T = (size_t)pad4(n) * 16;
   Carver c{reinterpret_cast<char*>(base)};
-  Scratch s;
+  Scratch s{};
   s.handoff = c.take<float>(T * kD);
   s.dx = c.take<float>(T * kD);
   s.ridx = c.take<int32_t>(n);
+  if (dx_only) {   // the input-gradient-only backward (train_dx.hip): no operand pairs, no partials; the head above is what the forward uses
+    s.dout_s = c.take<float>(T * 32);
+    s.scale = h->d_ls;
+    s.bytes = c.off;
+    return s;
+  }
   const size_t set_off0 = c.off;
   s.e_h1 = c.take<__bf16>(T * kD);
   s.e_dqkv = c.take<__bf16>(T * 3 * kD);
@@ -1036,6 +1041,18 @@ int unscale_grads(scldm_dit* h, const scldm_dit_grads* g, float* dx_out, long dx
   a.state = s.scale;
   a.found_inf = h->found_inf;
   unscale_kernel<<<dim3(a.count, 32), 256, 0, st>>>(a);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+
+int unscale_dx(scldm_dit* h, float* dx_out, long dx_elems, const Scratch& s, hipStream_t st) {
+  UnscaleArgs a{};
+  a.p[0] = dx_out;
+  a.n[0] = (int)dx_elems;
+  a.count = 1;
+  a.state = s.scale;
+  a.found_inf = h->found_inf;
+  unscale_kernel<<<dim3(1, 32), 256, 0, st>>>(a);
   LAUNCH_CHECK();
   return SCLDM_OK;
 }

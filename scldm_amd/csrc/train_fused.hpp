@@ -37,8 +37,12 @@ struct Scratch {
   float* scale;     // fp16 policy: the handle's loss-scale state ([0] S, a power of two decided on device from max |dout|, [1] 1 / S, ...)
   size_t bytes;
 };
-Scratch carve_scratch(const scldm_dit* h, int n, void* base);
+// dx_only: the layout of the input-gradient-only backward - the same head (handoff, dx, ridx: all the forward touches), then dout_s;
+// every other pointer stays NULL
+Scratch carve_scratch(const scldm_dit* h, int n, void* base, bool dx_only = false);
 
+constexpr int kOverlapTiles = 160;   // <= this many 64-token tiles (640 cells): weight gradients of layer l beside the backward of layer l - 1;
+                                     // <= this many 32-token tiles (320 cells): the 32-token-tile backward
 constexpr int kMaxFp16TrainLayers = 16;   // the fp16 backward un-scales every gradient tensor through a by-value pointer table
 bool eligible(const scldm_dit* h, int n, int precision);   // shape, precision (bf16 | fp16) and batch served by the fused path
 
@@ -57,6 +61,12 @@ int to_plain(const float* tile, float* plain, int n, hipStream_t st);
 int backward_layers(scldm_dit* h, const scldm_dit_grads* g, const float* mod, float* dmod, int n, const Record& rec, const Scratch& s,
                     hipStream_t st, int precision);
 
+// Input-gradient-only walk (train_dx.hip; the SCLDM_BWD_DXONLY family of dit_backward.hpp): s.dx as above, nothing else is written -
+// no operand pairs, no dmod, no weight-gradient launches.  d x has the bits of backward_layers' (same operands, same k order).
+int backward_layers_dx(scldm_dit* h, const float* mod, int n, const Record& rec, const Scratch& s, hipStream_t st, int precision);
+// final layer, d x only (tile layout): final_backward without the fin_w / fin_b / adaLN gradients
+int final_backward_dx(scldm_dit* h, const float* x_last, const float* mod, const float* dout, const float* fin_w, int n, float* dx, hipStream_t st);
+
 // The two ends of the backward as single kernels on the tile layout (n_embed_input 8 / 16 / 32):
 //   final_backward: LayerNorm + Linear of the final layer: dx (tile layout), d(shift, scale) into dmod, d fin_w, d fin_b
 //   inproj_backward: d in_w, d in_b and (gpos != NULL) d pos_embed from d x0 (tile layout) and the input latents x
@@ -74,6 +84,7 @@ int join_side(scldm_dit* h, hipStream_t st, int k);
 // the non-finite values it meets (overflow guard: the next scale_dout lowers the scale, h->found_inf lets the optimizer skip the step).
 int scale_dout(scldm_dit* h, const float* dout, long n_elem, const Scratch& s, hipStream_t st);
 int unscale_grads(scldm_dit* h, const scldm_dit_grads* g, float* dx_out, long dx_elems, const Scratch& s, hipStream_t st);
+int unscale_dx(scldm_dit* h, float* dx_out, long dx_elems, const Scratch& s, hipStream_t st);   // the same launch over dx_out alone
 
 // (mod_w, 256) stacked weight gradient + (mod_w) stacked bias gradient -> g->ada_w[l] / ada_b[l] / fin_ada_w / fin_ada_b
 int scatter_ada_grads(scldm_dit* h, const scldm_dit_grads* g, const float* dw_all, const float* db_all, hipStream_t st);

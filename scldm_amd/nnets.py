@@ -131,6 +131,16 @@ class _DiTTrainFn(torch.autograd.Function):
             raise RuntimeError("DiT parameters were modified between forward and backward (the HIP backward reads them live)")
         dout = dout.contiguous().float()
         w, _ = module._weights_struct(params)
+        if ctx.needs_input_grad[1] and not any(ctx.needs_input_grad[5:]):
+            # no parameter needs a gradient (an input VJP: likelihood, inversion, attribution): the input-gradient-only backward - the same
+            # dx bits without the weight-gradient GEMMs, the bias / adaLN / embedding gradients and the buffer that would receive them
+            dx = torch.empty_like(ctx.x)
+            with torch.cuda.device(dout.device):
+                _lib.check(L.scldm_dit_train_backward_dx(h, C.byref(w), ctx.x.data_ptr(), C.cast(ctx.labels, _lib.c_void_pp), dout.data_ptr(), n,
+                                                         dx.data_ptr(), ctx.prec, ctx.saved.data_ptr(), ctx.ws.data_ptr(), _stream_ptr()),
+                           "scldm_dit_train_backward_dx")
+            ctx.saved = ctx.ws = None
+            return (None, dx, None, None, None, *([None] * len(params)))
         pos_i = module._pos_index(params)
         need_pos = ctx.needs_input_grad[5 + pos_i]
         flat = torch.empty(module._grad_numel, dtype=torch.float32, device=dout.device)   # every gradient is a view of this buffer
@@ -671,6 +681,38 @@ class DiT(nn.Module):
         del keep
         return out
 
+    # ------------------------------------------------------------------ input VJP (recording forward + input-gradient-only backward)
+    @torch.no_grad()
+    def input_vjp(self, x: torch.Tensor, t: torch.Tensor, condition: dict[str, torch.Tensor], dout: torch.Tensor):
+        """(out, dx): out = forward(x, t, condition, force_drop_ids=False) and dx = (d out / d x)^T dout, through
+        scldm_dit_train_forward + scldm_dit_train_backward_dx - no parameter gradient is formed.  dx has the bits the training backward
+        returns for the same record.  The labels go through the label handling of `forward`: in eval mode they are used as given
+        (mutually_exclusive with several classes in `condition` keeps the one class `torch.randint` draws, as the reference does);
+        a module left in training mode with the joint strategy still draws its label-dropout mask."""
+        x, t, dout = _require_cuda_f32("x", x).contiguous(), _require_cuda_f32("t", t).contiguous(), _require_cuda_f32("dout", dout).contiguous()
+        n = x.shape[0]
+        if x.shape[1:] != (self.seq_len, self.n_embed_input) or t.shape != (n,) or dout.shape != x.shape:
+            raise ValueError(f"expected x, dout (B,{self.seq_len},{self.n_embed_input}) and t (B,), got {tuple(x.shape)}, {tuple(dout.shape)}, {tuple(t.shape)}")
+        L, h = self._native_handle()
+        labels, keep = self._label_ptrs(condition, n, False)
+        params = tuple(self.parameters())
+        cached = self.__dict__.get("_param_list")
+        if cached is None or len(cached) != len(params) or any(a is not b for a, b in zip(cached, params)):
+            self.__dict__["_param_list"] = params
+            self.__dict__.pop("_wstruct_cache", None)
+        w, _ = self._weights_struct(params)
+        prec = self._prec()
+        saved = torch.empty(L.scldm_dit_train_saved_bytes_for(h, n, prec), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(L.scldm_dit_train_workspace_bytes_dx_for(h, n, prec), dtype=torch.uint8, device=x.device)
+        out, dx = torch.empty_like(x), torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(L.scldm_dit_train_forward(h, C.byref(w), x.data_ptr(), t.data_ptr(), C.cast(labels, _lib.c_void_pp), n, out.data_ptr(),
+                                                 prec, saved.data_ptr(), ws.data_ptr(), _stream_ptr()), "scldm_dit_train_forward")
+            _lib.check(L.scldm_dit_train_backward_dx(h, C.byref(w), x.data_ptr(), C.cast(labels, _lib.c_void_pp), dout.data_ptr(), n,
+                                                     dx.data_ptr(), prec, saved.data_ptr(), ws.data_ptr(), _stream_ptr()), "scldm_dit_train_backward_dx")
+        del keep
+        return out, dx
+
     # ------------------------------------------------------------------ CFG plan shared by forward_with_cfg / sample_ode_cfg
     def _cfg_plan(self, condition, cfg_scale, B: int, dedup: bool):
         """Returns (ulabel_ptrs, n_urows, cell_row_ptr, n_pass, masks, scales, keepalive)."""
@@ -984,6 +1026,95 @@ class DiT(nn.Module):
         _lib.check(rc, "scldm_sample_sde")
         del keep
         return traj if return_trajectory else z
+
+    # ------------------------------------------------------------------ log-likelihood (transport.py:371-430 over forward_with_cfg)
+    def logp_probe(self, seed: int, evaluation: int, B: int, cell_offset: int = 0, cells_total: int | None = None) -> torch.Tensor:
+        """The (2B, S, C) Rademacher probe `log_likelihood_cfg(seed=seed)` draws at `evaluation` for cells [cell_offset, cell_offset + B) of
+        a solve over `cells_total` cells (scldm_logp_probe): a value depends on (seed, evaluation, half, global cell, column) only."""
+        total = B + cell_offset if cells_total is None else cells_total
+        e = self.seq_len * self.n_embed_input
+        out = torch.empty(2 * B, self.seq_len, self.n_embed_input, device=self.pos_embed.device, dtype=torch.float32)
+        L = _lib.lib()
+        with torch.cuda.device(out.device):
+            for half in range(2):
+                rc = L.scldm_logp_probe(out[half * B:].data_ptr(), B, e, int(seed) & (2 ** 64 - 1), evaluation, half, cell_offset, total, _stream_ptr())
+                if rc == -1:
+                    raise ValueError(L.scldm_last_error().decode())
+                _lib.check(rc, "scldm_logp_probe")
+        return out
+
+    def log_likelihood_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
+                           num_steps: int = 50, sampling_method: str = "euler", *, seed: int | None = None, probe: torch.Tensor | None = None,
+                           cell_offset: int = 0, cells_total: int | None = None, return_trace: bool = False):
+        """The reference's `Sampler.sample_ode_likelihood` over `forward_with_cfg` on the fixed grid linspace(0, 1, num_steps)
+        ("euler" / "heun"; `num_steps` grid points as sample_ode_cfg).  `z` is the doubled state cat([x, x]) (2B,S,C) of real latents,
+        `condition` the doubled label dict.  Returns (logp (2B), z_end (2B,S,C)) - first B rows under the unconditional field, last B
+        under the guided field; z_end is the noise-end latent of each row (the inversion).  With `return_trace` a third value: the
+        (n_evaluations, 2B) logp_grad of every evaluation.
+
+        The divergence is estimated with ONE Rademacher probe per evaluation (Hutchinson): logp is an unbiased but noisy estimate - average
+        over seeds for a tighter one.  The guided half integrates the GUIDED field u + sum_p s_p (c_p - u): that is the flow the sampler
+        follows, not a normalised conditional density, unless every scale is 1.
+        Probes: `probe` (n_evaluations, 2B, S, C) is used as given; otherwise a counter-based generator keyed by `seed` draws them on
+        device (`seed=None`: one drawn from torch's host generator), a value depending on (seed, evaluation, half, global cell, column)
+        only - with `cell_offset` / `cells_total` a shard of a larger solve draws what the whole solve would.
+        Fused shape in eval mode: the whole solve is one C call (scldm_logp_ode: recording forward + input-gradient-only backward per
+        evaluation, no host read).  Anything else: the generic `Sampler.sample_ode_likelihood` over differentiable `forward` calls with the
+        same probes."""
+        method = str(sampling_method).lower()
+        if method not in _lib.METHODS:
+            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented on the fixed grid: 'euler' and 'heun' are")
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (grid points)")
+        z = _require_cuda_f32("z", z).clone()
+        n = z.shape[0]
+        B = n // 2
+        if n != 2 * B or z.shape[1:] != (self.seq_len, self.n_embed_input):
+            raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+        total = B + cell_offset if cells_total is None else int(cells_total)
+        if cell_offset < 0 or total < cell_offset + B:
+            raise ValueError(f"cells_total ({total}) must cover cell_offset ({cell_offset}) + B ({B})")
+        n_evals = (num_steps - 1) * (2 if method == "heun" else 1)
+        if probe is not None:
+            probe = _require_cuda_f32("probe", probe).contiguous()
+            if tuple(probe.shape) != (n_evals, *z.shape):
+                raise ValueError(f"expected probe {(n_evals, *z.shape)}, got {tuple(probe.shape)}")
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = int(seed) & (2 ** 64 - 1)
+        self._need_null_row("the likelihood of a CFG field (the unconditional pass)")
+        if self.training or not self.fused_shape:
+            from .transport import Sampler, create_transport
+            draws = iter(range(n_evals))
+            draw = lambda x: probe[next(draws)] if probe is not None else self.logp_probe(seed, next(draws), B, cell_offset, total)
+            fn = Sampler(create_transport()).sample_ode_likelihood(sampling_method=method, num_steps=num_steps)
+            logp, z_end = fn(z, lambda x, t: self._composed_forward_with_cfg(x, t.contiguous(), condition, cfg_scale), _probe=draw)
+            return (logp, z_end, torch.stack(fn.last_trace["logp_grad"])) if return_trace else (logp, z_end)
+        L, h = self._native_handle()
+        params = tuple(self.parameters())
+        cached = self.__dict__.get("_param_list")
+        if cached is None or len(cached) != len(params) or any(a is not b for a, b in zip(cached, params)):
+            self.__dict__["_param_list"] = params
+            self.__dict__.pop("_wstruct_cache", None)
+        w, _ = self._weights_struct(params)
+        prec = self._prec()
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+        N = (2 + n_pass) * B
+        saved = torch.empty(L.scldm_dit_train_saved_bytes_for(h, N, prec), dtype=torch.uint8, device=z.device)
+        ws = torch.empty(L.scldm_logp_workspace_bytes(h, B, n_pass, prec), dtype=torch.uint8, device=z.device)
+        logp = torch.empty(n, dtype=torch.float32, device=z.device)
+        trace = torch.empty(n_evals, n, dtype=torch.float32, device=z.device) if return_trace else None
+        with torch.cuda.device(z.device):
+            rc = L.scldm_logp_ode(h, C.byref(w), z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass,
+                                  masks, scales, num_steps - 1, _lib.METHODS[method], probe.data_ptr() if probe is not None else None, seed,
+                                  cell_offset, total, logp.data_ptr(), trace.data_ptr() if trace is not None else None, prec,
+                                  saved.data_ptr(), ws.data_ptr(), _stream_ptr())
+        if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
+            raise ValueError(L.scldm_last_error().decode())
+        _lib.check(rc, "scldm_logp_ode")
+        del keep
+        return (logp, z, trace) if return_trace else (logp, z)
 
     # ------------------------------------------------------------------ bench hook
     def layers_per_launch(self) -> int:

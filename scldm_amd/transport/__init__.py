@@ -109,6 +109,12 @@ class Transport:
         self.train_eps, self.sample_eps = train_eps, sample_eps
         self.path_sampler = LinearPath()
 
+    def prior_logp(self, z: torch.Tensor) -> torch.Tensor:
+        """Standard multivariate normal log-density of every row of a batched z: -N/2 log 2 pi - sum z^2 / 2 (transport.py:59-67)."""
+        import math
+        n = z[0].numel()
+        return z.new_tensor(-n / 2.0) * math.log(2 * math.pi) - z.pow(2).flatten(1).sum(1) / 2.0
+
     def check_interval(self, *a, **k):
         return 0, 1  # velocity + Linear integrates over exactly [0, 1] (transport.py:86-90)
 
@@ -429,6 +435,75 @@ class Sampler:
             return xs
 
         return _sample
+
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3):
+        """Returns fn(x, model, **model_kwargs) -> (logp, x_end): the reference's likelihood sampler (transport.py:371-430), signature and
+        defaults included.  The augmented state (x, delta_logp) is integrated over solver time s from 0 to 1 with
+
+            d x / d s = -v,   d delta_logp / d s = eps . (d v / d x)^T eps,   v = model(x, 1 - s),
+
+        one fresh Rademacher probe eps per evaluation (Hutchinson's estimator of the divergence: unbiased, noisy), and
+        logp = prior_logp(x_end) - delta_logp.  x_end is the noise-end latent of x (the inversion).  `model` is any differentiable
+        callable (x, t (n,)) -> v; the vector-Jacobian product comes from torch.autograd.grad.  The probe is drawn as the reference
+        draws it (`torch.randint(2, x.size(), dtype=float, device=x.device) * 2 - 1`), or comes from `_probe=` (internal: x -> eps,
+        one call per evaluation, as `_draw=` of sample_sde).  One model call per evaluation (the reference makes a second, identical one).
+        "euler" / "heun" step on this project's fixed grid linspace(0, 1, num_steps) (num_steps grid points; Heun's second evaluation
+        at the next grid point); "dopri5" runs the Dormand-Prince driver of sample_ode on the packed state (n, x[0].numel() + 1) - the
+        reference passes one atol / rtol for both components, i.e. one mixed rms norm over the packed state (parity with torchdiffeq
+        unpinned, as for sample_ode).  After a call `fn.last_trace` = {"t": [...], "logp_grad": [...]} of every evaluation.
+        A scldm_amd DiT runs the fixed-grid solve on device through `DiT.log_likelihood_cfg`."""
+        method = str(sampling_method).lower()
+        if method not in ("euler", "heun", "dopri5"):
+            raise NotImplementedError(f"sampling_method={sampling_method!r}: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are provided")
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (grid points)")
+        drift, transport = self.drift, self.transport
+
+        def _sample_fn(x, model, _probe=None, **model_kwargs):
+            trace = {"t": [], "logp_grad": []}
+
+            def likelihood_drift(xc, s):
+                """(-v, logp_grad) at solver time s (a (n,) tensor): _likelihood_drift of the reference."""
+                eps = (torch.randint(2, xc.size(), dtype=torch.float, device=xc.device) * 2 - 1).to(xc.dtype) if _probe is None else _probe(xc)
+                t = torch.ones_like(s) * (1 - s)
+                with torch.enable_grad():
+                    xr = xc.detach().requires_grad_(True)
+                    v = drift(xr, t, model, **model_kwargs)
+                    grad = torch.autograd.grad(torch.sum(v * eps), xr)[0]
+                lg = torch.sum(grad * eps, dim=tuple(range(1, xc.dim())))
+                trace["t"].append(t.detach())
+                trace["logp_grad"].append(lg.detach())
+                return -v.detach(), lg.detach()
+
+            def at(xc, tval):   # one scalar broadcast to (n,) as a stride-0 view (see sample_ode)
+                return likelihood_drift(xc, torch.full((), float(tval), device=xc.device, dtype=torch.float32).expand(xc.shape[0]))
+
+            x = x.detach()
+            dl = torch.zeros(x.size(0)).to(x)
+            if method == "dopri5":
+                n, shape = x.shape[0], x.shape
+
+                def packed(y, s):
+                    dxv, lg = likelihood_drift(y[:, :-1].reshape(shape), s)
+                    return torch.cat([dxv.reshape(n, -1), lg.reshape(n, 1).to(dxv.dtype)], dim=1)
+
+                y = Sampler(transport)._sample_dopri5(num_steps, atol, rtol)(torch.cat([x.reshape(n, -1), dl.reshape(n, 1)], dim=1), packed)[-1]
+                x, dl = y[:, :-1].reshape(shape), y[:, -1]
+            else:
+                ts = torch.linspace(0.0, 1.0, num_steps)
+                with torch.no_grad():
+                    for i in range(num_steps - 1):
+                        h = float(ts[i + 1] - ts[i])
+                        k1x, k1l = at(x, ts[i])
+                        if method == "euler":
+                            x, dl = x + h * k1x, dl + h * k1l
+                        else:
+                            k2x, k2l = at(x + h * k1x, ts[i + 1])
+                            x, dl = x + (0.5 * h) * (k1x + k2x), dl + (0.5 * h) * (k1l + k2l)
+            _sample_fn.last_trace = trace
+            return transport.prior_logp(x) - dl, x
+
+        return _sample_fn
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-5, rtol=1e-5, reverse=False):
         """Returns fn(x, model, **model_kwargs) -> (num_steps, *x.shape) trajectory; callers take [-1] (models.py:812).
