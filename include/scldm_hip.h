@@ -533,6 +533,10 @@ typedef struct {
   scldm_vae_cross enc_cross, dec_cross;
   const scldm_vae_block* enc_blocks; /* HOST array of n_layer entries */
   const scldm_vae_block* dec_blocks;
+  /* Appended (every offset above is unchanged): decoder_head.ln.weight / .bias (32) of the Gaussian head
+   * (GaussianTransformerLayer, stochastic_layers.py:13-35; `decoder_name: gaussian`).  Both NULL: a negative-binomial head,
+   * as before.  Both given: a Gaussian head - theta must be NULL, head_w is (1,32), head_b is (1). */
+  const float* head_ln_w; const float* head_ln_b;
 } scldm_vae_weights;
 
 int scldm_vae_create(const scldm_vae_config* cfg, scldm_vae** out);
@@ -586,6 +590,21 @@ int scldm_vae_kernel_timing(scldm_vae* h, int kind, int* n_launches, double* tot
 
 /* The same draw from explicit parameter tensors: out[i] ~ NB(mu[i], theta[i]), i < n  (NegativeBinomial(mu, theta).sample()). */
 int scldm_nb_sample(const float* mu, const float* theta, float* out, size_t n, unsigned long long seed, void* stream);
+
+/* TransformerVAE.decode with the Gaussian head (vae.py:82-85; the handle's weights carry head_ln_w / head_ln_b):
+ * mu (B,G) = params(LayerNorm(h_x)), the mean of Normal(mu, 1); library_size plays no part.  The per-gene kernel stores mu itself:
+ * no pass over (B,G) follows it.  The LayerNorm and the 32 -> 1 product of the head are fp32 in every `precision`.  Workspace:
+ * scldm_vae_workspace_bytes.  A handle with a negative-binomial head returns SCLDM_ERR_SHAPE; so do scldm_vae_decode,
+ * scldm_vae_decode_sample and the scldm_vae_train_* entry points on a handle with a Gaussian head (it decodes only). */
+int scldm_vae_decode_gaussian(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* mu, int precision, void* ws,
+                              void* stream);
+/* The same followed by Normal(mu, 1).sample() (models.py:819): out = mu + n with n the standard normal of Philox4x32-10 keyed by
+ * `seed`, counter = element index cell * G + position, drawn in the per-gene kernel's epilogue (mu never reaches HBM).  Equal bit for
+ * bit to scldm_vae_decode_gaussian followed by scldm_normal_sample with the same seed. */
+int scldm_vae_decode_gaussian_sample(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* out,
+                                     unsigned long long seed, int precision, void* ws, void* stream);
+/* out[i] = mu[i] + n_i, i < n: the draw of Normal(mu, 1) from an explicit mean tensor. */
+int scldm_normal_sample(const float* mu, float* out, size_t n, unsigned long long seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * TransformerVAE TRAINING step (BASELINE configs[0]; the reference trains through torch autograd over
@@ -736,6 +755,10 @@ int scldm_eval_count_metrics(const float* pred, int n_pred, const float* truth, 
                              const float* true_div, float target_sum, double* out, float* pcc_per_gene, float* gene_stats,
                              void* ws, void* stream);
 int scldm_log1p_normalize(const float* x, int n, int G, const float* div, float target_sum, float* out, void* stream);
+/* Reconstruction loss of the Gaussian head per cell (models.py:239-245 before .mean()): loss_rows[b] = sum_g (log1p(counts[b,g] /
+ * rowsum_b * target_sum) - mu[b,g])^2, one workgroup per row, fixed-order sums (bit-reproducible); the scaled counts are those of
+ * scldm_log1p_normalize with div = NULL (target_sum <= 0: the counts as they are). */
+int scldm_gaussian_recon_loss(const float* counts, const float* mu, int B, int G, float target_sum, float* loss_rows, void* stream);
 
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the

@@ -59,7 +59,8 @@ class VaeCross(C.Structure):
 class VaeWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("gene_embedding", "inducing_points", "enc_pos_embed", "enc_latent_w", "dec_latent_w",
                                           "theta", "head_w", "head_b")] + \
-               [("enc_cross", VaeCross), ("dec_cross", VaeCross), ("enc_blocks", C.POINTER(VaeBlock)), ("dec_blocks", C.POINTER(VaeBlock))]
+               [("enc_cross", VaeCross), ("dec_cross", VaeCross), ("enc_blocks", C.POINTER(VaeBlock)), ("dec_blocks", C.POINTER(VaeBlock))] + \
+               [("head_ln_w", C.c_void_p), ("head_ln_b", C.c_void_p)]       # appended: decoder_head.ln of the Gaussian head (NULL = NB head)
 
 
 class AdamwLaunch(C.Structure):
@@ -188,6 +189,10 @@ def lib() -> C.CDLL:
                                    C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_vae_decode_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                           C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_vae_decode_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_vae_decode_gaussian_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_int,
+                                                   C.c_void_p, C.c_void_p]
+    L.scldm_normal_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
     L.scldm_vae_train_saved_bytes.argtypes = [C.c_void_p, C.c_int]
     L.scldm_vae_train_saved_bytes.restype = C.c_size_t
     L.scldm_vae_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -227,6 +232,7 @@ def lib() -> C.CDLL:
     L.scldm_eval_count_metrics.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.scldm_log1p_normalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    L.scldm_gaussian_recon_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -239,7 +245,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_vae_workspace_bytes", "scldm_vae_encode", "scldm_vae_decode", "scldm_vae_decode_sample", "scldm_vae_train_saved_bytes", "scldm_vae_train_workspace_bytes", "scldm_vae_train_forward", "scldm_vae_train_backward", "scldm_vae_train_forward_ex", "scldm_vae_train_backward_ex", "scldm_vae_train_set_found_inf", "scldm_vae_train_rows_bytes", "scldm_vae_train_backward_ordered", "scldm_nb_loglik", "scldm_nb_loglik_bwd", "scldm_nb_sample", "scldm_tokenize_expressed", "scldm_csr_count", "scldm_csr_fill", "scldm_mmd_workspace_bytes",
            "scldm_mmd_kernel_sum", "scldm_sinkhorn_workspace_bytes", "scldm_wasserstein_sinkhorn", "scldm_eval_workspace_bytes",
            "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise",
-           "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe"]
+           "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe",
+           "scldm_vae_decode_gaussian", "scldm_vae_decode_gaussian_sample", "scldm_normal_sample", "scldm_gaussian_recon_loss"]
 
 
 def check(rc: int, what: str) -> None:

@@ -1,4 +1,4 @@
-// C ABI of the fused evaluation metrics (include/scldm_hip.h): scldm_eval_count_metrics, scldm_log1p_normalize.
+// C ABI of the fused evaluation metrics (include/scldm_hip.h): scldm_eval_count_metrics, scldm_log1p_normalize, scldm_gaussian_recon_loss.
 #include <hip/hip_runtime.h>
 
 #include "api_common.hpp"
@@ -87,6 +87,14 @@ extern "C" int scldm_log1p_normalize(const float* x, int n, int G, const float* 
   if (!x || !out) return fail(SCLDM_ERR_SHAPE, "null argument");
   if (n < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need n >= 1 and G >= 1 (got %d, %d)", n, G);
   hipLaunchKernelGGL(eval_log1p_normalize_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream_, x, G, div, target_sum, out);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+
+extern "C" int scldm_gaussian_recon_loss(const float* counts, const float* mu, int B, int G, float target_sum, float* loss_rows, void* stream_) {
+  if (!counts || !mu || !loss_rows) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if (B < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B >= 1 and G >= 1 (got %d, %d)", B, G);
+  hipLaunchKernelGGL(gaussian_recon_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, counts, mu, G, target_sum, loss_rows);
   LAUNCH_CHECK();
   return SCLDM_OK;
 }

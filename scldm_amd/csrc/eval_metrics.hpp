@@ -75,6 +75,32 @@ __global__ __launch_bounds__(256) void eval_log1p_normalize_kernel(const float* 
   for (int g = threadIdx.x; g < G; g += 256) orow[g] = eval_log1p(row[g] * s);
 }
 
+// Reconstruction loss of the Gaussian head before .mean() (models.py:239-245 with distributions.py:45-62, sigma = None):
+//   loss_rows[b] = sum_g (log1p(counts[b, g] / rowsum_b * target_sum) - mu[b, g])^2
+// One workgroup per row, two passes over the row (its sum, then the squared error; the second read comes from cache), the
+// scaled counts exactly those of eval_log1p_normalize_kernel (an all-zero row: 0 * inf = NaN, as there and as in the reference).
+// 256 strided fp32 lane sums, then a double tree: one order, bit-reproducible.
+__global__ __launch_bounds__(256) void gaussian_recon_loss_kernel(const float* __restrict__ counts, const float* __restrict__ mu, int G,
+                                                                  float target_sum, float* __restrict__ loss_rows) {
+  __shared__ double sh[256];
+  const float* row = counts + (size_t)blockIdx.x * G;
+  const float* mrow = mu + (size_t)blockIdx.x * G;
+  const bool raw = !(target_sum > 0.f);
+  const float s = raw ? 1.0f : target_sum / (float)eval_block_row_sum(row, G, sh);
+  float acc = 0.f;
+  for (int g = threadIdx.x; g < G; g += 256) {
+    const float d = (raw ? row[g] : eval_log1p(row[g] * s)) - mrow[g];
+    acc = fmaf(d, d, acc);
+  }
+  sh[threadIdx.x] = (double)acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_rows[blockIdx.x] = (float)sh[0];
+}
+
 // Partials: `part` holds 5 planes (mean_u, M2_u, mean_v, M2_v, C_uv) of (plane_rows, G) floats, row = row block.
 // PAIRED: a and b are pred and true with the same n; all five planes and the workgroup's (sum (u-v)^2, zero agreement)
 // pair are written.  !PAIRED: only `a` is read and planes slot, slot + 1 are written (the r2 metrics of two matrices

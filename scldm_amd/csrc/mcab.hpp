@@ -627,6 +627,13 @@ struct DecGeneArgs {
   int G, n_chunks, tiles_per_wave;
   float eps, inv_temp;
 };
+// Gaussian head (stochastic_layers.py:13-35, `decoder_name: gaussian`): mu = params(ln(y + mlp)) written to `logits` as it stands -
+// no softmax over the genes, so no `part` and no finalize pass.  theta_emb / head_w2 / theta / part / inv_temp are unused.
+struct DecGeneGaussArgs : DecGeneArgs {
+  const float* hln_w; const float* hln_b;   // decoder_head.ln (32), (32)
+  unsigned long long seed;                  // draw != 0: out = mu + n, n ~ N(0, 1) of (seed, cell * G + position) (nb_sample.hpp)
+  int draw;
+};
 
 // BF = false: exact-fp32 chain (v_mfma_f32_32x32x2_f32, the parity path).  BF = true: the same chain with bf16 operands
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulate; softmax / LayerNorm / SiLU / logits stay fp32): eight consecutive fp32 steps
@@ -639,8 +646,10 @@ struct DecGeneArgs {
 constexpr int kDecWaves = 8;
 constexpr int kDecThreads = 64 * kDecWaves;
 constexpr int kDecMinWaves = 4;   // waves per SIMD the fp32 instantiation is compiled for
-template <class OP>
-__global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kDecWaves / 2 : 1) : kDecMinWaves) void dec_gene_kernel(const DecGeneArgs a) {   // two workgroups per CU
+// GAUSS: the Gaussian head instead of the NB logit + (max, sum exp) partials; a template parameter, so the NB instantiations keep
+// their instruction streams and their kernel arguments.
+template <class OP, bool GAUSS = false>
+__global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kDecWaves / 2 : 1) : kDecMinWaves) void dec_gene_kernel(const std::conditional_t<GAUSS, DecGeneGaussArgs, DecGeneArgs> a) {   // two workgroups per CU
   constexpr bool BF = McabOp<OP>::k16;
   using H8 = typename McabOp<OP>::Frag;
   constexpr int kWF4 = BF ? 1 : 40 * 64, kKV4 = BF ? 1 : kNI * 16, kWF8 = BF ? 20 * 64 : 1, kKV8 = BF ? 6 * 64 : 1;
@@ -648,7 +657,7 @@ __global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kD
   __shared__ f32x4 KVP[kKV4];   // fp32: this cell's K | V, plain [key][64 floats]
   __shared__ H8 WFh[kWF8];  // 16-bit operands: the 160 fragments, 8 steps per 16-byte fragment
   __shared__ H8 KVh[kKV8];  // 16-bit operands: this cell's 48 K/V fragments
-  __shared__ float VEC[4 * kE];   // ln2_w | ln2_b | head_w | head_w row 1 (unshared theta)
+  __shared__ float VEC[(GAUSS ? 5 : 4) * kE];   // ln2_w | ln2_b | head_w | head_w row 1 (unshared theta); GAUSS: ... | head_w | head ln_w | head ln_b
   __shared__ float RED[kDecWaves][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c32 = lane & 31, hh = lane >> 5;
@@ -675,7 +684,11 @@ __global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kD
       WF[i] = i < 4 * 64 ? reinterpret_cast<const f32x4*>(a.wfrag_cproj_halves)[i] : reinterpret_cast<const f32x4*>(a.wfrag)[i];
     for (int i = tid; i < kNI * 16; i += kDecThreads) KVP[i] = reinterpret_cast<const f32x4*>(a.kvfrag + (size_t)cell * (kNI * 64))[i];
   }
-  if (tid < kE) { VEC[tid] = a.ln2_w[tid]; VEC[kE + tid] = a.ln2_b[tid]; VEC[2 * kE + tid] = a.head_w[tid]; VEC[3 * kE + tid] = a.head_w2 ? a.head_w2[tid] : 0.f; }
+  if constexpr (GAUSS) {
+    if (tid < kE) { VEC[tid] = a.ln2_w[tid]; VEC[kE + tid] = a.ln2_b[tid]; VEC[2 * kE + tid] = a.head_w[tid]; VEC[3 * kE + tid] = a.hln_w[tid]; VEC[4 * kE + tid] = a.hln_b[tid]; }
+  } else {
+    if (tid < kE) { VEC[tid] = a.ln2_w[tid]; VEC[kE + tid] = a.ln2_b[tid]; VEC[2 * kE + tid] = a.head_w[tid]; VEC[3 * kE + tid] = a.head_w2 ? a.head_w2[tid] : 0.f; }
+  }
   __syncthreads();
   // acc += F[steps step0 .. step0+7] (A operand, from LDS) x x[0..7] (B operand, accumulator-order registers)
   auto mm8 = [&](const f32x4* F4, const H8* F8, int step0, const float* x, f32x16 acc) {
@@ -859,6 +872,30 @@ __global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kD
       }
       mo = mm8(WF, WFh, 16 + 16 * kHTiles + 8 * u, hv, mo);
     }
+    if constexpr (GAUSS) {
+      // Gaussian head: mu = w . LN(y + mlp) + b, statistics over the 32 features (16 per lane, the half-waves joined) in fp32 in
+      // every operand policy; every gene stands alone - stored (or drawn from) here, nothing is left for a second pass
+      float yo[16], hs = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { yo[r] = y[r] + mo[r]; hs += yo[r]; }
+      const float hmean = xor32_sum(hs) * (1.0f / kE);
+      float hss = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { yo[r] -= hmean; hss += yo[r] * yo[r]; }
+      const float hrstd = __builtin_amdgcn_rsqf(xor32_sum(hss) * (1.0f / kE) + a.eps);
+      float m = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int f = acc_row(r, hh);
+        m += (yo[r] * hrstd * VEC[3 * kE + f] + VEC[4 * kE + f]) * VEC[2 * kE + f];
+      }
+      m = xor32_sum(m) + hb;
+      if (valid && hh == 0) {
+        const size_t e = (size_t)cell * a.G + gi;
+        a.logits[e] = a.draw ? normal_draw_add(a.seed, e, m) : m;
+      }
+      continue;
+    }
     // NB head: logit = w . (y + mlp) + b
     float lg = 0.f;
 #pragma unroll
@@ -880,6 +917,7 @@ __global__ __launch_bounds__(kDecThreads, McabOp<OP>::k16 ? (kDecWaves >= 8 ? kD
       run_m = nm;
     }
   }
+  if constexpr (GAUSS) return;
   // reduce (max, sum) over the 32 gene lanes of the wave, then over the 4 waves
   float m = run_m, sacc = run_s;
 #pragma unroll
@@ -974,6 +1012,11 @@ __global__ __launch_bounds__(256) void dec_finalize_sample_kernel(float* __restr
 __global__ __launch_bounds__(256) void nb_sample_kernel(const float* __restrict__ mu, const float* __restrict__ theta, float* __restrict__ out,
                                                         size_t n, unsigned long long seed) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = nb_draw(seed, i, mu[i], theta[i]);
+}
+
+// Stand-alone draw of the Gaussian head's Normal(mu, 1) (Normal.sample() on the decode output): the epilogue of dec_gene_kernel<., true>
+__global__ __launch_bounds__(256) void normal_sample_kernel(const float* __restrict__ mu, float* __restrict__ out, size_t n, unsigned long long seed) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = normal_draw_add(seed, i, mu[i]);
 }
 
 // ------------------------------------------------------------------------------------------------

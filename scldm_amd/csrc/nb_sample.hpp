@@ -106,4 +106,15 @@ __device__ __forceinline__ float nb_draw(unsigned long long seed, unsigned long 
   return poisson_draw(g, lam);
 }
 
+// Gaussian head (vae.py:83-85: Normal(mu, 1)): out = mu + n, n = the first Philox::normal() of (seed, element) on a stream index of
+// its own.  The add is kept apart from the Box-Muller product (no fma contraction): the fused epilogue of dec_gene_kernel and
+// normal_sample_kernel then round alike, so decode_sample(seed) == decode().sample(seed) bit for bit.
+__device__ __forceinline__ float normal_draw_add(unsigned long long seed, unsigned long long element, float mu) {
+#pragma clang fp contract(off)
+  Philox g;
+  g.init(seed, element, 0x6a055u);
+  const float n = g.normal();
+  return mu + n;
+}
+
 }  // namespace scldm

@@ -26,7 +26,8 @@ enum : int {
   S_ENC_IND = S_ENC_CP + 32 * 128, S_ENC_POS = S_ENC_IND + 512, S_ENC_LAT = S_ENC_POS + 512,    // (n_lat<=32, 32)
   S_DEC_LAT = S_ENC_LAT + 1024, S_DEC_LN1W = S_DEC_LAT + 1024, S_DEC_LN1B = S_DEC_LN1W + 32,
   S_DEC_KV = S_DEC_LN1B + 32, S_DEC_LN2W = S_DEC_KV + 64 * 32, S_DEC_LN2B = S_DEC_LN2W + 32,
-  S_HEAD_W = S_DEC_LN2B + 32, S_HEAD_B = S_HEAD_W + 32, S_HEAD_W2 = S_HEAD_B + 32, S_TOTAL = S_HEAD_W2 + 32
+  S_HEAD_W = S_DEC_LN2B + 32, S_HEAD_B = S_HEAD_W + 32, S_HEAD_W2 = S_HEAD_B + 32,
+  S_HEAD_LNW = S_HEAD_W2 + 32, S_HEAD_LNB = S_HEAD_LNW + 32, S_TOTAL = S_HEAD_LNB + 32    // decoder_head.ln (Gaussian head)
 };
 
 
@@ -189,6 +190,11 @@ extern "C" int scldm_vae_load_weights(scldm_vae* h, const scldm_vae_weights* w, 
   const scldm_vae_config& c = h->cfg;
   const int H = c.hidden_dim, nl = c.n_embed_latent;
   if (c.positional_encoding && !w->enc_pos_embed) return fail(SCLDM_ERR_SHAPE, "positional_encoding set but enc_pos_embed is NULL");
+  // head kind: decoder_head.ln present = Gaussian head (params is (1, 32), no theta); absent = NB head, theta NULL = unshared (params (2, 32))
+  const bool gauss = w->head_ln_w || w->head_ln_b;
+  if (gauss && (!w->head_ln_w || !w->head_ln_b)) return fail(SCLDM_ERR_SHAPE, "Gaussian head: head_ln_w and head_ln_b must both be given");
+  if (gauss && w->theta) return fail(SCLDM_ERR_SHAPE, "Gaussian head (head_ln_w / head_ln_b given) has no theta: pass theta = NULL");
+  const int head_rows = (gauss || w->theta) ? 1 : 2;
   JobList jl;
   trunk_jobs(jl, h->enc_trunk, w->enc_blocks, c.n_layer, H);
   trunk_jobs(jl, h->dec_trunk, w->dec_blocks, c.n_layer, H);
@@ -198,8 +204,9 @@ extern "C" int scldm_vae_load_weights(scldm_vae* h, const scldm_vae_weights* w, 
   jl.copy(s + S_ENC_PROJ, ec.attn_proj, 1024); jl.copy(s + S_ENC_W1, ec.w1, H * 32); jl.copy(s + S_ENC_W2, ec.w2, H * 32); jl.copy(s + S_ENC_CP, ec.cproj, 32 * H);
   jl.copy(s + S_ENC_IND, w->inducing_points, 512); jl.copy(s + S_ENC_LAT, w->enc_latent_w, nl * 32); jl.copy(s + S_DEC_LAT, w->dec_latent_w, 32 * nl);
   jl.copy(s + S_DEC_LN1W, dc.ln1_w, 32); jl.copy(s + S_DEC_LN1B, dc.ln1_b, 32); jl.copy(s + S_DEC_KV, dc.attn_kv, 64 * 32);
-  jl.copy(s + S_DEC_LN2W, dc.ln2_w, 32); jl.copy(s + S_DEC_LN2B, dc.ln2_b, 32); jl.copy(s + S_HEAD_W, w->head_w, 32); jl.copy(s + S_HEAD_B, w->head_b, w->theta ? 1 : 2);
-  if (!w->theta) jl.copy(s + S_HEAD_W2, w->head_w + 32, 32);   // unshared theta: decoder_head.params is Linear(32, 2) (stochastic_layers.py:94-96)
+  jl.copy(s + S_DEC_LN2W, dc.ln2_w, 32); jl.copy(s + S_DEC_LN2B, dc.ln2_b, 32); jl.copy(s + S_HEAD_W, w->head_w, 32); jl.copy(s + S_HEAD_B, w->head_b, head_rows);
+  if (head_rows == 2) jl.copy(s + S_HEAD_W2, w->head_w + 32, 32);   // unshared theta: decoder_head.params is Linear(32, 2) (stochastic_layers.py:94-96)
+  if (gauss) { jl.copy(s + S_HEAD_LNW, w->head_ln_w, 32); jl.copy(s + S_HEAD_LNB, w->head_ln_b, 32); }   // stochastic_layers.py:24
   if (c.positional_encoding) jl.copy(s + S_ENC_POS, w->enc_pos_embed, 512);
   // MFMA fragments
   float* fc = h->frag_cell;
@@ -224,7 +231,7 @@ extern "C" int scldm_vae_load_weights(scldm_vae* h, const scldm_vae_weights* w, 
     jl.src(cr->cproj, (long long)32 * H);
   }
   jl.src(w->inducing_points, 512); jl.src(w->enc_latent_w, (long long)nl * 32); jl.src(w->dec_latent_w, (long long)32 * nl);
-  jl.src(w->head_w, w->theta ? 32 : 64); jl.src(w->head_b, w->theta ? 1 : 2); jl.src(w->gene_embedding, (long long)(c.n_genes + 1) * 32);
+  jl.src(w->head_w, 32 * head_rows); jl.src(w->head_b, head_rows); jl.src(w->head_ln_w, 32); jl.src(w->head_ln_b, 32); jl.src(w->gene_embedding, (long long)(c.n_genes + 1) * 32);
   if (c.positional_encoding) jl.src(w->enc_pos_embed, 512);
   for (const VaePackJob& j : jl.jobs)
     if (!j.src0 || !j.dst || (j.kind == VJ_W12 && !j.src1)) return fail(SCLDM_ERR_SHAPE, "scldm_vae_load_weights: a weight pointer is NULL");
@@ -236,6 +243,7 @@ extern "C" int scldm_vae_load_weights(scldm_vae* h, const scldm_vae_weights* w, 
   h->q_dln_w = dc.ln1q_w; h->q_dln_b = dc.ln1q_b; h->q_dwq = dc.attn_q;
   h->emb = w->gene_embedding;
   h->theta = w->theta;
+  h->gaussian = gauss;
   if ((rc = scldm_vae_refresh(h, true, st))) return rc;
   h->loaded = true;
   return SCLDM_OK;
@@ -346,6 +354,8 @@ static int vae_decode_impl(scldm_vae* h, const float* z, const int64_t* genes, c
                            float* kv_plain = nullptr) {
   int rc = vae_ready(h);
   if (rc) return rc;
+  if (h->gaussian)
+    return fail(SCLDM_ERR_SHAPE, "this handle holds a Gaussian head (GaussianTransformerLayer): use scldm_vae_decode_gaussian / _gaussian_sample");
   if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_BF16 && precision != SCLDM_PREC_FP16)
     return fail(SCLDM_ERR_SHAPE, "unsupported MCAB precision %d (fp32, bf16, fp16)", precision);
   if (B <= 0 || G <= 0 || !z || !genes || !library_size || !mu || (!theta && !draw) || !ws_) return fail(SCLDM_ERR_SHAPE, "bad argument");
@@ -413,6 +423,66 @@ int scldm_vae_decode_train_fp16(scldm_vae* h, const float* z, const int64_t* gen
 extern "C" int scldm_vae_decode_sample(scldm_vae* h, const float* z, const int64_t* genes, const float* library_size, int B, int G,
                                        float* counts, unsigned long long seed, int precision, void* ws_, void* stream_) {
   return vae_decode_impl(h, z, genes, library_size, B, G, counts, nullptr, true, seed, precision, ws_, stream_);
+}
+
+// TransformerVAE.decode with the Gaussian head: the cell pair kernel as above, then the per-gene kernel stores mu (or mu + n) itself
+static int vae_decode_gauss_impl(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* out, bool draw,
+                                 unsigned long long seed, int precision, void* ws_, void* stream_) {
+  int rc = vae_ready(h);
+  if (rc) return rc;
+  if (!h->gaussian)
+    return fail(SCLDM_ERR_SHAPE, "this handle holds a negative-binomial head (NegativeBinomialTransformerLayer): use scldm_vae_decode / _decode_sample");
+  if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_BF16 && precision != SCLDM_PREC_FP16)
+    return fail(SCLDM_ERR_SHAPE, "unsupported MCAB precision %d (fp32, bf16, fp16)", precision);
+  if (B <= 0 || G <= 0 || !z || !genes || !out || !ws_) return fail(SCLDM_ERR_SHAPE, "bad argument");
+  hipStream_t st = (hipStream_t)stream_;
+  const scldm_vae_config& c = h->cfg;
+  float* kv = (float*)ws_;
+  DecCellArgs d;
+  d.z = z; d.lat_frag = h->frag_cell + F_DEC_LAT; d.trunk = h->dec_trunk;
+  d.ca_ln1_w = h->small + S_DEC_LN1W; d.ca_ln1_b = h->small + S_DEC_LN1B; d.kv_frag = h->frag_cell + F_DEC_KV;
+  d.kvfrag = kv; d.B = B; d.n_lat = c.n_embed_latent; d.n_layer = c.n_layer; d.eps = c.layernorm_eps;
+  {
+    KernelTimer kt(h, SCLDM_VAE_K_DEC_CELL, st);
+    if (precision == SCLDM_PREC_FP16) dec_cell_kernel<OpFP16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
+    else if (precision == SCLDM_PREC_BF16) dec_cell_kernel<OpBF16><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
+    else dec_cell_kernel<OpF32><<<cdiv(B, 2), 64 * kTrunkWaves, 0, st>>>(d);
+  }
+  LAUNCH_CHECK();
+  const int nch = dec_chunks(G);
+  DecGeneGaussArgs g;
+  g.genes = genes; g.emb = h->emb; g.qtab = h->qtab; g.theta_emb = nullptr; g.kvfrag = kv; g.wfrag = h->frag_dec; g.wfrag_cproj_halves = h->frag_dec_halves;
+  g.ln2_w = h->small + S_DEC_LN2W; g.ln2_b = h->small + S_DEC_LN2B; g.head_w = h->small + S_HEAD_W; g.head_b = h->small + S_HEAD_B;
+  g.head_w2 = nullptr; g.logits = out; g.theta = nullptr; g.part = nullptr; g.G = G; g.n_chunks = nch; g.tiles_per_wave = kDecTilesPerWave;
+  g.eps = c.layernorm_eps; g.inv_temp = 1.0f;
+  g.hln_w = h->small + S_HEAD_LNW; g.hln_b = h->small + S_HEAD_LNB; g.seed = seed; g.draw = draw ? 1 : 0;
+  {
+    KernelTimer kt(h, SCLDM_VAE_K_DEC_GENE, st);
+    if (precision == SCLDM_PREC_BF16) dec_gene_kernel<OpBF16, true><<<dim3(nch, B), kDecThreads, 0, st>>>(g);
+    else if (precision == SCLDM_PREC_FP16) dec_gene_kernel<OpFP16, true><<<dim3(nch, B), kDecThreads, 0, st>>>(g);
+    else dec_gene_kernel<OpF32, true><<<dim3(nch, B), kDecThreads, 0, st>>>(g);
+  }
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+
+extern "C" int scldm_vae_decode_gaussian(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* mu, int precision,
+                                         void* ws_, void* stream_) {
+  return vae_decode_gauss_impl(h, z, genes, B, G, mu, false, 0ull, precision, ws_, stream_);
+}
+
+extern "C" int scldm_vae_decode_gaussian_sample(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* out,
+                                                unsigned long long seed, int precision, void* ws_, void* stream_) {
+  return vae_decode_gauss_impl(h, z, genes, B, G, out, true, seed, precision, ws_, stream_);
+}
+
+extern "C" int scldm_normal_sample(const float* mu, float* out, size_t n, unsigned long long seed, void* stream_) {
+  if (!mu || !out) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if (n == 0) return SCLDM_OK;
+  const int grid = (int)std::min<size_t>((n + 255) / 256, 256 * 32);
+  normal_sample_kernel<<<grid, 256, 0, (hipStream_t)stream_>>>(mu, out, n, seed);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
 }
 
 extern "C" int scldm_nb_sample(const float* mu, const float* theta, float* out, size_t n, unsigned long long seed, void* stream_) {

@@ -20,6 +20,7 @@ struct scldm_vae {
   // borrowed (caller-owned, must stay alive): the big tables
   const float* emb;
   const float* theta;
+  bool gaussian;      // Gaussian head (head_ln_w / head_ln_b given): theta is NULL, head_w is (1, 32); the NB entry points refuse it
   // re-pack job table + fingerprint state (scldm_vae_load_weights builds them, scldm_vae_refresh_weights runs them)
   void* d_jobs;                 // device VaePackJob[n_jobs]
   int n_jobs, jobs_cap;

@@ -43,6 +43,11 @@ Saved carve_saved(int B, void* base) {
   return s;
 }
 
+// every training entry refuses a handle that holds the Gaussian head: its LayerNorm breaks the rank-1 form of d(y + mlp) the per-gene
+// backward is built on
+const char* const kGaussNoTrain = "the training kernels are built for the negative-binomial head; this handle holds a Gaussian head "
+                                  "(GaussianTransformerLayer), which decodes only";
+
 // precision of a training step: fp32 (exact), or fp16 (fp16 operands of the per-gene MCAB contractions, forward and backward)
 int check_train_precision(int precision) {
   if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_FP16)
@@ -170,6 +175,7 @@ extern "C" size_t scldm_vae_train_workspace_bytes(const scldm_vae* h, int B, int
 
 extern "C" int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf) {
   if (!h) return fail(SCLDM_ERR_SHAPE, "scldm_vae_train_set_found_inf: null handle");
+  if (h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kGaussNoTrain);
   h->found_inf = found_inf;
   return SCLDM_OK;
 }
@@ -182,6 +188,7 @@ extern "C" int scldm_vae_train_forward_ex(scldm_vae* h, const float* counts_subs
   if (!h || !counts_subset || !genes_subset || !genes || !library_size || !mu || !theta || !z || !saved_ || !ws)
     return fail(SCLDM_ERR_SHAPE, "null argument");
   if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1");
+  if (h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kGaussNoTrain);
   if (h->loaded && !h->theta)
     return fail(SCLDM_ERR_STATE, "the training backward is built for the shared-theta NB head (vae_base.yaml:62); the unshared head decodes only");
   hipStream_t st = (hipStream_t)stream_;
@@ -218,6 +225,7 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
                         int precision, const int32_t* order, const int32_t* seg, int n_entries, void* rows_, void* stream_) {
   int rc = check_train_precision(precision);
   if (rc) return rc;
+  if (h && h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kGaussNoTrain);
   rc = check_train(h, w, B, S, G);
   if (rc) return rc;
   const bool f16 = precision == SCLDM_PREC_FP16;

@@ -1,4 +1,5 @@
-"""Losses with the reference's API (src/scldm/distributions.py): `log_nb_positive` as ONE HIP kernel forward and one backward."""
+"""Losses with the reference's API (src/scldm/distributions.py): `log_nb_positive` as ONE HIP kernel forward and one backward;
+`log_gaussian` and its fused per-cell form for the Gaussian head, `gaussian_recon_loss`."""
 from __future__ import annotations
 
 import torch
@@ -54,3 +55,29 @@ def log_nb_positive(x: torch.Tensor, mu: torch.Tensor, theta: torch.Tensor, eps:
     if x.shape != mu.shape or theta.shape != mu.shape:
         x, mu, theta = torch.broadcast_tensors(x, mu, theta)
     return _LogNB.apply(x, mu, theta, eps)
+
+
+def log_gaussian(x: torch.Tensor, mu: torch.Tensor, sigma: torch.Tensor | None = None, eps: float = 1e-8, log_fn=torch.log) -> torch.Tensor:
+    """Elementwise Gaussian reconstruction term (distributions.py:45-62, same signature and defaults): (x - mu)^2 without `sigma` -
+    what VAE.loss uses for the Gaussian head (models.py:241) - else 0.5 ((x - mu) / (sigma + eps))^2 + log(sigma + eps).  Plain
+    tensor arithmetic on the inputs' device; the loss of a batch in one pass is `gaussian_recon_loss`."""
+    if sigma is None:
+        return (x - mu) ** 2
+    sigma = sigma + eps
+    return 0.5 * torch.pow((x - mu) / sigma, 2) + log_fn(sigma)
+
+
+def gaussian_recon_loss(counts: torch.Tensor, mu: torch.Tensor, target_sum: float = 1e4) -> torch.Tensor:
+    """(B,) fp32: sum_g (log1p(counts / rowsum * target_sum) - mu)^2, i.e. `log_gaussian(y, mu).sum(1)` of models.py:240-241,245 in
+    one HIP pass (scldm_gaussian_recon_loss) that never writes y; `.mean()` of it is the reference's loss.  Fixed-order sums:
+    bit-reproducible.  counts, mu: contiguous fp32 (B, G) CUDA (ROCm) tensors; no CPU path, not differentiable."""
+    if not (isinstance(counts, torch.Tensor) and isinstance(mu, torch.Tensor) and counts.is_cuda and mu.device == counts.device):
+        raise RuntimeError("gaussian_recon_loss runs on the MI355X HIP path; there is no CPU fallback")
+    if counts.dim() != 2 or counts.shape != mu.shape or counts.shape[0] < 1 or counts.shape[1] < 1:
+        raise ValueError(f"expected counts and mu (B, G), got {tuple(counts.shape)} and {tuple(mu.shape)}")
+    counts, mu = counts.detach().contiguous().float(), mu.detach().contiguous().float()
+    out = torch.empty(counts.shape[0], dtype=torch.float32, device=counts.device)
+    with torch.cuda.device(counts.device):
+        _lib.check(_lib.lib().scldm_gaussian_recon_loss(counts.data_ptr(), mu.data_ptr(), counts.shape[0], counts.shape[1], float(target_sum),
+                                                        out.data_ptr(), torch.cuda.current_stream().cuda_stream), "scldm_gaussian_recon_loss")
+    return out

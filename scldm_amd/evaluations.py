@@ -216,10 +216,16 @@ WASSERSTEIN_METRICS = {"wasserstein1_sinkhorn": partial(wasserstein, method="sin
                        "wasserstein2_sinkhorn": partial(wasserstein, method="sinkhorn", power=2)}   # models.py:46-49
 
 
-def reconstruction_metrics(counts_pred: torch.Tensor, counts: torch.Tensor) -> dict:
-    """The metric block of `VAE.shared_step` (models.py:320-331) for the negative-binomial head: both matrices scaled by their own
-    row sums; returns mse, pcc, zeros_accuracy."""
-    m = count_metrics(counts_pred, counts)
+def reconstruction_metrics(counts_pred: torch.Tensor, counts: torch.Tensor, head: str = "nb") -> dict:
+    """The metric block of `VAE.shared_step` (models.py:315-331); returns mse, pcc, zeros_accuracy.  head="nb": `counts_pred` are
+    drawn counts and both matrices are scaled by their own row sums.  head="gaussian": `counts_pred` is the head's mu, used as it
+    is (models.py:316-318) - only the true counts are scaled."""
+    if head == "gaussian":
+        m = count_metrics(counts_pred, normalize_log1p(counts), target_sum=0.0)
+    elif head == "nb":
+        m = count_metrics(counts_pred, counts)
+    else:
+        raise ValueError(f"head must be 'nb' or 'gaussian', got {head!r}")
     return {k: m[k] for k in ("mse", "pcc", "zeros_accuracy")}
 
 

@@ -87,6 +87,9 @@ def generate_cells_stream(dit, vae, batches, guidance_weight, genes: torch.Tenso
     dev = dit.pos_embed.device
     if dev.type != "cuda":
         raise RuntimeError("generate_cells_stream needs the model on a CUDA (ROCm) device; there is no CPU path")
+    if getattr(vae, "gaussian_head", False):
+        raise NotImplementedError("generate_cells_stream assembles CSR count matrices; a Gaussian-head VAE (GaussianTransformerLayer) "
+                                  "decodes dense reals - use sample_cells, which returns them as they are")
     # (normal priority: a lowest-priority HIP stream starves batch i's decode until batch i + 1's ODE has drained, and the host - blocked in
     # finish(i) - then queues batch i + 2 too late: 20.45 against 19.55 ms per batch, profiles/r6_gen_stream_ab.txt)
     side = torch.cuda.Stream(device=dev)

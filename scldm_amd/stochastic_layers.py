@@ -1,8 +1,29 @@
-"""Output head of the VAE with the reference's API (src/scldm/stochastic_layers.py:76-116), shared- and unshared-theta variants."""
+"""Output heads of the VAE with the reference's API: the negative-binomial head (src/scldm/stochastic_layers.py:76-116), shared- and
+unshared-theta variants, and the Gaussian head (stochastic_layers.py:13-35) of the `_gaussian` checkpoints."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+
+class GaussianTransformerLayer(nn.Module):
+    """Parameter container of the reference's Gaussian head (stochastic_layers.py:13-35; vae_base.yaml `decoder_name: gaussian`): `ln`
+    LayerNorm(n_embed) with affine and `params` Linear(n_embed, 1); mu = params(ln(h_x)), computed inside
+    scldm_vae_decode_gaussian (the epilogue of dec_gene_kernel).  TransformerVAE.decode returns Normal(mu, 1) (vae.py:83-85).  The
+    class name is what the reference dispatches on (vae.py:46-47, models.py:238).  Decodes only: there is no training backward for it."""
+
+    def __init__(self, *, n_embed: int | None = None, norm_layer: str = "layernorm", layernorm_eps: float = 1e-8):
+        super().__init__()
+        if n_embed is None:
+            raise ValueError("GaussianTransformerLayer requires n_embed (got None)")
+        if norm_layer != "layernorm":
+            raise NotImplementedError(f"the Gaussian head's kernel normalises with LayerNorm (norm_layer={norm_layer!r})")
+        self.ln = nn.LayerNorm(n_embed, eps=layernorm_eps)
+        self.params = nn.Linear(n_embed, 1, bias=True)
+        self.layernorm_eps = layernorm_eps
+
+    def forward(self, *a, **k):  # pragma: no cover - guard only
+        raise RuntimeError("GaussianTransformerLayer is fused into scldm_amd.vae.TransformerVAE.decode")
 
 
 class NegativeBinomialTransformerLayer(nn.Module):
@@ -66,3 +87,42 @@ class NegativeBinomial(torch.distributions.Distribution):
             _lib.check(_lib.lib().scldm_nb_sample(mu.data_ptr(), theta.data_ptr(), out.data_ptr(), mu.numel(), C.c_uint64(seed),
                                                   torch.cuda.current_stream().cuda_stream), "scldm_nb_sample")
         return out
+
+
+class Normal(torch.distributions.Normal):
+    """The distribution TransformerVAE.decode returns for the Gaussian head (vae.py:85: Normal(mu, ones_like(mu))): torch's Normal
+    with `.mu` and a `sample` that draws on the device, mirroring NegativeBinomial.sample."""
+
+    def __init__(self, mu: torch.Tensor, scale: torch.Tensor | float = 1.0, validate_args=False):
+        self._unit_scale = isinstance(scale, (int, float)) and scale == 1      # (known without reading the device)
+        if isinstance(scale, (int, float)):
+            # a 0-d device tensor made by a fill launch: torch's own broadcast of a Python number is a host-to-device copy, which
+            # makes every decode wait for the stream (measured: 0.2 ms per decode at 512 x 17 002)
+            scale = torch.full((), float(scale), dtype=mu.dtype, device=mu.device)
+        super().__init__(mu, scale, validate_args=validate_args)
+
+    @property
+    def mu(self):
+        return self.loc
+
+    @torch.no_grad()
+    def sample(self, sample_shape=torch.Size(), seed: int | None = None):
+        """mu + scale * n, n ~ N(0, 1) from the HIP kernel behind scldm_normal_sample (Philox4x32-10, Box-Muller; counter = element
+        index, so the result depends on (seed, element) only).  `seed` defaults to a draw from torch's global generator.  With scale 1
+        (what decode builds) this is bit for bit TransformerVAE.decode_sample with the same seed.  Device tensors only."""
+        import ctypes as C
+
+        from . import _lib
+        shape = self._extended_shape(sample_shape)
+        mu = self.loc.expand(shape).contiguous().float()
+        if not mu.is_cuda:
+            raise RuntimeError("Normal.sample draws on the MI355X (scldm_normal_sample); mu must be a CUDA (ROCm) tensor")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
+        unit = self._unit_scale
+        out = torch.empty_like(mu)
+        src = mu if unit else torch.zeros_like(mu)
+        with torch.cuda.device(mu.device):
+            _lib.check(_lib.lib().scldm_normal_sample(src.data_ptr(), out.data_ptr(), mu.numel(), C.c_uint64(seed),
+                                                      torch.cuda.current_stream().cuda_stream), "scldm_normal_sample")
+        return out if unit else mu + self.scale.expand(shape) * out

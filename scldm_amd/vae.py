@@ -11,7 +11,7 @@ from torch._utils import _unflatten_dense_tensors
 from . import _lib
 from .layers import InputTransformerVAE, swiglu_hidden
 from .nnets import Decoder, Encoder, _require_cuda_f32, _stream_ptr
-from .stochastic_layers import NegativeBinomial, NegativeBinomialTransformerLayer
+from .stochastic_layers import GaussianTransformerLayer, NegativeBinomial, NegativeBinomialTransformerLayer, Normal
 
 
 def table_order(genes: torch.Tensor, genes_subset: torch.Tensor, counts_subset: torch.Tensor, n_rows: int):
@@ -137,7 +137,7 @@ class TransformerVAE(nn.Module):
     deterministic: bool = False
     last_table_gradient_mode: str | None = None      # "ordered" / "atomic": the mode of the last backward
 
-    def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer,
+    def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer | GaussianTransformerLayer,
                  input_layer: InputTransformerVAE):
         super().__init__()
         self.encoder = encoder
@@ -158,6 +158,11 @@ class TransformerVAE(nn.Module):
         self._ws = None
         self._keep = None
 
+    @property
+    def gaussian_head(self) -> bool:
+        """The head kind, told as the reference tells it: by the class name (vae.py:46-47,82-83)."""
+        return self.decoder_head.__class__.__name__ == "GaussianTransformerLayer"
+
     # ------------------------------------------------------------------ native handle
     def _native(self):
         L = _lib.lib()
@@ -170,7 +175,7 @@ class TransformerVAE(nn.Module):
                                  n_embed_latent=enc.latent_embedding, n_layer=enc.n_layer, n_head=enc.n_head,
                                  n_head_cross=enc.n_head_cross, hidden_dim=swiglu_hidden(enc.n_embed, enc.multiple_of),
                                  layernorm_eps=enc.layernorm_eps, positional_encoding=int(enc.pos_embed is not None),
-                                 nb_temperature=float(self.decoder_head.t))
+                                 nb_temperature=1.0 if self.gaussian_head else float(self.decoder_head.t))
             h = C.c_void_p()
             with torch.cuda.device(emb.device):
                 _lib.check(L.scldm_vae_create(C.byref(cfg), C.byref(h)), "scldm_vae_create")
@@ -244,13 +249,16 @@ class TransformerVAE(nn.Module):
 
         eb = (_lib.VaeBlock * max(n, 1))(*[block(b) for b in enc.encoder_layers])
         db = (_lib.VaeBlock * max(n, 1))(*[block(b) for b in dec.decoder_layers])
+        head = self.decoder_head
+        gauss = self.gaussian_head      # (no theta table, params (1, 32), and decoder_head.ln in the two appended fields)
         w = _lib.VaeWeights(gene_embedding=dp(self.input_layer.gene_embedding.weight), inducing_points=dp(enc.ca_layer.inducing_points),
                             enc_pos_embed=dp(enc.pos_embed) if enc.pos_embed is not None else None,
                             enc_latent_w=dp(enc.encoder_latent_input[0].weight), dec_latent_w=dp(dec.decoder_latent_input[1].weight),
-                            theta=dp(self.decoder_head.theta.weight) if self.decoder_head.theta is not None else None,   # NULL = unshared theta
-                            head_w=dp(self.decoder_head.params.weight),
-                            head_b=dp(self.decoder_head.params.bias), enc_cross=cross(enc.ca_layer),
-                            dec_cross=cross(dec.decoder_cross_attention), enc_blocks=eb, dec_blocks=db)
+                            theta=dp(head.theta.weight) if not gauss and head.theta is not None else None,   # NULL = unshared theta
+                            head_w=dp(head.params.weight),
+                            head_b=dp(head.params.bias), enc_cross=cross(enc.ca_layer),
+                            dec_cross=cross(dec.decoder_cross_attention), enc_blocks=eb, dec_blocks=db,
+                            head_ln_w=dp(head.ln.weight) if gauss else None, head_ln_b=dp(head.ln.bias) if gauss else None)
         return w, (eb, db)
 
     def _load_weights(self, L):
@@ -327,8 +335,13 @@ class TransformerVAE(nn.Module):
             raise ValueError(f"expected z (B,{self.encoder.latent_dim},{self.encoder.latent_embedding}) and library_size (B,1); got "
                              f"{tuple(z.shape)}, {tuple(library_size.shape)} for genes {tuple(g.shape)}")
         mu = torch.empty(B, G, device=z.device, dtype=torch.float32)
-        theta = torch.empty(B, G, device=z.device, dtype=torch.float32)
         ws = self._workspace(L, B, G)
+        if self.gaussian_head:      # Normal(mu, 1) (vae.py:83-85); library_size is accepted and unused, as in the reference
+            with torch.cuda.device(z.device):
+                _lib.check(L.scldm_vae_decode_gaussian(h, z.data_ptr(), g.data_ptr(), B, G, mu.data_ptr(), _lib.PRECISIONS[self.precision], ws,
+                                                       _stream_ptr()), "scldm_vae_decode_gaussian")
+            return Normal(mu, 1.0)
+        theta = torch.empty(B, G, device=z.device, dtype=torch.float32)
         with torch.cuda.device(z.device):
             _lib.check(L.scldm_vae_decode(h, z.data_ptr(), g.data_ptr(), lib.data_ptr(), B, G, mu.data_ptr(), theta.data_ptr(),
                                           _lib.PRECISIONS[self.precision], ws, _stream_ptr()), "scldm_vae_decode")
@@ -337,7 +350,8 @@ class TransformerVAE(nn.Module):
     @torch.no_grad()
     def decode_sample(self, z: torch.Tensor, genes: torch.Tensor, library_size: torch.Tensor, seed: int | None = None) -> torch.Tensor:
         """`decode(z, genes, library_size).sample()` in one call (models.py:819 after vae.py:71-87): the negative-binomial draw is
-        fused into the decoder's normalisation pass, mu / theta never reach HBM.  Returns counts (B, G) fp32."""
+        fused into the decoder's normalisation pass, mu / theta never reach HBM.  Returns counts (B, G) fp32.  Gaussian head: mu + n
+        from the per-gene kernel's epilogue, bit for bit `decode(...).sample(seed=seed)`."""
         L, h = self._native()
         z = _require_cuda_f32("z", z)
         if not genes.is_cuda:
@@ -352,17 +366,26 @@ class TransformerVAE(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
         counts = torch.empty(B, G, device=z.device, dtype=torch.float32)
         ws = self._workspace(L, B, G)
+        if self.gaussian_head:
+            with torch.cuda.device(z.device):
+                _lib.check(L.scldm_vae_decode_gaussian_sample(h, z.data_ptr(), g.data_ptr(), B, G, counts.data_ptr(), C.c_uint64(seed),
+                                                              _lib.PRECISIONS[self.precision], ws, _stream_ptr()),
+                           "scldm_vae_decode_gaussian_sample")
+            return counts
         with torch.cuda.device(z.device):
             _lib.check(L.scldm_vae_decode_sample(h, z.data_ptr(), g.data_ptr(), lib.data_ptr(), B, G, counts.data_ptr(), C.c_uint64(seed),
                                                  _lib.PRECISIONS[self.precision], ws, _stream_ptr()), "scldm_vae_decode_sample")
         return counts
 
     def forward(self, counts, genes, library_size, counts_subset=None, genes_subset=None):
-        """(params, z) with params = {"mu", "theta"} (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
+        """(params, z) with params = {"mu", "theta"}, or {"mu"} for the Gaussian head (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
         are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
         (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.gaussian_head:
+                raise NotImplementedError("the HIP training backward is built for the negative-binomial head; the Gaussian head "
+                                          "(GaussianTransformerLayer) encodes and decodes only - call forward under torch.no_grad()")
             if counts_subset is None or genes_subset is None:
                 raise ValueError("TransformerVAE.forward needs counts_subset / genes_subset (the reference passes them to the input layer, vae.py:37-40)")
             cs = _require_cuda_f32("counts_subset", counts_subset)
@@ -385,4 +408,6 @@ class TransformerVAE(nn.Module):
         with torch.no_grad():
             z = self.encode(counts, genes, counts_subset, genes_subset)
             nb = self.decode(z, genes, library_size)
+            if self.gaussian_head:
+                return {"mu": nb.mu}, z        # vae.py:47-49
             return {"mu": nb.mu, "theta": nb.theta}, z
