@@ -646,6 +646,14 @@ int scldm_vae_train_backward_ex(scldm_vae* h, const scldm_vae_weights* w, const 
                                 const float* dz, void* saved, void* ws, int precision, void* stream);
 int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf /* device, caller-owned, may be NULL */);
 
+/* How the backward divides its two gene-axis kernels at batch B, S encoder tokens and G decoded genes - host arithmetic, no handle
+ * and no GPU: out = {tiles, chunks} of the per-gene decoder kernel (over G), then {tiles, chunks} of the pooling kernel (over S).
+ * Every cell gets `chunks` workgroups, each walking `tiles` 64-token tiles in one go; the backward launches with exactly these
+ * (about 512 workgroups per kernel, or this process's SCLDM_VAE_GENE_WGS / SCLDM_VAE_POOL_WGS).  For tests and tools that must know
+ * which regime a shape runs in: 1 tile per workgroup up to a few cells, 266 and 97 tiles at G = 17 002, S = 6 147 from batch 257.
+ * B, S or G below 1, or a NULL out: SCLDM_ERR_SHAPE. */
+int scldm_vae_train_split(int B, int S, int G, int out[4]);
+
 /* ORDERED table gradients: scldm_vae_train_backward_ex with the gradients of gene_embedding and theta formed without float atomics.
  * Replaces torch's embedding backward under the autograd of TransformerVAE.forward (src/scldm/vae.py:29-56; the gene-embedding lookups
  * of layers.py:111-118 and the theta lookup of stochastic_layers.py:108-110) when the trainer asks for `deterministic:`

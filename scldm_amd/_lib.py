@@ -208,6 +208,7 @@ def lib() -> C.CDLL:
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.scldm_vae_train_set_found_inf.argtypes = [C.c_void_p, C.c_void_p]
+    L.scldm_vae_train_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.scldm_vae_train_rows_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.scldm_vae_train_rows_bytes.restype = C.c_size_t
     L.scldm_vae_train_backward_ordered.argtypes = L.scldm_vae_train_backward_ex.argtypes[:-1] + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -246,7 +247,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_mmd_kernel_sum", "scldm_sinkhorn_workspace_bytes", "scldm_wasserstein_sinkhorn", "scldm_eval_workspace_bytes",
            "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise",
            "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe",
-           "scldm_vae_decode_gaussian", "scldm_vae_decode_gaussian_sample", "scldm_normal_sample", "scldm_gaussian_recon_loss"]
+           "scldm_vae_decode_gaussian", "scldm_vae_decode_gaussian_sample", "scldm_normal_sample", "scldm_gaussian_recon_loss",
+           "scldm_vae_train_split"]
 
 
 def check(rc: int, what: str) -> None:

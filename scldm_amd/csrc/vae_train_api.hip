@@ -32,6 +32,20 @@ void split_tiles(int n_tok, int B, int* tiles, int* chunks, int wgs) {
   *chunks = cdiv(per_cell, *tiles);
 }
 
+// the split of both kernels at batch B, S encoder tokens and G decoded genes: what carve_ws launches with and scldm_vae_train_split
+// reports (the workgroups are four waves, two per CU: one full round of 512 measured best at batch 32 - per-gene kernel
+// 606 us against 633-645 us with 1 024-4 096 workgroups, pooling 123 us against 130-138 us - and equal at batch 512;
+// SCLDM_VAE_GENE_WGS / SCLDM_VAE_POOL_WGS override the target counts)
+struct Split { int tilesD, chunksD, tilesE, chunksE; };
+Split train_split(int B, int S, int G) {
+  static const int wgs_d = [] { const char* e = getenv("SCLDM_VAE_GENE_WGS"); return e ? atoi(e) : 512; }();
+  static const int wgs_e = [] { const char* e = getenv("SCLDM_VAE_POOL_WGS"); return e ? atoi(e) : 512; }();
+  Split s;
+  split_tiles(G, B, &s.tilesD, &s.chunksD, wgs_d);
+  split_tiles(S, B, &s.tilesE, &s.chunksE, wgs_e);
+  return s;
+}
+
 struct Saved { float *pooled, *lse2, *kv; size_t bytes; };
 Saved carve_saved(int B, void* base) {
   Carver c{reinterpret_cast<char*>(base)};
@@ -65,13 +79,8 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   const int L = c.n_layer;
   Carver k{reinterpret_cast<char*>(base)};
   Ws w;
-  // (the workgroups are four waves, two per CU: one full round of 512 measured best at batch 32 - per-gene kernel
-  // 606 us against 633-645 us with 1 024-4 096 workgroups, pooling 123 us against 130-138 us - and equal at batch 512;
-  // SCLDM_VAE_GENE_WGS / SCLDM_VAE_POOL_WGS override the target counts)
-  static const int wgs_d = [] { const char* e = getenv("SCLDM_VAE_GENE_WGS"); return e ? atoi(e) : 512; }();
-  static const int wgs_e = [] { const char* e = getenv("SCLDM_VAE_POOL_WGS"); return e ? atoi(e) : 512; }();
-  split_tiles(G, B, &w.tilesD, &w.chunksD, wgs_d);
-  split_tiles(S, B, &w.tilesE, &w.chunksE, wgs_e);
+  const Split sp = train_split(B, S, G);
+  w.tilesD = sp.tilesD; w.chunksD = sp.chunksD; w.tilesE = sp.tilesE; w.chunksE = sp.chunksE;
   w.wct = k.take((size_t)(2 + 2 * L) * kHP * 32);
   w.Q = k.take(512);
   w.dQ = k.take(512);
@@ -171,6 +180,14 @@ extern "C" size_t scldm_vae_train_workspace_bytes(const scldm_vae* h, int B, int
   if (!h || B < 1 || S < 1 || G < 1) return 0;
   // the forward borrows the inference workspace layout; the backward carves its own
   return std::max(carve_ws(h, B, S, G, nullptr).bytes, scldm_vae_workspace_bytes(h, B, G));
+}
+
+extern "C" int scldm_vae_train_split(int B, int S, int G, int out[4]) {
+  if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1 (got %d, %d, %d)", B, S, G);
+  if (!out) return fail(SCLDM_ERR_SHAPE, "scldm_vae_train_split: null output");
+  const Split s = train_split(B, S, G);
+  out[0] = s.tilesD; out[1] = s.chunksD; out[2] = s.tilesE; out[3] = s.chunksE;
+  return SCLDM_OK;
 }
 
 extern "C" int scldm_vae_train_set_found_inf(scldm_vae* h, float* found_inf) {

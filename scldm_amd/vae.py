@@ -38,6 +38,15 @@ def table_order(genes: torch.Tensor, genes_subset: torch.Tensor, counts_subset: 
     return order, seg
 
 
+def train_split(B: int, S: int, G: int):
+    """((tiles, chunks) of the per-gene decoder backward, (tiles, chunks) of the pooling backward) at batch B, S encoder tokens and G
+    decoded genes: every cell gets `chunks` workgroups, each walking `tiles` 64-token tiles (scldm_vae_train_split: the split the
+    training backward launches with in this process; host arithmetic, no GPU)."""
+    out = (C.c_int * 4)()
+    _lib.check(_lib.lib().scldm_vae_train_split(B, S, G, out), "scldm_vae_train_split")
+    return (out[0], out[1]), (out[2], out[3])
+
+
 class _VAETrainFn(torch.autograd.Function):
     """TransformerVAE.forward with a HIP backward (scldm_vae_train_forward / _backward, include/scldm_hip.h): replaces torch
     autograd over the reference's module tree (vae.py:29-56) inside VAE.training_step (models.py:249-290).  Outputs mu, theta

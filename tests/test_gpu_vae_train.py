@@ -143,7 +143,9 @@ def test_fused_log_nb_positive_matches_the_reference_formula_and_its_autograd():
 
 
 def test_training_loop_at_the_dentate_shape_reduces_the_loss():
-    """BASELINE configs[0] shape: batch 32, G = 17 002 decoded genes, S = 6 147 encoder tokens; 20 AdamW steps on a fixed batch."""
+    """BASELINE configs[0] shape: batch 32, G = 17 002 decoded genes, S = 6 147 encoder tokens; 20 AdamW steps on a fixed batch.
+    (Workgroups walk 17 and 7 tiles here, but only the loss is looked at; the values of a multi-tile walk are compared with the
+    oracle in test_gpu_vae_train_multitile.py.)"""
     G, S, B, n_genes = 17002, 6147, 32, 17002
     vae, sd, cfg = build(n_genes, 401)
     with torch.no_grad():   # a realistic starting point: embeddings O(1), theta table at its reference init (ones)

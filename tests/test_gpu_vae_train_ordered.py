@@ -7,7 +7,9 @@ atomics.
   4. the switches; 5. the fp16 overflow flag.
 The oracle comparison of (3) is made for the fp32 step only: 1e-4 is the project's gate for exact-fp32 arithmetic, which fp16 operands
 (10 mantissa bits, errors near 1e-3) cannot meet in either mode; the fp16 ordered step is pinned to the fp16 atomic one in (2) - bit
-equal outside the two tables - whose accuracy test_gpu_vae_train_fp16.py gates against the TF32-operand oracle."""
+equal outside the two tables - whose accuracy test_gpu_vae_train_fp16.py gates against the TF32-operand oracle.
+All shapes here give every workgroup of the gene-axis kernels one 64-token tile; the row buffers of workgroups that walk several
+tiles (the bench and production splits) are checked in test_gpu_vae_train_multitile.py."""
 import numpy as np
 import pytest
 import torch
@@ -123,8 +125,9 @@ def collide_case(case):
 @pytest.mark.parametrize("case", ["a", "b", "c", "d"])
 def test_four_runs_are_bit_equal_where_the_atomics_collide(case, prec):
     """(a) 13 table rows hit hundreds of times each, genes repeated inside cells, 37 cells (no whole four-cell wave); (b) several
-    64-gene tiles and chunks per cell with a ragged last tile; (c) one cell, one gene, one token; (d) a fifth of the encoder tokens
-    with zero counts (left out of the index).  Default two-stream overlap."""
+    chunks per cell, one 64-gene tile each (16 decoder and 5 pooling workgroups per cell), with a ragged last tile; (c) one cell, one
+    gene, one token; (d) a fifth of the encoder tokens with zero counts (left out of the index).  Default two-stream overlap.  Every
+    workgroup here walks ONE tile; workgroups that walk several are in test_gpu_vae_train_multitile.py."""
     vae, sd, cfg, inputs, zw = collide_case(case)
     first, loss, params, z = grads(vae, inputs, prec, True, zw)
     for run in range(3):
