@@ -407,6 +407,40 @@ size_t scldm_dit_train_workspace_bytes_dx_for(const scldm_dit* h, int n, int pre
 int scldm_dit_train_backward_dx(scldm_dit* h, const scldm_dit_weights* w, const float* x, const int64_t* const* labels,
                                 const float* dout, int n, float* dx, int precision, void* saved, void* ws, void* stream);
 
+/* Record-free inference and sampling of the shapes outside the fused family (handles the fused entry points refuse: n_embed % 256 == 0,
+ * seq_len 16, head_dim 32 or 64, e.g. a 1 024-wide DiT-L): conditioning rows -> trunk over a row index -> CFG blend + state update, the
+ * three layers of scldm_dit_cond_rows / scldm_dit_forward_rows / scldm_dit_forward_cfg / scldm_sample_ode over the kernels of
+ * scldm_dit_train_forward.  They read the live parameters `w` like the training entry points (nothing is loaded into the handle),
+ * take the precisions scldm_dit_train_forward takes on such a handle (fp32, bf16; bf16x3 / fp16 are served by the fp32 route) and keep
+ * no activation record: the workspace holds ONE layer's arrays, n_rows conditioning rows and the split-K partials, whatever n_layer is.
+ * The bf16 policy's weight mirror (allocated inside the handle on first use) is refreshed from `w` once per call, not once per
+ * evaluation; apart from that mirror no call allocates.  n_direct, rep, row_index, ulabels, n_urows, cell_row, pass_mask, pass_scale,
+ * n_steps and method mean what their fused namesakes document above.  A fused-family handle, a rejected argument (n_steps < 1, an
+ * unknown method or t_stride, a NULL pointer, a class without its null row): SCLDM_ERR_SHAPE with a message, nothing launched.
+ *
+ * Bits: with one conditioning row per sample-forward (row_index NULL = identity) and the same n, scldm_dit_infer_cond_rows(t_stride 1)
+ * + scldm_dit_infer_forward_rows return what scldm_dit_train_forward returns (same kernels, operands and split-K choices).
+ *
+ * scldm_dit_infer_workspace_bytes(h, n_fwd, n_rows, n_state, precision): bytes for calls over up to n_fwd sample-forwards, n_rows
+ *   conditioning rows and an ODE state of n_state samples.  n_fwd == 0 sizes scldm_dit_infer_cond_rows alone (it writes to mod_out).
+ * scldm_dit_infer_cond_rows: t (n_rows) with t_stride 1, or one device float with t_stride 0 (its timestep embedding is formed once
+ *   and shared by the rows); labels[c] (n_rows) int64 or NULL = the null token; mod_out (n_rows, mod_width).
+ * scldm_dit_infer_forward_rows: x (n_direct, S, Din); sample-forwards beyond n_direct re-read the last `rep` latents;
+ *   mod (rows, mod_width); row_index (n_fwd) int32 or NULL = sample-forward s reads row s; out (n_fwd, S, Din).
+ * scldm_dit_infer_forward_cfg: scldm_dit_forward_cfg with t_stride 0 (one device float) or 1 (t (2B), per-cell label rows).
+ * scldm_dit_infer_sample_ode: scldm_sample_ode; z (2B, S, Din) is updated in place. */
+size_t scldm_dit_infer_workspace_bytes(const scldm_dit* h, int n_fwd, int n_rows, int n_state, int precision);
+int scldm_dit_infer_cond_rows(scldm_dit* h, const scldm_dit_weights* w, const float* t, int t_stride, const int64_t* const* labels,
+                              int n_rows, float* mod_out, int precision, void* ws, void* stream);
+int scldm_dit_infer_forward_rows(scldm_dit* h, const scldm_dit_weights* w, const float* x, int n_direct, int rep, int n_fwd,
+                                 const float* mod, const int32_t* row_index, float* out, int precision, void* ws, void* stream);
+int scldm_dit_infer_forward_cfg(scldm_dit* h, const scldm_dit_weights* w, const float* x, const float* t, int t_stride,
+                                const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                                const uint32_t* pass_mask, const float* pass_scale, float* out, int precision, void* ws, void* stream);
+int scldm_dit_infer_sample_ode(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                               const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale,
+                               int n_steps, int method, int precision, void* ws, void* stream);
+
 /* Exact log-likelihood of latents under the probability flow (Sampler.sample_ode_likelihood, src/scldm/transport/transport.py:371-430)
  * over forward_with_cfg, as launches only (no host read).  Capture: with SCLDM_PREC_FP32 / _BF16X3 everything runs on `stream` and
  * the call can be captured as it is; with bf16 / fp16 operands on the fused base shape every evaluation's scldm_dit_train_forward forks

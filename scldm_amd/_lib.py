@@ -170,6 +170,17 @@ def lib() -> C.CDLL:
     L.scldm_logp_ode.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                  C.POINTER(C.c_uint32), c_float_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_longlong, C.c_longlong,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    # record-free inference of the shapes outside the fused family (the fused entries' arguments with the live weight struct in front)
+    L.scldm_dit_infer_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.scldm_dit_infer_workspace_bytes.restype = C.c_size_t
+    L.scldm_dit_infer_cond_rows.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, C.c_int, c_void_pp, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p]
+    L.scldm_dit_infer_forward_rows.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_dit_infer_forward_cfg.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, C.c_void_p, C.c_int, c_void_pp, C.c_int, C.c_void_p,
+                                              C.c_int, C.c_int, C.POINTER(C.c_uint32), c_float_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_dit_infer_sample_ode.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                             C.POINTER(C.c_uint32), c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_logp_probe.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
     L.scldm_fm_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -248,7 +259,9 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_eval_count_metrics", "scldm_log1p_normalize", "scldm_sample_sde", "scldm_sde_noise",
            "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe",
            "scldm_vae_decode_gaussian", "scldm_vae_decode_gaussian_sample", "scldm_normal_sample", "scldm_gaussian_recon_loss",
-           "scldm_vae_train_split"]
+           "scldm_vae_train_split",
+           "scldm_dit_infer_workspace_bytes", "scldm_dit_infer_cond_rows", "scldm_dit_infer_forward_rows", "scldm_dit_infer_forward_cfg",
+           "scldm_dit_infer_sample_ode"]
 
 
 def check(rc: int, what: str) -> None:

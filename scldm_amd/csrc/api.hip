@@ -191,7 +191,7 @@ extern "C" void scldm_dit_destroy(scldm_dit* h) {
     if (h->wfinal[p]) (void)hipFree(h->wfinal[p]);
   }
   void* ptrs[] = {h->ada_x3, h->w0t, h->b0, h->w2t, h->b2, h->emb, h->ada_t, h->ada_b, h->in_wt, h->in_w, h->in_b, h->pos, h->fin_b, h->b_qkv,
-                  h->b_proj, h->label_err, h->d_plan, h->d_ls, h->d_fp16_stats, h->d_jobs, h->d_fp_src, h->d_fp_state, h->d_dirty, h->bwd_stream, h->d_tjobs, h->iota, h->w16, h->wt16, h->d_cast_jobs, h->ada16, h->ada_ball};
+                  h->b_proj, h->label_err, h->d_plan, h->d_ls, h->d_fp16_stats, h->d_jobs, h->d_fp_src, h->d_fp_state, h->d_dirty, h->bwd_stream, h->d_tjobs, h->iota, h->w16, h->wt16, h->d_cast_jobs, h->ada16, h->ada_ball, h->d_infer_jobs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : h->ev) (void)hipEventDestroy(ev);
@@ -718,7 +718,7 @@ static int check_ready(const scldm_dit* h, int prec) {
   if (!h) return fail(SCLDM_ERR_SHAPE, "null handle");
   if (!h->loaded) return fail(SCLDM_ERR_STATE, "scldm_dit_load_weights has not been called");
   if (prec != SCLDM_PREC_FP32 && prec != SCLDM_PREC_BF16 && prec != SCLDM_PREC_BF16X3 && prec != SCLDM_PREC_FP16) return fail(SCLDM_ERR_SHAPE, "unknown precision %d", prec);
-  if (!h->fused) return fail(SCLDM_ERR_SHAPE, "this handle's shape is outside the fused family (scldm_dit_train_* only)");
+  if (!h->fused) return fail(SCLDM_ERR_SHAPE, "this handle's shape is outside the fused family (scldm_dit_train_* and scldm_dit_infer_* serve it)");
   return SCLDM_OK;
 }
 
@@ -877,6 +877,37 @@ static int cfg_eval(scldm_dit* h, const CfgPlan& pl, const float* z, const float
   int rc = cfg_cond(h, pl, t_dev, t_stride, w, prec, st, temb_pre);
   if (rc) return rc;
   return cfg_trunk(h, pl, z, w, dz, prec, st, euler_z, euler_h);
+}
+
+// host launchers of the CFG / ODE kernels for the record-free inference path of wide shapes (train_api.hip; dit_handle.hpp)
+int scldm_cfg_fill_row_index(int32_t* ri, const int32_t* cell_row, int n_direct, int uncond_rows, int B, int U, int P, hipStream_t st) {
+  fill_cfg_row_index_kernel<<<cdiv(n_direct + P * B, 256), 256, 0, st>>>(ri, cell_row, n_direct, uncond_rows, B, U, P);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+int scldm_cfg_blend(const float* v, float* dz, int B, int e, int P, const float* scale, float* euler_z, float euler_h, hipStream_t st) {
+  CfgArgs ca;
+  ca.v = v;
+  ca.dz = dz;
+  ca.B = B;
+  ca.e = e;
+  ca.P = P;
+  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) ca.scale[p] = p < P ? scale[p] : 0.f;
+  ca.z = euler_z;
+  ca.hstep = euler_h;
+  cfg_blend_kernel<<<cdiv((size_t)2 * B * e, 256), 256, 0, st>>>(ca);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+int scldm_ode_axpy(const float* z, const float* k, float* out, float hstep, size_t n, hipStream_t st) {
+  axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, k, out, hstep, n);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+int scldm_ode_heun(float* z, const float* k1, const float* k2, float half_h, size_t n, hipStream_t st) {
+  heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, k1, k2, half_h, n);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
 }
 
 static int make_plan(scldm_dit* h, CfgPlan& pl, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B,

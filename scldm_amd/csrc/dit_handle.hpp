@@ -92,6 +92,11 @@ struct scldm_dit {
   void* d_cast_jobs;        // device CastJob table (rebuilt when the weights' device pointers change)
   int n_cast_jobs;
   std::vector<const void*> w16_key;
+  // record-free inference of the same shapes (scldm_dit_infer_*): its own cast-job table over the same mirror, without the transposed
+  // copies - a training step and a sampling call alternate without re-uploading either table
+  void* d_infer_jobs;
+  int n_infer_jobs;
+  std::vector<const void*> infer_key;
   // gradient-ready events of the NEXT scldm_dit_train_backward (scldm_dit_train_set_grad_events): recorded on the call's stream
   struct GradEvent { hipEvent_t ev; int kind, layer; bool fired; };
   std::vector<GradEvent> grad_events;
@@ -102,3 +107,10 @@ struct scldm_dit {
 // api.hip internals shared with train_fused.hip
 int scldm_build_pack_tables(scldm_dit* h, const scldm_dit_weights* w, hipStream_t st);   // (re)builds the device job tables if `w` changed
 int scldm_run_pack(scldm_dit* h, bool force, unsigned prec_mask, hipStream_t st);
+
+// api.hip's CFG / fixed-grid ODE kernels, launched for train_api.hip's record-free inference path (they depend only on the
+// (2B, 16, n_embed_input) state; arguments as fill_cfg_row_index_kernel, cfg_blend_kernel, axpy_kernel and heun_kernel document them)
+int scldm_cfg_fill_row_index(int32_t* ri, const int32_t* cell_row, int n_direct, int uncond_rows, int B, int U, int P, hipStream_t st);
+int scldm_cfg_blend(const float* v, float* dz, int B, int e, int P, const float* scale, float* euler_z, float euler_h, hipStream_t st);
+int scldm_ode_axpy(const float* z, const float* k, float* out, float hstep, size_t n, hipStream_t st);
+int scldm_ode_heun(float* z, const float* k1, const float* k2, float half_h, size_t n, hipStream_t st);

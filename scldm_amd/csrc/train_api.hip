@@ -12,6 +12,7 @@
 #include "bgemm8.hpp"
 #include "attn_mfma.hpp"
 #include "train_fused.hpp"
+#include "infer_wide.hpp"
 
 using namespace scldm;
 using namespace scldm::train;
@@ -90,6 +91,12 @@ Saved carve_saved(const scldm_dit* h, int n, void* base, bool fused_path) {
 }
 
 constexpr int kMaxSplit = 32;
+// split-K partials of the largest weight gradient (6D x D, or H x D) and column-sum partials (+ row sums).  The forward products split
+// K against the same bound, so the record-free inference path carves the same number: same split choice for the same extents.
+size_t split_k_floats(const scldm_dit* h) {
+  const size_t H = h->cfg.hidden_dim, kD = h->cfg.n_embed;
+  return (size_t)kMaxSplit * (std::max<size_t>((size_t)6 * kD * kD, std::max<size_t>(H, 3 * kD) * kD) + 6 * kD);
+}
 // fused_path: the per-token gradient arrays of the layers (dy, dao, dqkv, dhid, da, db) are not used
 Scratch carve_scratch(const scldm_dit* h, int n, void* base, bool fused_path) {
   const size_t T = (size_t)n * kS, H = h->cfg.hidden_dim, kD = h->cfg.n_embed;
@@ -114,8 +121,7 @@ Scratch carve_scratch(const scldm_dit* h, int n, void* base, bool fused_path) {
   s.dsth = c.take((size_t)n * kD);
   s.dth = c.take((size_t)n * kD);
   s.temb = c.take((size_t)n * kD);
-  // split-K partials of the largest weight gradient (6D x D, or H x D) and column-sum partials
-  s.part_floats = (size_t)kMaxSplit * (std::max<size_t>((size_t)6 * kD * kD, std::max<size_t>(H, 3 * kD) * kD) + 6 * kD);  // + row sums
+  s.part_floats = split_k_floats(h);
   s.part = c.take(s.part_floats);
   s.bytes = c.off;
   return s;
@@ -461,44 +467,63 @@ bool want_wt(const scldm_dit* h, int n) {
   static const int wt_min = [] { const char* e = getenv("SCLDM_WT_MIN_TILES"); return e ? atoi(e) : 32; }();
   return g_dgrad_wt && (g_bgemm256 == 2 || cdiv((long)n * kS, 256L) * cdiv((long)h->cfg.n_embed, 256L) >= wt_min);   // (2: the tests force 256-tiles)
 }
-int prepare_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st) {
-  const size_t D = h->cfg.n_embed, H = h->cfg.hidden_dim, Hp = hidden16(h);
-  const int L = h->cfg.n_layer;
-  if (L == 0) return SCLDM_OK;
-  h->w16_layer_elems = 4 * D * D + 2 * H * D + Hp * D;
-  if (!h->w16) HIP_TRY(hipMalloc(&h->w16, (size_t)L * h->w16_layer_elems * sizeof(__bf16)));
-  h->wt16_layer_elems = 4 * D * D + 2 * D * Hp + H * D;
-  const bool wt = want_wt(h, n);
-  if (wt && !h->wt16) HIP_TRY(hipMalloc(&h->wt16, (size_t)L * h->wt16_layer_elems * sizeof(__bf16)));
-  h->wt16_live = wt;
-  if (!h->ada16) HIP_TRY(hipMalloc(&h->ada16, (size_t)h->mod_w * D * sizeof(__bf16)));
-  if (!h->ada_ball) HIP_TRY(hipMalloc(&h->ada_ball, (size_t)h->mod_w * sizeof(float)));
+// the parameters a cast-job table reads (+ the transposed block it writes, or NULL): the table is rebuilt when one of them moved
+std::vector<const void*> w16_key_of(const scldm_dit* h, const scldm_dit_weights* w, bool wt) {
   std::vector<const void*> key;
-  for (int l = 0; l < L; ++l)
+  for (int l = 0; l < h->cfg.n_layer; ++l)
     for (const float* p : {w->attn_w[l], w->proj_w[l], w->w1[l], w->w2[l], w->cproj[l], w->ada_w[l], w->ada_b[l]}) key.push_back(p);
   key.push_back(w->fin_ada_w);
   key.push_back(w->fin_ada_b);
   key.push_back(wt ? h->wt16 : nullptr);
+  return key;
+}
+// wt: the jobs of the layers' matrices also write the transposed copies (the training step's data gradients); inference needs none
+std::vector<CastJob> w16_cast_jobs(const scldm_dit* h, const scldm_dit_weights* w, bool wt) {
+  const size_t D = h->cfg.n_embed, H = h->cfg.hidden_dim, Hp = hidden16(h);
+  const int L = h->cfg.n_layer;
+  std::vector<CastJob> jobs;
+  // every adaLN Linear stacked in the order of the modulation vector's columns: layer l rows [6 D l, 6 D (l+1)), then the final layer's 2 D
+  __bf16* a16 = reinterpret_cast<__bf16*>(h->ada16);
+  for (int l = 0; l <= L; ++l) {
+    const int rows = (int)(l < L ? 6 * D : 2 * D);
+    jobs.push_back(CastJob{l < L ? w->ada_w[l] : w->fin_ada_w, a16 + (size_t)l * 6 * D * D, rows, (int)D, (int)D, 0, nullptr, 0, 0});
+    jobs.push_back(CastJob{l < L ? w->ada_b[l] : w->fin_ada_b, reinterpret_cast<__bf16*>(h->ada_ball + (size_t)l * 6 * D), 1, rows, rows, 1, nullptr, 0, 0});
+  }
+  // ... then the layers in order
+  for (int l = 0; l < L; ++l) {
+    const W16 d = w16_layer(h, l);
+    const W16 dt = wt ? wt16_layer(h, l) : W16{};
+    auto tp = [](const __bf16* p) { return const_cast<__bf16*>(p); };
+    jobs.push_back(CastJob{w->attn_w[l], tp(d.attn_w), (int)(3 * D), (int)D, (int)D, 0, tp(dt.attn_w), (int)(3 * D), (int)(3 * D)});
+    jobs.push_back(CastJob{w->proj_w[l], tp(d.proj_w), (int)D, (int)D, (int)D, 0, tp(dt.proj_w), (int)D, (int)D});
+    jobs.push_back(CastJob{w->w1[l], tp(d.w1), (int)H, (int)D, (int)D, 0, tp(dt.w1), (int)(2 * Hp), (int)Hp});
+    jobs.push_back(CastJob{w->w2[l], tp(d.w2), (int)H, (int)D, (int)D, 0, tp(dt.w2), (int)(2 * Hp), (int)Hp});
+    jobs.push_back(CastJob{w->cproj[l], tp(d.cproj), (int)D, (int)H, (int)Hp, 0, tp(dt.cproj), (int)D, (int)D});
+  }
+  return jobs;
+}
+// the mirror's allocations (first use only)
+int alloc_w16(scldm_dit* h) {
+  const size_t D = h->cfg.n_embed, H = h->cfg.hidden_dim, Hp = hidden16(h);
+  h->w16_layer_elems = 4 * D * D + 2 * H * D + Hp * D;
+  if (!h->w16) HIP_TRY(hipMalloc(&h->w16, (size_t)h->cfg.n_layer * h->w16_layer_elems * sizeof(__bf16)));
+  if (!h->ada16) HIP_TRY(hipMalloc(&h->ada16, (size_t)h->mod_w * D * sizeof(__bf16)));
+  if (!h->ada_ball) HIP_TRY(hipMalloc(&h->ada_ball, (size_t)h->mod_w * sizeof(float)));
+  return SCLDM_OK;
+}
+int prepare_w16(scldm_dit* h, const scldm_dit_weights* w, int n, hipStream_t st) {
+  const size_t D = h->cfg.n_embed, H = h->cfg.hidden_dim, Hp = hidden16(h);
+  const int L = h->cfg.n_layer;
+  if (L == 0) return SCLDM_OK;
+  int rc = alloc_w16(h);
+  if (rc != SCLDM_OK) return rc;
+  h->wt16_layer_elems = 4 * D * D + 2 * D * Hp + H * D;
+  const bool wt = want_wt(h, n);
+  if (wt && !h->wt16) HIP_TRY(hipMalloc(&h->wt16, (size_t)L * h->wt16_layer_elems * sizeof(__bf16)));
+  h->wt16_live = wt;
+  const std::vector<const void*> key = w16_key_of(h, w, wt);
   if (key != h->w16_key || !h->d_cast_jobs) {
-    std::vector<CastJob> jobs;
-    // every adaLN Linear stacked in the order of the modulation vector's columns: layer l rows [6 D l, 6 D (l+1)), then the final layer's 2 D
-    __bf16* a16 = reinterpret_cast<__bf16*>(h->ada16);
-    for (int l = 0; l <= L; ++l) {
-      const int rows = (int)(l < L ? 6 * D : 2 * D);
-      jobs.push_back(CastJob{l < L ? w->ada_w[l] : w->fin_ada_w, a16 + (size_t)l * 6 * D * D, rows, (int)D, (int)D, 0, nullptr, 0, 0});
-      jobs.push_back(CastJob{l < L ? w->ada_b[l] : w->fin_ada_b, reinterpret_cast<__bf16*>(h->ada_ball + (size_t)l * 6 * D), 1, rows, rows, 1, nullptr, 0, 0});
-    }
-    // ... then the layers in order
-    for (int l = 0; l < L; ++l) {
-      const W16 d = w16_layer(h, l);
-      const W16 dt = wt ? wt16_layer(h, l) : W16{};
-      auto tp = [](const __bf16* p) { return const_cast<__bf16*>(p); };
-      jobs.push_back(CastJob{w->attn_w[l], tp(d.attn_w), (int)(3 * D), (int)D, (int)D, 0, tp(dt.attn_w), (int)(3 * D), (int)(3 * D)});
-      jobs.push_back(CastJob{w->proj_w[l], tp(d.proj_w), (int)D, (int)D, (int)D, 0, tp(dt.proj_w), (int)D, (int)D});
-      jobs.push_back(CastJob{w->w1[l], tp(d.w1), (int)H, (int)D, (int)D, 0, tp(dt.w1), (int)(2 * Hp), (int)Hp});
-      jobs.push_back(CastJob{w->w2[l], tp(d.w2), (int)H, (int)D, (int)D, 0, tp(dt.w2), (int)(2 * Hp), (int)Hp});
-      jobs.push_back(CastJob{w->cproj[l], tp(d.cproj), (int)D, (int)H, (int)Hp, 0, tp(dt.cproj), (int)D, (int)D});
-    }
+    const std::vector<CastJob> jobs = w16_cast_jobs(h, w, wt);
     if (!h->d_cast_jobs) HIP_TRY(hipMalloc(&h->d_cast_jobs, jobs.size() * sizeof(CastJob)));
     // (synchronous copy of a pageable vector: only when the parameters' device pointers changed)
     HIP_TRY(hipStreamSynchronize(st));
@@ -1317,3 +1342,5 @@ extern "C" int scldm_fm_loss_bwd(const float* pred, const float* ut, const float
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
+
+#include "infer_wide_api.inc"

@@ -329,6 +329,9 @@ class DiT(nn.Module):
             with torch.cuda.device(dev):
                 _lib.check(L.scldm_dit_create(C.byref(cfg), C.byref(h)), "scldm_dit_create")
             self._handle = h
+            # shapes outside the fused family, eval mode: the record-free inference entries (scldm_dit_infer_*) serve forward,
+            # forward_with_cfg and the fixed-grid sampler; SCLDM_WIDE_INFER=0 keeps them composed from scldm_dit_train_forward calls
+            self.__dict__["_wide_infer"] = os.environ.get("SCLDM_WIDE_INFER", "1") != "0"
         return L, self._handle
 
     def found_inf_flag(self) -> torch.Tensor:
@@ -422,7 +425,7 @@ class DiT(nn.Module):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _ws=None, _dedup_cache={})
         for k in ("_wstruct_cache", "_grad_offsets", "_grad_numel", "_grad_segs", "_pos_idx", "_param_list", "_prepared_key", "_grad_sync",
-                  "_train_step_sync", "_fp16_checked", "_found_inf", "_found_inf_handle", "_dense_rows", "_label_bad"):   # (_found_inf is registered with the handle that does not travel)
+                  "_train_step_sync", "_fp16_checked", "_found_inf", "_found_inf_handle", "_dense_rows", "_label_bad", "_wide_infer", "_ws_wide"):   # (_found_inf is registered with the handle that does not travel)
             state.pop(k, None)
         return state
 
@@ -605,6 +608,63 @@ class DiT(nn.Module):
                 g = g + float(s) * (cond_pass({c}) - u2)
         return torch.cat([u[:B], g], dim=0)
 
+    # ------------------------------------------------------------------ record-free inference of the same shapes (scldm_dit_infer_*)
+    def _wide_infer_on(self) -> bool:
+        """Eval-mode inference of a shape outside the fused family goes through scldm_dit_infer_* (SCLDM_WIDE_INFER, read when the native
+        handle is created; 0: the route composed from scldm_dit_train_forward calls)."""
+        if self.fused_shape or self.training:
+            return False
+        self._native_handle()
+        return bool(self.__dict__.get("_wide_infer", True))
+
+    def _wide_setup(self, n_fwd: int, n_rows: int, n_state: int):
+        """(L, handle, live weight struct, workspace pointer) of a scldm_dit_infer_* call; the workspace is kept and grows on demand."""
+        L, h = self._native_handle()
+        params = tuple(self.parameters())
+        cached = self.__dict__.get("_param_list")
+        if cached is None or len(cached) != len(params) or any(a is not b for a, b in zip(cached, params)):
+            self.__dict__["_param_list"] = params
+            self.__dict__.pop("_wstruct_cache", None)
+        w, _ = self._weights_struct(params)
+        need = L.scldm_dit_infer_workspace_bytes(h, n_fwd, n_rows, n_state, self._prec())
+        ws = self.__dict__.get("_ws_wide")
+        if ws is None or ws.numel() < need or ws.device != self.pos_embed.device:
+            self.__dict__["_ws_wide"] = ws = None   # (the old block is released before the new one is requested)
+            self.__dict__["_ws_wide"] = ws = torch.empty(need, dtype=torch.uint8, device=self.pos_embed.device)
+        return L, h, w, ws.data_ptr()
+
+    def _wide_forward(self, x: torch.Tensor, t: torch.Tensor, labels) -> torch.Tensor:
+        """DiT.forward in eval mode: conditioning rows (one per sample), then the trunk over one layer's working set."""
+        n = x.shape[0]
+        L, h, w, ws = self._wide_setup(n, n, 0)
+        mod = torch.empty(n, L.scldm_dit_mod_width(h), dtype=torch.float32, device=x.device)
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(L.scldm_dit_infer_cond_rows(h, C.byref(w), t.data_ptr(), 1, C.cast(labels, _lib.c_void_pp), n, mod.data_ptr(),
+                                                   self._prec(), ws, _stream_ptr()), "scldm_dit_infer_cond_rows")
+            _lib.check(L.scldm_dit_infer_forward_rows(h, C.byref(w), x.data_ptr(), n, 1, n, mod.data_ptr(), None, out.data_ptr(),
+                                                      self._prec(), ws, _stream_ptr()), "scldm_dit_infer_forward_rows")
+        return out
+
+    def _wide_forward_with_cfg(self, x, t, condition, cfg_scale) -> torch.Tensor:
+        """forward_with_cfg as one call: a one-element or stride-0 t shares ONE conditioning row among the unconditional sample-forwards
+        and one per unique label tuple among the conditional ones; any other t gets per-sample rows."""
+        self._need_null_row("forward_with_cfg (the unconditional pass)")
+        n = x.shape[0]
+        B = n // 2
+        t_stride = 0 if (t.stride(0) == 0 or n == 1) else 1
+        tt = _require_cuda_f32("t", t[:1] if t_stride == 0 else t)
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=t_stride == 0)
+        n_rows = (1 + n_pass * n_u) if t_stride == 0 else (2 * B + n_pass * B)
+        L, h, w, ws = self._wide_setup(2 * B + n_pass * B, n_rows, 0)
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(L.scldm_dit_infer_forward_cfg(h, C.byref(w), x.data_ptr(), tt.data_ptr(), t_stride,
+                                                     C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass, masks,
+                                                     scales, out.data_ptr(), self._prec(), ws, _stream_ptr()), "scldm_dit_infer_forward_cfg")
+        del keep
+        return out
+
     # ------------------------------------------------------------------ label handling (nnets.py:380-456)
     def _label_ptrs(self, condition: dict[str, torch.Tensor], n: int, force_drop_ids: bool):
         """Device label pointers per class (sorted-name order); None -> the class uses its null token.
@@ -671,7 +731,7 @@ class DiT(nn.Module):
                 self.__dict__.pop("_wstruct_cache", None)
             return _DiTTrainFn.apply(self, x, t, labels, keep, *params)
         if not self.fused_shape:
-            return self._generic_forward(x, t, labels)
+            return self._wide_forward(x, t, labels) if self._wide_infer_on() else self._generic_forward(x, t, labels)
         L, h = self._native()
         out = torch.empty_like(x)
         ws = self._workspace(L, n, n, 0)
@@ -828,6 +888,8 @@ class DiT(nn.Module):
             if xg.shape[0] % 2 or xg.shape[1:] != (self.seq_len, self.n_embed_input) or tg.shape != (xg.shape[0],):
                 raise ValueError(f"expected x (2B,{self.seq_len},{self.n_embed_input}) and t (2B,), got {tuple(xg.shape)}, {tuple(tg.shape)}")
             with torch.no_grad():
+                if self._wide_infer_on():
+                    return self._wide_forward_with_cfg(xg, t, condition, cfg_scale)   # (t as given: a stride-0 view says it is one scalar)
                 return self._generic_forward_with_cfg(xg, tg, condition, cfg_scale)
         self._need_null_row("forward_with_cfg (the unconditional pass)")
         L, h = self._native()
@@ -910,6 +972,25 @@ class DiT(nn.Module):
             from .transport import Sampler, create_transport
             fn = Sampler(create_transport()).sample_ode(sampling_method="dopri5", num_steps=2, atol=atol, rtol=rtol)
             return fn(_require_cuda_f32("z", z), self.forward_with_cfg, condition=condition, cfg_scale=cfg_scale)[-1]
+        if self._wide_infer_on():
+            # shapes outside the fused family: the whole solve as one call over the generic kernels (scldm_dit_infer_sample_ode)
+            self._need_null_row("CFG sampling (the unconditional pass)")
+            method = sampling_method.lower()
+            if method not in _lib.METHODS:
+                raise KeyError(method)
+            z = _require_cuda_f32("z", z).clone()
+            n = z.shape[0]
+            B = n // 2
+            if n != 2 * B or z.shape[1:] != (self.seq_len, self.n_embed_input):
+                raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+            ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+            L, h, w, ws = self._wide_setup(2 * B + n_pass * B, 1 + n_pass * n_u, 2 * B)
+            with torch.cuda.device(z.device):
+                _lib.check(L.scldm_dit_infer_sample_ode(h, C.byref(w), z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None,
+                                                        n_u, cell_row, B, n_pass, masks, scales, num_steps - 1, _lib.METHODS[method],
+                                                        self._prec(), ws, _stream_ptr()), "scldm_dit_infer_sample_ode")
+            del keep
+            return z
         if self.training or not self.fused_shape:
             # fixed-grid Euler / Heun over forward_with_cfg, one evaluation per call (same grid as the fused loop): shapes outside
             # the fused family, and modules left in training mode (the reference samples in whatever mode the caller left the
