@@ -629,7 +629,8 @@ int scldm_nb_sample(const float* mu, const float* theta, float* out, size_t n, u
  * mu (B,G) = params(LayerNorm(h_x)), the mean of Normal(mu, 1); library_size plays no part.  The per-gene kernel stores mu itself:
  * no pass over (B,G) follows it.  The LayerNorm and the 32 -> 1 product of the head are fp32 in every `precision`.  Workspace:
  * scldm_vae_workspace_bytes.  A handle with a negative-binomial head returns SCLDM_ERR_SHAPE; so do scldm_vae_decode,
- * scldm_vae_decode_sample and the scldm_vae_train_* entry points on a handle with a Gaussian head (it decodes only). */
+ * scldm_vae_decode_sample and the NB scldm_vae_train_* entry points on a handle with a Gaussian head (it trains through
+ * scldm_vae_train_gaussian_forward / _gaussian_backward below). */
 int scldm_vae_decode_gaussian(scldm_vae* h, const float* z, const int64_t* genes, int B, int G, float* mu, int precision, void* ws,
                               void* stream);
 /* The same followed by Normal(mu, 1).sample() (models.py:819): out = mu + n with n the standard normal of Philox4x32-10 keyed by
@@ -716,6 +717,23 @@ int scldm_vae_train_backward_ordered(scldm_vae* h, const scldm_vae_weights* w, c
                                      const float* dz, void* saved, void* ws, int precision, const int32_t* order, const int32_t* seg,
                                      int n_entries, void* rows, void* stream);
 
+/* The training step of a handle with the GAUSSIAN head (GaussianTransformerLayer; loss log_gaussian(log1p(counts / rowsum * 1e4),
+ * mu).sum(1).mean(), models.py:239-245), fp32, beside the NB entries above as scldm_vae_decode_gaussian sits beside scldm_vae_decode.
+ *   forward : (mu, z) on the inference kernels (the per-gene kernel writes mu itself); `saved` as scldm_vae_train_forward leaves it.
+ *   backward: given d loss / d mu (B, G; may be NULL) and optionally d loss / d z, writes every gradient named in `g`, now including
+ *             g->head_ln_w, g->head_ln_b, g->head_w (1,32) and g->head_b (1) - the bias gradient is real here; g->theta is ignored.
+ *             order == NULL: gene_embedding by float atomics (seg, n_entries, rows are ignored); otherwise order / seg / n_entries /
+ *             rows are those of scldm_vae_train_backward_ordered and every gradient is bit-equal run to run.
+ * The LayerNorm in front of the head makes the gradient entering the per-gene MLP rank two, so the per-gene backward is a kernel of
+ * its own (one workgroup per CU).  scldm_vae_train_saved_bytes / _workspace_bytes / _rows_bytes / _split serve both heads.  A handle
+ * with a negative-binomial head returns SCLDM_ERR_SHAPE (the message names the head), as the NB entries do on a Gaussian handle. */
+int scldm_vae_train_gaussian_forward(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S,
+                                     const int64_t* genes, int G, float* mu, float* z, void* saved, void* ws, void* stream);
+int scldm_vae_train_gaussian_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
+                                      const int64_t* genes_subset, int B, int S, const int64_t* genes, int G, const float* mu,
+                                      const float* z, const float* dmu, const float* dz, void* saved, void* ws, const int32_t* order,
+                                      const int32_t* seg, int n_entries, void* rows, void* stream);
+
 /* log_nb_positive (src/scldm/distributions.py:6-42) elementwise over n values, and its gradient w.r.t. mu and theta given the
  * upstream gradient of the log-likelihood (either output may be NULL):
  *   res = theta (log(theta + eps) - L) + x (log(mu + eps) - L) + lgamma(x + theta) - lgamma(theta) - lgamma(x + 1),  L = log(theta + mu + eps) */
@@ -801,6 +819,9 @@ int scldm_log1p_normalize(const float* x, int n, int G, const float* div, float 
  * rowsum_b * target_sum) - mu[b,g])^2, one workgroup per row, fixed-order sums (bit-reproducible); the scaled counts are those of
  * scldm_log1p_normalize with div = NULL (target_sum <= 0: the counts as they are). */
 int scldm_gaussian_recon_loss(const float* counts, const float* mu, int B, int G, float target_sum, float* loss_rows, void* stream);
+/* ... and its gradient w.r.t. mu given d / d loss_rows (B): dmu[b,g] = -2 (y[b,g] - mu[b,g]) gout_rows[b], y recomputed as above. */
+int scldm_gaussian_recon_loss_bwd(const float* counts, const float* mu, const float* gout_rows, int B, int G, float target_sum,
+                                  float* dmu, void* stream);
 
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the

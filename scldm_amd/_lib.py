@@ -245,6 +245,12 @@ def lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.scldm_log1p_normalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.scldm_gaussian_recon_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    L.scldm_gaussian_recon_loss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    L.scldm_vae_train_gaussian_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scldm_vae_train_gaussian_backward.argtypes = [C.c_void_p, C.POINTER(VaeWeights), C.POINTER(VaeWeights), C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -260,6 +266,7 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_train_workspace_bytes_dx_for", "scldm_dit_train_backward_dx", "scldm_logp_workspace_bytes", "scldm_logp_ode", "scldm_logp_probe",
            "scldm_vae_decode_gaussian", "scldm_vae_decode_gaussian_sample", "scldm_normal_sample", "scldm_gaussian_recon_loss",
            "scldm_vae_train_split",
+           "scldm_vae_train_gaussian_forward", "scldm_vae_train_gaussian_backward", "scldm_gaussian_recon_loss_bwd",
            "scldm_dit_infer_workspace_bytes", "scldm_dit_infer_cond_rows", "scldm_dit_infer_forward_rows", "scldm_dit_infer_forward_cfg",
            "scldm_dit_infer_sample_ode"]
 

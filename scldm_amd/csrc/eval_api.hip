@@ -98,3 +98,12 @@ extern "C" int scldm_gaussian_recon_loss(const float* counts, const float* mu, i
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
+
+extern "C" int scldm_gaussian_recon_loss_bwd(const float* counts, const float* mu, const float* gout_rows, int B, int G, float target_sum,
+                                             float* dmu, void* stream_) {
+  if (!counts || !mu || !gout_rows || !dmu) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if (B < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B >= 1 and G >= 1 (got %d, %d)", B, G);
+  hipLaunchKernelGGL(gaussian_recon_loss_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, counts, mu, gout_rows, G, target_sum, dmu);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}

@@ -100,6 +100,20 @@ __global__ __launch_bounds__(256) void gaussian_recon_loss_kernel(const float* _
   }
   if (threadIdx.x == 0) loss_rows[blockIdx.x] = (float)sh[0];
 }
+// ... and its gradient with respect to mu in one pass: dmu[b, g] = -2 (y[b, g] - mu[b, g]) gout_rows[b], y recomputed exactly as above
+// (the training step of the Gaussian head: mu requires grad, counts do not)
+__global__ __launch_bounds__(256) void gaussian_recon_loss_bwd_kernel(const float* __restrict__ counts, const float* __restrict__ mu,
+                                                                      const float* __restrict__ gout_rows, int G, float target_sum,
+                                                                      float* __restrict__ dmu) {
+  __shared__ double sh[256];
+  const float* row = counts + (size_t)blockIdx.x * G;
+  const float* mrow = mu + (size_t)blockIdx.x * G;
+  float* drow = dmu + (size_t)blockIdx.x * G;
+  const bool raw = !(target_sum > 0.f);
+  const float s = raw ? 1.0f : target_sum / (float)eval_block_row_sum(row, G, sh);
+  const float go = -2.0f * gout_rows[blockIdx.x];
+  for (int g = threadIdx.x; g < G; g += 256) drow[g] = ((raw ? row[g] : eval_log1p(row[g] * s)) - mrow[g]) * go;
+}
 
 // Partials: `part` holds 5 planes (mean_u, M2_u, mean_v, M2_v, C_uv) of (plane_rows, G) floats, row = row block.
 // PAIRED: a and b are pred and true with the same n; all five planes and the workgroup's (sum (u-v)^2, zero agreement)

@@ -6,7 +6,7 @@
 // This file holds what the kernels of the backward share: the argument structs and the layouts of the per-workgroup partials
 // (DP_*, TP_*, dc_*, ec_*, EP_*), and the small kernels around the heavy ones - weight transposes, the encoder's cell-independent
 // query branch (enc_q_*), the NB head backward, the partial reductions and the fused NB log-likelihood.  The heavy kernels (per-gene
-// decoder chain, the two 16-token cell sides, the encoder pooling) are in vae_train_wide.hpp.
+// decoder chain in its NB and Gaussian-head forms, the two 16-token cell sides, the encoder pooling) are in vae_train_wide.hpp.
 // Sums over TOKENS (weight gradients, the per-cell dK / dV of the decoder's cross attention, the encoder's dQ) are written as ONE
 // partial per workgroup, and a final pass adds the partials in index order (deterministic).  Only the two embedding-table
 // gradients (gene_embedding, theta: scatter by gene id) use float atomics by default, like torch's own embedding backward.  The
@@ -269,6 +269,14 @@ struct DecBwdArgs {
   // the caller's found-inf flag (may be null)
   const float* dl_scale;
   float* found_inf;
+};
+// Gaussian head (wide::dec_gene_bwd_gauss_kernel): `nb.dl` is d loss / d mu as the caller gives it, `nb.head_w` the (1, 32) params
+// weight; the partial is the NB layout followed by the head LayerNorm's vectors and the head bias (a layout of its own: DP_SIZE
+// and the NB kernels' argument block stay what they were)
+enum : int { GP_HLNW = DP_SIZE, GP_HLNB = GP_HLNW + 32, GP_HEADB = GP_HLNB + 32, GP_SIZE = GP_HEADB + 32 };
+struct DecBwdGaussArgs {
+  DecBwdArgs nb;
+  const float *hln_w, *hln_b;   // decoder_head.ln.weight / .bias (32)
 };
 
 // =================================================================================================================================

@@ -1,4 +1,4 @@
-// C ABI of the TransformerVAE training step (scldm_vae_train_*, scldm_nb_loglik*; see include/scldm_hip.h): host-side
+// C ABI of the TransformerVAE training step (scldm_vae_train_*, scldm_vae_train_gaussian_*, scldm_nb_loglik*; see include/scldm_hip.h): host-side
 // sequencing of the kernels in vae_train.hpp and vae_train_wide.hpp.  The forward is the inference path (mcab.hpp) with two extra outputs; the backward
 // reads the parameters LIVE from the caller's tensors (PyTorch layouts) and writes every gradient in the same layout.
 #include <algorithm>
@@ -57,10 +57,12 @@ Saved carve_saved(int B, void* base) {
   return s;
 }
 
-// every training entry refuses a handle that holds the Gaussian head: its LayerNorm breaks the rank-1 form of d(y + mlp) the per-gene
-// backward is built on
-const char* const kGaussNoTrain = "the training kernels are built for the negative-binomial head; this handle holds a Gaussian head "
-                                  "(GaussianTransformerLayer), which decodes only";
+// the NB training entries refuse a handle that holds the Gaussian head, and the Gaussian ones an NB handle: the head's LayerNorm
+// makes d(y + mlp) rank two per gene, which is a per-gene kernel of its own (wide::dec_gene_bwd_gauss_kernel)
+const char* const kGaussNoTrain = "this entry trains the negative-binomial head; this handle holds a Gaussian head "
+                                  "(GaussianTransformerLayer): use scldm_vae_train_gaussian_forward / _gaussian_backward";
+const char* const kNbNoGaussTrain = "this entry trains the Gaussian head (GaussianTransformerLayer); this handle holds a negative-binomial "
+                                    "head (NegativeBinomialTransformerLayer): use scldm_vae_train_forward / _backward";
 
 // precision of a training step: fp32 (exact), or fp16 (fp16 operands of the per-gene MCAB contractions, forward and backward)
 int check_train_precision(int precision) {
@@ -93,7 +95,7 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   w.dao = k.take((size_t)B * kT * 32);
   w.dgq = k.take((size_t)B * 64);
   w.bsum = k.take((size_t)B);
-  w.p_gene = k.take((size_t)B * w.chunksD * DP_SIZE);
+  w.p_gene = k.take((size_t)B * w.chunksD * (h->gaussian ? GP_SIZE : DP_SIZE));   // (the Gaussian partial carries the head rows)
   w.p_dkv = k.take((size_t)B * w.chunksD * kT * 64);
   w.p_dcell = k.take((size_t)B * dc_size(L));      // cell-side partials: one per cell
   w.p_ecell = k.take((size_t)B * ec_size(L));
@@ -234,21 +236,43 @@ extern "C" int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset,
                                     SCLDM_PREC_FP32, stream_);
 }
 
+// Gaussian head: the inference path (the per-gene kernel writes mu itself, no finalize pass) and the same `saved` as the NB forward
+extern "C" int scldm_vae_train_gaussian_forward(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S,
+                                                const int64_t* genes, int G, float* mu, float* z, void* saved_, void* ws, void* stream_) {
+  if (!h || !counts_subset || !genes_subset || !genes || !mu || !z || !saved_ || !ws) return fail(SCLDM_ERR_SHAPE, "null argument");
+  if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1");
+  if (!h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kNbNoGaussTrain);
+  hipStream_t st = (hipStream_t)stream_;
+  Saved s = carve_saved(B, saved_);
+  int rc = scldm_vae_encode_ex(h, counts_subset, genes_subset, B, S, z, SCLDM_PREC_FP32, s.pooled, s.lse2, st);
+  if (rc) return rc;
+  rc = scldm_vae_decode_gaussian(h, z, genes, B, G, mu, SCLDM_PREC_FP32, ws, stream_);
+  if (rc) return rc;
+  // (the fp32 decode leaves the cells' plain K | V at the start of its workspace, as scldm_vae_decode does)
+  HIP_TRY(hipMemcpyAsync(s.kv, ws, (size_t)B * kT * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return SCLDM_OK;
+}
+
 namespace {
 // the backward of both table-gradient modes: atomic (rows_ == nullptr; scldm_vae_train_backward_ex) or ordered
 int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,
                         const int64_t* genes_subset, int B, int S, const int64_t* genes, const float* library_size, int G, const float* mu,
                         const float* theta, const float* z, const float* dmu, const float* dtheta, const float* dz, void* saved_, void* ws_,
-                        int precision, const int32_t* order, const int32_t* seg, int n_entries, void* rows_, void* stream_) {
+                        int precision, const int32_t* order, const int32_t* seg, int n_entries, void* rows_, void* stream_,
+                        bool gauss = false) {
+  // gauss: the Gaussian head (scldm_vae_train_gaussian_backward) - library_size, theta, dtheta are NULL and unused, fp32 only
   int rc = check_train_precision(precision);
   if (rc) return rc;
-  if (h && h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kGaussNoTrain);
+  if (h && h->gaussian != gauss) return fail(SCLDM_ERR_SHAPE, "%s", gauss ? kNbNoGaussTrain : kGaussNoTrain);
   rc = check_train(h, w, B, S, G);
   if (rc) return rc;
   const bool f16 = precision == SCLDM_PREC_FP16;
-  if (!g || !counts_subset || !genes_subset || !genes || !library_size || !mu || !theta || !z || !saved_ || !ws_)
+  if (!g || !counts_subset || !genes_subset || !genes || !mu || !z || !saved_ || !ws_ || (!gauss && (!library_size || !theta)))
     return fail(SCLDM_ERR_SHAPE, "null argument");
-  if (!g->gene_embedding || !g->theta) return fail(SCLDM_ERR_SHAPE, "the gene_embedding and theta gradient tables are required");
+  if (gauss) {
+    if (!g->gene_embedding) return fail(SCLDM_ERR_SHAPE, "the gene_embedding gradient table is required");
+    if (!w->head_ln_w || !w->head_ln_b || !w->head_w) return fail(SCLDM_ERR_SHAPE, "Gaussian head: head_ln_w, head_ln_b and head_w are required");
+  } else if (!g->gene_embedding || !g->theta) return fail(SCLDM_ERR_SHAPE, "the gene_embedding and theta gradient tables are required");
   hipStream_t st = (hipStream_t)stream_;
   const scldm_vae_config& c = h->cfg;
   const int L = c.n_layer, H = c.hidden_dim, nl = c.n_embed_latent;
@@ -261,7 +285,7 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
   const Rows rw = carve_rows(B, S, G, rows_);
   if (!ordered) {   // (the ordered reduction writes every table row, the untouched ones as zeros)
     HIP_TRY(hipMemsetAsync(g_emb, 0, (size_t)(c.n_genes + 1) * 32 * 4, st));
-    HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
+    if (!gauss) HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
   }
   if (f16 && h->found_inf) HIP_TRY(hipMemsetAsync(h->found_inf, 0, sizeof(float), st));
 
@@ -299,6 +323,8 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
       HIP_TRY(hipFuncSetAttribute((const void*)wide::enc_pool_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wide::PB_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_gauss_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::MG_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_gauss_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::MG_BYTES));
       if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
     }
   }
@@ -336,20 +362,27 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
   wide::dec_cell_fwd_kernel<<<B, wide::kThreads, wide::LDS_BYTES, s2>>>(da);
   LAUNCH_CHECK();
   if (overlap) HIP_TRY(hipEventRecord(h->ev_join, s2));
-  // ---- NB head, then the per-gene decoder chain
-  if (ordered) {
+  // ---- NB head, then the per-gene decoder chain (the Gaussian head has no head pass: d logit is d mu as given, the head bias
+  // gradient comes out of the per-gene kernel's partial, and there is no theta)
+  if (gauss) {
+    if (!dmu) HIP_TRY(hipMemsetAsync(k.dl, 0, (size_t)B * G * sizeof(float), st));
+  } else if (ordered) {
     if (f16) head_bwd_kernel<true, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, k.dl_scale);
     else head_bwd_kernel<false, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, nullptr);
   } else if (f16) head_bwd_kernel<true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, k.dl_scale);
   else head_bwd_kernel<false><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, genes, G, 1.0f / c.nb_temperature, k.dl, g_theta, k.bsum, nullptr);
   LAUNCH_CHECK();
   DecBwdArgs ga{};
-  ga.genes = genes; ga.emb = w->gene_embedding; ga.dl = k.dl; ga.kv = overlap ? sv.kv : k.kv;
+  ga.genes = genes; ga.emb = w->gene_embedding; ga.dl = gauss && dmu ? dmu : k.dl; ga.kv = overlap ? sv.kv : k.kv;
   ga.ln1q_w = w->dec_cross.ln1q_w; ga.ln1q_b = w->dec_cross.ln1q_b; ga.wq = w->dec_cross.attn_q; ga.wp = w->dec_cross.attn_proj;
   ga.ln2_w = w->dec_cross.ln2_w; ga.ln2_b = w->dec_cross.ln2_b; ga.head_w = w->head_w;
   ga.mlp = mlp_of(w->dec_cross.w1, w->dec_cross.w2, wct(1), H);
   ga.g_emb = ordered ? rw.emb : g_emb; ga.part = k.p_gene; ga.dkv_part = k.p_dkv; ga.G = G; ga.tiles = k.tilesD; ga.eps = eps;
-  if (f16) {
+  if (gauss) {
+    DecBwdGaussArgs gg{ga, w->head_ln_w, w->head_ln_b};
+    if (ordered) wide::dec_gene_bwd_gauss_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::MG_BYTES, st>>>(gg);
+    else wide::dec_gene_bwd_gauss_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::MG_BYTES, st>>>(gg);
+  } else if (f16) {
     ga.dl_scale = k.dl_scale;
     ga.found_inf = h->found_inf;
     if (ordered) wide::dec_gene_bwd_mfma2_kernel<true, true><<<dim3(k.chunksD, B), wide::kThreads, wide::M_BYTES, st>>>(ga);
@@ -377,7 +410,7 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
     // The theta table walks the same segments and takes the decoder entries (those below B * G) only.
     const int n_table = c.n_genes + 1, n_dec = B * G;
     table_rows_reduce_kernel<<<n_table, 256, 0, st>>>(rw.emb, order, seg, n_table, n_entries, n_dec + B * S, g_emb);
-    table_scalars_reduce_kernel<<<cdiv(n_table, 32), 256, 0, st>>>(rw.theta, order, seg, n_table, n_entries, n_dec, g_theta);
+    if (!gauss) table_scalars_reduce_kernel<<<cdiv(n_table, 32), 256, 0, st>>>(rw.theta, order, seg, n_table, n_entries, n_dec, g_theta);
     LAUNCH_CHECK();
   }
 
@@ -398,10 +431,17 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
     j.vec(G_(g->head_w), DP_HEADW, 32);
     // (on the second stream, beside the cell-side backward kernels: it only needs the per-gene kernel's partials)
     if (overlap) HIP_TRY(hipStreamWaitEvent(s2, h->ev_gene, 0));
-    if ((rc = j.run(k.p_gene, B * k.chunksD, DP_SIZE, s2))) return rc;
-    Jobs jb;
-    jb.vec(G_(g->head_b), 0, 1);
-    if ((rc = jb.run(k.bsum, B, 1, s2))) return rc;
+    if (gauss) {
+      j.vec(G_(g->head_ln_w), GP_HLNW, 32);
+      j.vec(G_(g->head_ln_b), GP_HLNB, 32);
+      j.vec(G_(g->head_b), GP_HEADB, 1);
+      if ((rc = j.run(k.p_gene, B * k.chunksD, GP_SIZE, s2))) return rc;
+    } else {
+      if ((rc = j.run(k.p_gene, B * k.chunksD, DP_SIZE, s2))) return rc;
+      Jobs jb;
+      jb.vec(G_(g->head_b), 0, 1);
+      if ((rc = jb.run(k.bsum, B, 1, s2))) return rc;
+    }
   }
   {
     Jobs j;   // decoder cell side
@@ -471,6 +511,27 @@ extern "C" int scldm_vae_train_backward_ordered(scldm_vae* h, const scldm_vae_we
     return fail(SCLDM_ERR_SHAPE, "n_entries %d outside [0, B * G + B * S = %lld]", n_entries, n_max);
   return train_backward_impl(h, w, g, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, dmu, dtheta, dz, saved_, ws_,
                              precision, order, seg, n_entries, rows, stream_);
+}
+
+// Gaussian head, both table-gradient modes: order == NULL is the atomic mode, otherwise the contract of scldm_vae_train_backward_ordered
+extern "C" int scldm_vae_train_gaussian_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g,
+                                                 const float* counts_subset, const int64_t* genes_subset, int B, int S, const int64_t* genes,
+                                                 int G, const float* mu, const float* z, const float* dmu, const float* dz, void* saved_,
+                                                 void* ws_, const int32_t* order, const int32_t* seg, int n_entries, void* rows,
+                                                 void* stream_) {
+  if (h && !h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kNbNoGaussTrain);
+  if (order) {
+    if (!seg || !rows) return fail(SCLDM_ERR_SHAPE, "scldm_vae_train_gaussian_backward: null order / seg / rows");
+    if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1 (got %d, %d, %d)", B, S, G);
+    const long long n_max = (long long)B * G + (long long)B * S;
+    if (n_max > 0x7fffffffLL - 64) return fail(SCLDM_ERR_SHAPE, "B * (G + S) = %lld entries exceed the int32 entry index", n_max);
+    if (n_entries < 0 || n_entries > n_max)
+      return fail(SCLDM_ERR_SHAPE, "n_entries %d outside [0, B * G + B * S = %lld]", n_entries, n_max);
+  } else {
+    rows = nullptr;
+  }
+  return train_backward_impl(h, w, g, counts_subset, genes_subset, B, S, genes, nullptr, G, mu, nullptr, z, dmu, nullptr, dz, saved_, ws_,
+                             SCLDM_PREC_FP32, order, seg, n_entries, rows, stream_, true);
 }
 
 extern "C" int scldm_vae_train_backward(scldm_vae* h, const scldm_vae_weights* w, const scldm_vae_weights* g, const float* counts_subset,

@@ -67,17 +67,40 @@ def log_gaussian(x: torch.Tensor, mu: torch.Tensor, sigma: torch.Tensor | None =
     return 0.5 * torch.pow((x - mu) / sigma, 2) + log_fn(sigma)
 
 
+class _GaussRecon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, counts, mu, target_sum):
+        out = torch.empty(counts.shape[0], dtype=torch.float32, device=counts.device)
+        with torch.cuda.device(counts.device):
+            _lib.check(_lib.lib().scldm_gaussian_recon_loss(counts.data_ptr(), mu.data_ptr(), counts.shape[0], counts.shape[1], target_sum,
+                                                            out.data_ptr(), torch.cuda.current_stream().cuda_stream), "scldm_gaussian_recon_loss")
+        ctx.save_for_backward(counts, mu)
+        ctx.target_sum = target_sum
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        counts, mu = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        dmu = torch.empty_like(mu)
+        with torch.cuda.device(mu.device):
+            _lib.check(_lib.lib().scldm_gaussian_recon_loss_bwd(counts.data_ptr(), mu.data_ptr(), gout.data_ptr(), counts.shape[0],
+                                                                counts.shape[1], ctx.target_sum, dmu.data_ptr(),
+                                                                torch.cuda.current_stream().cuda_stream), "scldm_gaussian_recon_loss_bwd")
+        return None, dmu, None
+
+
 def gaussian_recon_loss(counts: torch.Tensor, mu: torch.Tensor, target_sum: float = 1e4) -> torch.Tensor:
     """(B,) fp32: sum_g (log1p(counts / rowsum * target_sum) - mu)^2, i.e. `log_gaussian(y, mu).sum(1)` of models.py:240-241,245 in
     one HIP pass (scldm_gaussian_recon_loss) that never writes y; `.mean()` of it is the reference's loss.  Fixed-order sums:
-    bit-reproducible.  counts, mu: contiguous fp32 (B, G) CUDA (ROCm) tensors; no CPU path, not differentiable."""
+    bit-reproducible.  counts, mu: contiguous fp32 (B, G) CUDA (ROCm) tensors; no CPU path.  Differentiable with respect to `mu`
+    when it requires grad (one fused backward pass, scldm_gaussian_recon_loss_bwd: -2 (y - mu) per element); never w.r.t. counts."""
     if not (isinstance(counts, torch.Tensor) and isinstance(mu, torch.Tensor) and counts.is_cuda and mu.device == counts.device):
         raise RuntimeError("gaussian_recon_loss runs on the MI355X HIP path; there is no CPU fallback")
     if counts.dim() != 2 or counts.shape != mu.shape or counts.shape[0] < 1 or counts.shape[1] < 1:
         raise ValueError(f"expected counts and mu (B, G), got {tuple(counts.shape)} and {tuple(mu.shape)}")
-    counts, mu = counts.detach().contiguous().float(), mu.detach().contiguous().float()
-    out = torch.empty(counts.shape[0], dtype=torch.float32, device=counts.device)
-    with torch.cuda.device(counts.device):
-        _lib.check(_lib.lib().scldm_gaussian_recon_loss(counts.data_ptr(), mu.data_ptr(), counts.shape[0], counts.shape[1], float(target_sum),
-                                                        out.data_ptr(), torch.cuda.current_stream().cuda_stream), "scldm_gaussian_recon_loss")
-    return out
+    counts = counts.detach().contiguous().float()
+    if not (torch.is_grad_enabled() and mu.requires_grad):
+        mu = mu.detach()
+    return _GaussRecon.apply(counts, mu.contiguous().float(), float(target_sum))

@@ -47,6 +47,32 @@ def train_split(B: int, S: int, G: int):
     return (out[0], out[1]), (out[2], out[3])
 
 
+def _grad_structs(module, params, dev):
+    """(flat, w, g) of a training backward: every gradient is a view of ONE zero-initialised buffer `flat` (parameters the kernels do
+    not write, e.g. a frozen table, stay 0).  The offsets, the weight-pointer struct `w` and (while the allocator hands back the same
+    block) the gradient-pointer struct `g` are cached on the module: building two 175-field ctypes structs per step is host time a
+    batch-32 step cannot hide."""
+    cache = module.__dict__.setdefault("_train_cache", {})
+    pk = tuple(p.data_ptr() for p in params)
+    if cache.get("pk") != pk:
+        offs, total = {}, 0
+        for p in params:       # dense: the kernels write gradients with 4-byte stores / atomics, nothing needs more alignment
+            offs[id(p)] = total
+            total += p.numel()
+        cache.clear()
+        cache.update(pk=pk, offs=offs, total=total, w=module._weights_struct(lambda t: t.data_ptr()))
+    offs, total = cache["offs"], cache["total"]
+    flat = torch.zeros(total, dtype=torch.float32, device=dev)
+    base = flat.data_ptr()
+    if cache.get("gbase") != base:
+        cache["gbase"], cache["g"] = base, module._weights_struct(lambda t: base + 4 * offs[id(t)])
+    return flat, cache["w"][0], cache["g"][0]
+
+
+def _ordered_mode(module) -> bool:
+    return bool(module.deterministic) or module.__dict__.get("_env_deterministic", False) or torch.are_deterministic_algorithms_enabled()
+
+
 class _VAETrainFn(torch.autograd.Function):
     """TransformerVAE.forward with a HIP backward (scldm_vae_train_forward / _backward, include/scldm_hip.h): replaces torch
     autograd over the reference's module tree (vae.py:29-56) inside VAE.training_step (models.py:249-290).  Outputs mu, theta
@@ -94,37 +120,15 @@ class _VAETrainFn(torch.autograd.Function):
         dev = mu.device
         prep = lambda t: None if t is None else t.contiguous().float()
         dmu, dtheta, dz = prep(dmu), prep(dtheta), prep(dz)
-        # every gradient is a view of ONE zero-initialised buffer (parameters the kernels do not write, e.g. a frozen table, stay 0).
-        # The offsets, the weight-pointer struct and (while the allocator hands back the same block) the gradient-pointer struct are
-        # cached on the module: building two 175-field ctypes structs per step is host time a batch-32 step cannot hide.
-        cache = module.__dict__.setdefault("_train_cache", {})
-        pk = tuple(p.data_ptr() for p in params)
-        if cache.get("pk") != pk:
-            offs, total = {}, 0
-            for p in params:       # dense: the kernels write gradients with 4-byte stores / atomics, nothing needs more alignment
-                offs[id(p)] = total
-                total += p.numel()
-            cache.clear()
-            cache.update(pk=pk, offs=offs, total=total, w=module._weights_struct(lambda t: t.data_ptr()))
-        offs, total = cache["offs"], cache["total"]
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        base = flat.data_ptr()
-        if cache.get("gbase") != base:
-            cache["gbase"], cache["g"] = base, module._weights_struct(lambda t: base + 4 * offs[id(t)])
-        w, keep_w = cache["w"]
-        g, keep_g = cache["g"]
+        flat, w, g = _grad_structs(module, params, dev)
         ptr = lambda t: None if t is None else t.data_ptr()
         args = (h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(), lib.data_ptr(), G,
                 mu.data_ptr(), theta.data_ptr(), z.data_ptr(), ptr(dmu), ptr(dtheta), ptr(dz), ctx.saved.data_ptr(), ctx.ws.data_ptr(),
                 ctx.prec)
-        ordered = bool(module.deterministic) or module.__dict__.get("_env_deterministic", False) or torch.are_deterministic_algorithms_enabled()
+        ordered = _ordered_mode(module)
         with torch.cuda.device(dev):
             if ordered:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("the ordered (deterministic) VAE training backward cannot be captured into a graph: building "
-                                       "the table index allocates; capture the default (atomic) mode or run this step eagerly")
-                order, seg = table_order(genes, genes_subset, counts_subset, module.input_layer.gene_embedding.weight.shape[0])
-                rows = torch.empty(L.scldm_vae_train_rows_bytes(h, B, S, G), dtype=torch.uint8, device=dev)
+                order, seg, rows = _ordered_index(module, L, h, genes, genes_subset, counts_subset)
                 _lib.check(L.scldm_vae_train_backward_ordered(*args, order.data_ptr(), seg.data_ptr(), order.numel(), rows.data_ptr(),
                                                               _stream_ptr()),
                            "scldm_vae_train_backward_ordered")
@@ -137,6 +141,76 @@ class _VAETrainFn(torch.autograd.Function):
         return (None, None, None, None, None, *out)
 
 
+def _ordered_index(module, L, h, genes, genes_subset, counts_subset):
+    """(order, seg, rows) of an ordered backward: the table index and the row buffer."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("the ordered (deterministic) VAE training backward cannot be captured into a graph: building "
+                           "the table index allocates; capture the default (atomic) mode or run this step eagerly")
+    B, G = genes.shape
+    order, seg = table_order(genes, genes_subset, counts_subset, module.input_layer.gene_embedding.weight.shape[0])
+    rows = torch.empty(L.scldm_vae_train_rows_bytes(h, B, genes_subset.shape[1], G), dtype=torch.uint8, device=genes.device)
+    return order, seg, rows
+
+
+class _VAEGaussTrainFn(torch.autograd.Function):
+    """`_VAETrainFn` for the Gaussian head (scldm_vae_train_gaussian_forward / _backward): outputs mu (B, G) and z, fp32.  The loss
+    on top is the reference's `log_gaussian(log1p(counts / rowsum * 1e4), mu).sum(1).mean()` (models.py:239-245) in torch ops, or
+    scldm_amd.distributions.gaussian_recon_loss, the fused form."""
+
+    @staticmethod
+    def forward(ctx, module, counts_subset, genes_subset, genes, *params):
+        L, h = module._native()
+        B, S = counts_subset.shape
+        G = genes.shape[1]
+        dev = counts_subset.device
+        mu = torch.empty(B, G, device=dev, dtype=torch.float32)
+        z = torch.empty(B, module.encoder.latent_dim, module.encoder.latent_embedding, device=dev, dtype=torch.float32)
+        saved = torch.empty(L.scldm_vae_train_saved_bytes(h, B), dtype=torch.uint8, device=dev)
+        ws = torch.empty(L.scldm_vae_train_workspace_bytes(h, B, S, G), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.scldm_vae_train_gaussian_forward(h, counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(), G,
+                                                          mu.data_ptr(), z.data_ptr(), saved.data_ptr(), ws.data_ptr(), _stream_ptr()),
+                       "scldm_vae_train_gaussian_forward")
+        ctx.module, ctx.saved, ctx.ws = module, saved, ws
+        ctx.inputs = (counts_subset, genes_subset, genes)
+        ctx.outs = (mu, z)
+        ctx.params = params
+        ctx.param_versions = [p._version for p in params]
+        return mu, z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmu, dz):
+        module, params = ctx.module, ctx.params
+        L, h = _lib.lib(), module._handle
+        if [p._version for p in params] != ctx.param_versions:
+            raise RuntimeError("TransformerVAE parameters were modified between forward and backward (the HIP backward reads them live)")
+        counts_subset, genes_subset, genes = ctx.inputs
+        mu, z = ctx.outs
+        B, S = counts_subset.shape
+        G = genes.shape[1]
+        dev = mu.device
+        prep = lambda t: None if t is None else t.contiguous().float()
+        dmu, dz = prep(dmu), prep(dz)
+        flat, w, g = _grad_structs(module, params, dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        ordered = _ordered_mode(module)
+        with torch.cuda.device(dev):
+            order = seg = rows = None
+            if ordered:
+                order, seg, rows = _ordered_index(module, L, h, genes, genes_subset, counts_subset)
+            _lib.check(L.scldm_vae_train_gaussian_backward(h, C.byref(w), C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S,
+                                                           genes.data_ptr(), G, mu.data_ptr(), z.data_ptr(), ptr(dmu), ptr(dz),
+                                                           ctx.saved.data_ptr(), ctx.ws.data_ptr(), ptr(order), ptr(seg),
+                                                           order.numel() if ordered else 0, ptr(rows), _stream_ptr()),
+                       "scldm_vae_train_gaussian_backward")
+        module.last_table_gradient_mode = "ordered" if ordered else "atomic"
+        ctx.saved = ctx.ws = None
+        views = _unflatten_dense_tensors(flat, params)
+        out = [v if ctx.needs_input_grad[4 + i] else None for i, v in enumerate(views)]
+        return (None, None, None, None, *out)
+
+
 class TransformerVAE(nn.Module):
     # Gradients of the two embedding tables (gene_embedding, theta) in training: False = float atomics (torch's own embedding
     # backward does the same), True = a fixed-order segmented sum (scldm_vae_train_backward_ordered): with it EVERY gradient is
@@ -144,6 +218,10 @@ class TransformerVAE(nn.Module):
     # (experiments/configs/training/default.yaml:14).  Also on with SCLDM_VAE_DETERMINISTIC=1 (read when the native handle is
     # created) or while torch.are_deterministic_algorithms_enabled().  Ordered steps cannot be captured into a graph.
     deterministic: bool = False
+    # Training of the Gaussian head (GaussianTransformerLayer): False = forward under autograd raises NotImplementedError, as it did
+    # before that head had a backward; True = forward returns differentiable {"mu"}, z through the Gaussian per-gene backward
+    # (scldm_vae_train_gaussian_forward / _backward; `precision` "fp32" only).  `deterministic` selects the ordered mode as for NB.
+    train_gaussian_head: bool = False
     last_table_gradient_mode: str | None = None      # "ordered" / "atomic": the mode of the last backward
 
     def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer | GaussianTransformerLayer,
@@ -389,12 +467,15 @@ class TransformerVAE(nn.Module):
     def forward(self, counts, genes, library_size, counts_subset=None, genes_subset=None):
         """(params, z) with params = {"mu", "theta"}, or {"mu"} for the Gaussian head (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
         are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
-        (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()).  As in the
+        (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()); the Gaussian head with
+        `train_gaussian_head = True`, in fp32 (`_VAEGaussTrainFn`).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.gaussian_head:
-                raise NotImplementedError("the HIP training backward is built for the negative-binomial head; the Gaussian head "
-                                          "(GaussianTransformerLayer) encodes and decodes only - call forward under torch.no_grad()")
+            if self.gaussian_head and not self.train_gaussian_head:
+                raise NotImplementedError("training the Gaussian head (GaussianTransformerLayer) is switched off: set "
+                                          "`train_gaussian_head = True` on the module (fp32), or call forward under torch.no_grad()")
+            if self.gaussian_head and self.precision != "fp32":
+                raise NotImplementedError(f"the Gaussian head trains in fp32 only (precision={self.precision!r})")
             if counts_subset is None or genes_subset is None:
                 raise ValueError("TransformerVAE.forward needs counts_subset / genes_subset (the reference passes them to the input layer, vae.py:37-40)")
             cs = _require_cuda_f32("counts_subset", counts_subset)
@@ -406,6 +487,9 @@ class TransformerVAE(nn.Module):
             if cs.dim() != 2 or gs.shape != cs.shape or g.dim() != 2 or g.shape[0] != cs.shape[0] or lib.shape[0] != cs.shape[0]:
                 raise ValueError(f"expected counts_subset / genes_subset (B,S), genes (B,G), library_size (B,1); got {tuple(cs.shape)}, "
                                  f"{tuple(gs.shape)}, {tuple(g.shape)}, {tuple(library_size.shape)}")
+            if self.gaussian_head:
+                mu, z = _VAEGaussTrainFn.apply(self, cs, gs, g, *tuple(self.parameters()))
+                return {"mu": mu}, z
             if self.decoder_head.theta is None:
                 raise NotImplementedError("the HIP training backward is built for the shared-theta NB head (vae_base.yaml:62); "
                                           "the unshared-theta head (stochastic_layers.py:94-96) decodes only")
