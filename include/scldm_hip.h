@@ -654,7 +654,14 @@ int scldm_normal_sample(const float* mu, float* out, size_t n, unsigned long lon
  *             `w`.  The two embedding tables' gradients (gene_embedding, theta) are scatter-added with float atomics (like torch's
  *             embedding backward); every other gradient is a deterministic two-stage sum.  scldm_vae_train_backward_ordered below
  *             forms the two tables by a fixed-order sum instead: every gradient is then bit-equal run to run.
- * mu / theta / z passed to the backward are the forward's outputs.  Buffers: scldm_vae_train_saved_bytes / _workspace_bytes. */
+ * mu / theta / z passed to the backward are the forward's outputs.  Buffers: scldm_vae_train_saved_bytes / _workspace_bytes.
+ * UNSHARED-THETA head (the handle's weights were loaded with theta == NULL: decoder_head.params is Linear(32, 2), theta = exp of its
+ * second output, stochastic_layers.py:94-116): the same entries, plain, _ex and _ordered, in fp32 and fp16.  `theta` is then the
+ * (B, G) per-element dispersion the forward wrote and `dtheta` its gradient; w->head_w is (2, 32); the backward requires g->head_w
+ * (2, 32) and g->head_b (2) and writes both rows (d loss / d head_b[0] is analytically 0 and comes out as the sum it is); g->theta is
+ * ignored, there is no theta table to fill or to order.  Under SCLDM_PREC_FP16 the cell's power of two comes from max(|d logit|,
+ * |dtheta theta|) and scales both gradient streams.  Query the workspace size after scldm_vae_load_weights: it holds one more (B, G)
+ * array for this head. */
 size_t scldm_vae_train_saved_bytes(const scldm_vae* h, int B);
 size_t scldm_vae_train_workspace_bytes(const scldm_vae* h, int B, int S, int G);
 int scldm_vae_train_forward(scldm_vae* h, const float* counts_subset, const int64_t* genes_subset, int B, int S, const int64_t* genes,

@@ -244,6 +244,49 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   }
 }
 
+// Unshared-theta NB head (theta = exp(l1), one per cell and gene, no table): dl = d loss / d l0 as above, dl2 = d loss / d l1 =
+// dtheta theta (zeros where dtheta is NULL); the two head bias gradients come out of the per-gene kernel's partial.  SCALE: the cell's
+// power of two is taken from max(|dl|, |dl2|) over the cell and scales both streams (same window as head_bwd_kernel<true>).
+template <bool SCALE>
+__global__ __launch_bounds__(256) void head_bwd_nb2_kernel(const float* __restrict__ mu, const float* __restrict__ theta, const float* __restrict__ dmu,
+                                                           const float* __restrict__ dtheta, const float* __restrict__ lib, int G, float inv_temp,
+                                                           float* __restrict__ dl, float* __restrict__ dl2, float* __restrict__ dl_scale) {
+  __shared__ float red[4];
+  __shared__ float amax[4];
+  const int cell = blockIdx.x, tid = threadIdx.x;
+  const size_t base = (size_t)cell * G;
+  float s = 0.f;
+  for (int g = tid; g < G; g += 256) s = fmaf(dmu ? dmu[base + g] : 0.f, mu[base + g], s);
+  s = wave_sum(s);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  const float sc = (red[0] + red[1] + red[2] + red[3]) / lib[cell];
+  float m = 0.f;
+  for (int g = tid; g < G; g += 256) {
+    const float d = dmu ? mu[base + g] * (dmu[base + g] - sc) * inv_temp : 0.f;
+    const float d2 = dtheta ? dtheta[base + g] * theta[base + g] : 0.f;
+    dl[base + g] = d;
+    dl2[base + g] = d2;
+    if constexpr (SCALE) m = fmaxf(m, fmaxf(fabsf(d), fabsf(d2)));
+  }
+  if constexpr (SCALE) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) amax[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+      const float mx = fmaxf(fmaxf(amax[0], amax[1]), fmaxf(amax[2], amax[3]));
+      int e = 0;
+      if (mx > 0.f && mx <= 3.4e38f) {      // (a non-finite row keeps 2^0: the gene kernel's outputs then raise the flag)
+        int ex;
+        (void)frexpf(mx, &ex);
+        e = min(max(kDlScaleLog2 + 1 - ex, -126), 126);
+      }
+      dl_scale[cell] = ldexpf(1.0f, e);
+    }
+  }
+}
+
 // =================================================================================================================================
 // Decoder MCAB, per-gene chain backward (layers.py:305-330 with q = gene embeddings, nnets.py:206-208; NB logit head)
 //   q0 = E[gene]; qn = LN_1q(q0); qq = Wq qn; ao = softmax(qq K^T / sqrt 8) V (4 heads x 8, 16 latent keys of the cell);
@@ -277,6 +320,14 @@ enum : int { GP_HLNW = DP_SIZE, GP_HLNB = GP_HLNW + 32, GP_HEADB = GP_HLNB + 32,
 struct DecBwdGaussArgs {
   DecBwdArgs nb;
   const float *hln_w, *hln_b;   // decoder_head.ln.weight / .bias (32)
+};
+// Unshared-theta NB head (wide::dec_gene_bwd_nb2_kernel): `nb.head_w` is the (2, 32) params weight (row 1 at + 32), `nb.dl` is
+// d loss / d l0 and `dl2` d loss / d l1 = dtheta theta (head_bwd_nb2_kernel); the partial is the NB layout followed by head row 1 and
+// the two bias sums (a layout of its own, as GP_*)
+enum : int { NP_HEADW1 = DP_SIZE, NP_HEADB = NP_HEADW1 + 32, NP_SIZE = NP_HEADB + 32 };
+struct DecBwdNb2Args {
+  DecBwdArgs nb;
+  const float* dl2;             // (B, G)
 };
 
 // =================================================================================================================================

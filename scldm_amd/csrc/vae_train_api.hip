@@ -71,8 +71,12 @@ int check_train_precision(int precision) {
   return SCLDM_OK;
 }
 
+// the NB head without a theta table (decoder_head.params is Linear(32, 2), theta = exp of its second output): routed on the handle,
+// as decode does
+bool unshared_theta(const scldm_vae* h) { return h->loaded && !h->gaussian && !h->theta; }
+
 struct Ws {
-  float *wct, *Q, *dQ, *xs_enc, *xs_dec, *ysave, *kv, *dl, *dz_dec, *dao, *dgq, *bsum, *p_gene, *p_dkv, *p_dcell, *p_ecell, *p_pool, *dl_scale;
+  float *wct, *Q, *dQ, *xs_enc, *xs_dec, *ysave, *kv, *dl, *dz_dec, *dao, *dgq, *bsum, *p_gene, *p_dkv, *p_dcell, *p_ecell, *p_pool, *dl_scale, *dl2;
   int tilesD, chunksD, tilesE, chunksE;
   size_t bytes;
 };
@@ -95,12 +99,14 @@ Ws carve_ws(const scldm_vae* h, int B, int S, int G, void* base) {
   w.dao = k.take((size_t)B * kT * 32);
   w.dgq = k.take((size_t)B * 64);
   w.bsum = k.take((size_t)B);
-  w.p_gene = k.take((size_t)B * w.chunksD * (h->gaussian ? GP_SIZE : DP_SIZE));   // (the Gaussian partial carries the head rows)
+  const bool nb2 = unshared_theta(h);
+  w.p_gene = k.take((size_t)B * w.chunksD * (h->gaussian ? GP_SIZE : nb2 ? NP_SIZE : DP_SIZE));   // (the Gaussian / unshared partials carry the head rows)
   w.p_dkv = k.take((size_t)B * w.chunksD * kT * 64);
   w.p_dcell = k.take((size_t)B * dc_size(L));      // cell-side partials: one per cell
   w.p_ecell = k.take((size_t)B * ec_size(L));
   w.p_pool = k.take((size_t)B * w.chunksE * EP_SIZE);
   w.dl_scale = k.take((size_t)B);      // fp16: per-cell power of two of dl (head_bwd_kernel<true>)
+  w.dl2 = k.take(nb2 ? (size_t)B * G : 0);      // unshared theta: d loss / d l1 per slot
   w.bytes = k.off;
   return w;
 }
@@ -208,8 +214,6 @@ extern "C" int scldm_vae_train_forward_ex(scldm_vae* h, const float* counts_subs
     return fail(SCLDM_ERR_SHAPE, "null argument");
   if (B < 1 || S < 1 || G < 1) return fail(SCLDM_ERR_SHAPE, "need B, S, G >= 1");
   if (h->gaussian) return fail(SCLDM_ERR_SHAPE, "%s", kGaussNoTrain);
-  if (h->loaded && !h->theta)
-    return fail(SCLDM_ERR_STATE, "the training backward is built for the shared-theta NB head (vae_base.yaml:62); the unshared head decodes only");
   hipStream_t st = (hipStream_t)stream_;
   Saved s = carve_saved(B, saved_);
   if (precision == SCLDM_PREC_FP16) {
@@ -267,11 +271,16 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
   rc = check_train(h, w, B, S, G);
   if (rc) return rc;
   const bool f16 = precision == SCLDM_PREC_FP16;
+  const bool nb2 = unshared_theta(h);      // (check_train: the handle is loaded)
   if (!g || !counts_subset || !genes_subset || !genes || !mu || !z || !saved_ || !ws_ || (!gauss && (!library_size || !theta)))
     return fail(SCLDM_ERR_SHAPE, "null argument");
   if (gauss) {
     if (!g->gene_embedding) return fail(SCLDM_ERR_SHAPE, "the gene_embedding gradient table is required");
     if (!w->head_ln_w || !w->head_ln_b || !w->head_w) return fail(SCLDM_ERR_SHAPE, "Gaussian head: head_ln_w, head_ln_b and head_w are required");
+  } else if (nb2) {
+    if (!g->gene_embedding) return fail(SCLDM_ERR_SHAPE, "the gene_embedding gradient table is required");
+    if (!w->head_w || !g->head_w || !g->head_b)
+      return fail(SCLDM_ERR_SHAPE, "unshared-theta head: head_w (2, 32) and the head_w / head_b (2) gradients are required");
   } else if (!g->gene_embedding || !g->theta) return fail(SCLDM_ERR_SHAPE, "the gene_embedding and theta gradient tables are required");
   hipStream_t st = (hipStream_t)stream_;
   const scldm_vae_config& c = h->cfg;
@@ -285,7 +294,7 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
   const Rows rw = carve_rows(B, S, G, rows_);
   if (!ordered) {   // (the ordered reduction writes every table row, the untouched ones as zeros)
     HIP_TRY(hipMemsetAsync(g_emb, 0, (size_t)(c.n_genes + 1) * 32 * 4, st));
-    if (!gauss) HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
+    if (!gauss && !nb2) HIP_TRY(hipMemsetAsync(g_theta, 0, (size_t)(c.n_genes + 1) * 4, st));
   }
   if (f16 && h->found_inf) HIP_TRY(hipMemsetAsync(h->found_inf, 0, sizeof(float), st));
 
@@ -325,6 +334,10 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_mfma2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::M_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_gauss_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::MG_BYTES));
       HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_gauss_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::MG_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_nb2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::N_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_nb2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::N_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_nb2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::N_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)wide::dec_gene_bwd_nb2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wide::N_BYTES));
       if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
     }
   }
@@ -366,6 +379,9 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
   // gradient comes out of the per-gene kernel's partial, and there is no theta)
   if (gauss) {
     if (!dmu) HIP_TRY(hipMemsetAsync(k.dl, 0, (size_t)B * G * sizeof(float), st));
+  } else if (nb2) {      // d l0 | d l1 per slot; no theta table, and both bias sums come out of the per-gene kernel's partial
+    if (f16) head_bwd_nb2_kernel<true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, G, 1.0f / c.nb_temperature, k.dl, k.dl2, k.dl_scale);
+    else head_bwd_nb2_kernel<false><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, G, 1.0f / c.nb_temperature, k.dl, k.dl2, nullptr);
   } else if (ordered) {
     if (f16) head_bwd_kernel<true, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, k.dl_scale);
     else head_bwd_kernel<false, true><<<B, 256, 0, st>>>(mu, theta, dmu, dtheta, library_size, nullptr, G, 1.0f / c.nb_temperature, k.dl, rw.theta, k.bsum, nullptr);
@@ -382,6 +398,17 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
     DecBwdGaussArgs gg{ga, w->head_ln_w, w->head_ln_b};
     if (ordered) wide::dec_gene_bwd_gauss_kernel<true><<<dim3(k.chunksD, B), wide::kThreads, wide::MG_BYTES, st>>>(gg);
     else wide::dec_gene_bwd_gauss_kernel<false><<<dim3(k.chunksD, B), wide::kThreads, wide::MG_BYTES, st>>>(gg);
+  } else if (nb2) {
+    if (f16) {
+      ga.dl_scale = k.dl_scale;
+      ga.found_inf = h->found_inf;
+    }
+    DecBwdNb2Args gn{ga, k.dl2};
+    const dim3 grid(k.chunksD, B);
+    if (f16 && ordered) wide::dec_gene_bwd_nb2_kernel<true, true><<<grid, wide::kThreads, wide::N_BYTES, st>>>(gn);
+    else if (f16) wide::dec_gene_bwd_nb2_kernel<true><<<grid, wide::kThreads, wide::N_BYTES, st>>>(gn);
+    else if (ordered) wide::dec_gene_bwd_nb2_kernel<false, true><<<grid, wide::kThreads, wide::N_BYTES, st>>>(gn);
+    else wide::dec_gene_bwd_nb2_kernel<false><<<grid, wide::kThreads, wide::N_BYTES, st>>>(gn);
   } else if (f16) {
     ga.dl_scale = k.dl_scale;
     ga.found_inf = h->found_inf;
@@ -410,7 +437,7 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
     // The theta table walks the same segments and takes the decoder entries (those below B * G) only.
     const int n_table = c.n_genes + 1, n_dec = B * G;
     table_rows_reduce_kernel<<<n_table, 256, 0, st>>>(rw.emb, order, seg, n_table, n_entries, n_dec + B * S, g_emb);
-    if (!gauss) table_scalars_reduce_kernel<<<cdiv(n_table, 32), 256, 0, st>>>(rw.theta, order, seg, n_table, n_entries, n_dec, g_theta);
+    if (!gauss && !nb2) table_scalars_reduce_kernel<<<cdiv(n_table, 32), 256, 0, st>>>(rw.theta, order, seg, n_table, n_entries, n_dec, g_theta);
     LAUNCH_CHECK();
   }
 
@@ -436,6 +463,10 @@ int train_backward_impl(scldm_vae* h, const scldm_vae_weights* w, const scldm_va
       j.vec(G_(g->head_ln_b), GP_HLNB, 32);
       j.vec(G_(g->head_b), GP_HEADB, 1);
       if ((rc = j.run(k.p_gene, B * k.chunksD, GP_SIZE, s2))) return rc;
+    } else if (nb2) {
+      j.vec(G_(g->head_w) + 32, NP_HEADW1, 32);
+      j.vec(G_(g->head_b), NP_HEADB, 2);
+      if ((rc = j.run(k.p_gene, B * k.chunksD, NP_SIZE, s2))) return rc;
     } else {
       if ((rc = j.run(k.p_gene, B * k.chunksD, DP_SIZE, s2))) return rc;
       Jobs jb;

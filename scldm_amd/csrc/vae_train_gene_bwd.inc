@@ -1,5 +1,6 @@
 // Body of the per-gene decoder backward kernels of vae_train_wide.hpp (the header there explains the phases).  The including kernel
-// defines: `a` (DecBwdArgs), F16, ROWS, GAUSS (the Gaussian head: see dec_gene_bwd_gauss_kernel) and hln_w / hln_b (GAUSS only).
+// defines: `a` (DecBwdArgs), F16, ROWS, GAUSS (the Gaussian head: see dec_gene_bwd_gauss_kernel) and hln_w / hln_b (GAUSS only),
+// NB2 (the unshared-theta NB head: see dec_gene_bwd_nb2_kernel) and dl2 (NB2 only).
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int tid = threadIdx.x, tok = tid >> 4, j = tid & 15, chunk = blockIdx.x, cell = blockIdx.y, nch = gridDim.x;
   const int wave = tid >> 6, li = tid & 15, g4 = (tid & 63) >> 4;      // MFMA roles: lane = (li, g4)
@@ -35,20 +36,39 @@
         for (int i = 0; i < 32; ++i) s = fmaf(a.mlp.wct[tid * 32 + i], a.head_w[i], s);
       S[M_C0 + tid] = s;
     }
+    if constexpr (NB2) {
+      if (tid < 96) {      // c1[u] = sum_i Wc[i][u] w_head[1][i]
+        float s = 0.f;
+        if (tid < H)
+          for (int i = 0; i < 32; ++i) s = fmaf(a.mlp.wct[tid * 32 + i], a.head_w[32 + i], s);
+        S[G_DB + tid] = s;      // (passes through the DB rows into registers, see below)
+      }
+      if (tid < 32) S[N_W1 + tid] = a.head_w[32 + tid];
+    }
   }
   const float l1w0 = a.ln1q_w[j], l1w1 = a.ln1q_w[j + 16], l1b0 = a.ln1q_b[j], l1b1 = a.ln1q_b[j + 16];
   const float l2w0 = a.ln2_w[j], l2w1 = a.ln2_w[j + 16], l2b0 = a.ln2_b[j], l2b1 = a.ln2_b[j + 16];
   const float hw0 = GAUSS ? head_vec(j) : a.head_w[j], hw1 = GAUSS ? head_vec(j + 16) : a.head_w[j + 16];
   __syncthreads();
+  // NB2: a lane reads only the c1 entries of its two hidden-unit tiles, so they live in registers (the DB rows are first written in
+  // phase A, barriers later); the second gradient row and head row 1 sit behind the NB map (N_DL2, N_W1)
+  float c1u[2] = {0.f, 0.f};
+  if constexpr (NB2) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      if (wave + 4 * q < 6) c1u[q] = S[G_DB + 16 * (wave + 4 * q) + li];
+  }
   f32x4 gw1[3] = {z4(), z4(), z4()}, gw2[3] = {z4(), z4(), z4()}, gq = z4(), gp = z4(), gk = z4(), gv = z4();
   // GAUSS: sum (beta xhat) (x) hid, tiles D[feature 16 (wave & 1) + 4 g4 + r][unit 16 ((wave >> 1) + 2 n) + li]; a | b of phase A;
   // alpha of this lane's gene; the running sum Q of g
   f32x4 gwc[3] = {z4(), z4(), z4()}, ga_[2] = {z4(), z4()}, gb_[2] = {z4(), z4()};
   float alpha = 0.f, qsum = 0.f;
   float cacc[2] = {0.f, 0.f};   // c[u] partials of this lane's gene quad, hidden-unit tiles wave, wave + 4
-  float vs[10];                 // running sums of this lane's gene slot: ln1q w|b, ln2 w|b, head (two features each)
+  float cacc1[2] = {0.f, 0.f};  // NB2: C1 = sum d1 hid likewise
+  constexpr int NV = NB2 ? 12 : 10;
+  float vs[NV];                 // running sums of this lane's gene slot: ln1q w|b, ln2 w|b, head (two features each); NB2: head row 1
 #pragma unroll
-  for (int i = 0; i < 10; ++i) vs[i] = 0.f;
+  for (int i = 0; i < NV; ++i) vs[i] = 0.f;
   const int half = wave & 1, kh = wave >> 1;     // the small products' roles: (output half, k half)
   // x W^T with k along both images' rows: partial over input features 16 kh .. + 15 of output half `half`, D[gene 4 g4 + r][16 half + li]
   auto lin_partial = [&](int x_rows, int w_rows, int dst_rows) {
@@ -97,7 +117,7 @@
   const int rot = nsteps > 0 ? (int)(((unsigned)cell * 37u) % (unsigned)nsteps) : 0;
   auto first_gene = [&](int step) { return begin + 16 * ((step + rot) % nsteps); };
   long long gene_nx = 0, gene_n2 = 0;
-  float dl_nx = 0.f, e0_nx = 0.f, e1_nx = 0.f;
+  float dl_nx = 0.f, dl2_nx = 0.f, e0_nx = 0.f, e1_nx = 0.f;
   // F16: dl enters scaled by the cell's 2^e (so that the gradient operands sit in the fp16 range); every output leaves times 2^-e
   float dl_sc = 1.f;
   bool bad = false;     // F16: a non-finite value in this workgroup's outputs
@@ -108,6 +128,10 @@
     gene_n2 = a.genes[slot(first_gene(1))];
     dl_nx = ga + tok < end ? a.dl[slot(ga)] : 0.f;
     if constexpr (F16) dl_nx *= dl_sc;
+    if constexpr (NB2) {
+      dl2_nx = ga + tok < end ? dl2[slot(ga)] : 0.f;
+      if constexpr (F16) dl2_nx *= dl_sc;
+    }
     e0_nx = a.emb[(size_t)gene_nx * 32 + j];
     e1_nx = a.emb[(size_t)gene_nx * 32 + j + 16];
   }
@@ -124,6 +148,11 @@
     if constexpr (F16) dl_nx *= dl_sc;
     gene_n2 = a.genes[slot(first_gene(step + 2))];
     if (!GAUSS && j == 0) S[M_DL + tok] = dlog;      // (GAUSS: dlog is g = d loss / d mu; M_DL gets alpha in phase H)
+    if constexpr (NB2) {
+      if (j == 1) S[N_DL2 + tok] = dl2_nx;      // (d1 of this step is read back from the row where it is needed: one register less)
+      dl2_nx = g1 + tok < end ? dl2[slot(g1)] : 0.f;
+      if constexpr (F16) dl2_nx *= dl_sc;
+    }
     const Ln n1 = ln_own(q00, q01, a.eps);
     S[G_QN + tok * kP + j] = fmaf(n1.h0, l1w0, l1b0);
     S[G_QN + tok * kP + j + 16] = fmaf(n1.h1, l1w1, l1b1);
@@ -225,6 +254,18 @@
             gb_[q] = bb;
 #pragma unroll
             for (int r = 0; r < 4; ++r) S[X_HID + (4 * g4 + r) * kQ + 16 * ot + li] = aa[r] * sigm(aa[r]) * bb[r];
+          } else if constexpr (NB2) {     // d hid = d0 c0 + d1 c1; C0 | C1 running sums
+          const float c0u = S[M_C0 + 16 * ot + li];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int tk = 4 * g4 + r;
+            const float dl = S[M_DL + tk], dk = S[N_DL2 + tk], sg = sigm(aa[r]), sa = aa[r] * sg, dh = fmaf(dl, c0u, dk * c1u[q]);
+            const float hd = sa * bb[r];
+            cacc[q] = fmaf(dl, hd, cacc[q]);
+            cacc1[q] = fmaf(dk, hd, cacc1[q]);
+            S[G_DA + tk * kQ + 16 * ot + li] = dh * bb[r] * (sg * (1.0f + aa[r] * (1.0f - sg)));
+            S[G_DB + tk * kQ + 16 * ot + li] = dh * sa;
+          }
           } else {
           const float c0u = S[M_C0 + 16 * ot + li];
 #pragma unroll
@@ -362,6 +403,12 @@
       d0 = fmaf(dlog, hw0, d0);
       d1 = fmaf(dlog, hw1, d1);
       }
+      if constexpr (NB2) {     // head row 1: d yo = d0 w0 + d1 w1, and its running sums
+        const float dlog1 = S[N_DL2 + tok];
+        vs[NV - 2] = fmaf(dlog1, y0, vs[NV - 2]); vs[NV - 1] = fmaf(dlog1, y1, vs[NV - 1]);
+        d0 = fmaf(dlog1, S[N_W1 + j], d0);
+        d1 = fmaf(dlog1, S[N_W1 + j + 16], d1);
+      }
     }
     S[G_DY + tok * kP + j] = d0;
     S[G_DY + tok * kP + j + 16] = d1;
@@ -488,10 +535,12 @@
       vs[0] = fmaf(t0, n1.h0, vs[0]); vs[1] = fmaf(t1, n1.h1, vs[1]); vs[2] += t0; vs[3] += t1;
       float o0, o1;
       ln_back(n1, t0 * l1w0, t1 * l1w1, o0, o1);
+      // (a gene whose gradients are zero adds nothing; NB2: the d1 row is next written by this wave's own S0, after this read)
+      const bool live = NB2 ? (dlog != 0.f || S[N_DL2 + tok] != 0.f) : dlog != 0.f;
       if constexpr (ROWS) {
         if (valid) {
           float v0 = 0.f, v1 = 0.f;
-          if (dlog != 0.f) {
+          if (live) {
             v0 = d0 + o0;
             v1 = d1 + o1;
             if constexpr (F16) {
@@ -504,7 +553,7 @@
           row[j] = v0;
           row[j + 16] = v1;
         }
-      } else if (valid && dlog != 0.f) {
+      } else if (valid && live) {
         float* ge = a.g_emb + (size_t)gene * 32;
         float v0 = d0 + o0, v1 = d1 + o1;
         if constexpr (F16) {
@@ -538,12 +587,15 @@
     for (int n = 0; n < 3; ++n) { fix(gw1[n]); fix(gw2[n]); }
     fix(gq); fix(gp); fix(gk); fix(gv);
 #pragma unroll
-    for (int i = 0; i < 10; ++i) vs[i] *= inv;
+    for (int i = 0; i < NV; ++i) vs[i] *= inv;
 #pragma unroll
     for (int q = 0; q < 2; ++q) cacc[q] *= inv;
+    if constexpr (NB2) {
+      cacc1[0] *= inv; cacc1[1] *= inv;
+    }
   }
   // ---- one partial per workgroup (as dec_gene_bwd_mfma_kernel)
-  float* P = a.part + (size_t)(cell * nch + chunk) * (GAUSS ? GP_SIZE : DP_SIZE);
+  float* P = a.part + (size_t)(cell * nch + chunk) * (GAUSS ? GP_SIZE : NB2 ? NP_SIZE : DP_SIZE);
   {
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
@@ -567,9 +619,9 @@
     }
   }
   float* R = S;
-  float* RC = S + 16 * 10 * 16;
+  float* RC = S + 16 * NV * 16;
 #pragma unroll
-  for (int i = 0; i < 10; ++i) R[(tok * 10 + i) * 16 + j] = vs[i];
+  for (int i = 0; i < NV; ++i) R[(tok * NV + i) * 16 + j] = vs[i];
 #pragma unroll
   for (int q = 0; q < 2; ++q)
     if (wave + 4 * q < 6) RC[g4 * 96 + 16 * (wave + 4 * q) + li] = cacc[q];
@@ -577,15 +629,40 @@
   if constexpr (GAUSS) {
     if (j == 0) RQ[tok] = qsum;
   }
+  float* RC1 = RC + 4 * 96;     // NB2: C1 partials, then the four waves' partial bias sums
+  float* RB = RC1 + 4 * 96;
+  if constexpr (NB2) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      if (wave + 4 * q < 6) RC1[g4 * 96 + 16 * (wave + 4 * q) + li] = cacc1[q];
+    // d b_k = sum over the chunk's slots of d_k as the head pass wrote them (unscaled under F16): one more pass over values the
+    // L2 still holds, instead of two more registers across the gene loop
+    float b0 = 0.f, b1 = 0.f;
+    for (int g = begin + tid; g < end; g += kThreads) {
+      b0 += a.dl[(size_t)cell * a.G + g];
+      b1 += dl2[(size_t)cell * a.G + g];
+    }
+    b0 = wave_sum(b0);
+    b1 = wave_sum(b1);
+    if ((tid & 63) == 0) { RB[wave] = b0; RB[4 + wave] = b1; }
+  }
   __syncthreads();
   float sum = 0.f;
   const int vi = tid >> 4;
-  if (vi < 10) {
+  if (vi < NV) {
 #pragma unroll
-    for (int t = 0; t < kT; ++t) sum += R[(t * 10 + vi) * 16 + j];
+    for (int t = 0; t < kT; ++t) sum += R[(t * NV + vi) * 16 + j];
   }
   float cu = 0.f;
   if (tid < 96) cu = (RC[tid] + RC[96 + tid]) + (RC[192 + tid] + RC[288 + tid]);
+  float cu1 = 0.f;
+  if constexpr (NB2) {
+    if (tid < 96) cu1 = (RC1[tid] + RC1[96 + tid]) + (RC1[192 + tid] + RC1[288 + tid]);
+    if (vi == 12 && j < 2) {      // d b_0 | d b_1
+      sum = (RB[4 * j] + RB[4 * j + 1]) + (RB[4 * j + 2] + RB[4 * j + 3]);
+    }
+    if constexpr (F16) bad |= !__builtin_isfinite(cu1);
+  }
   if constexpr (F16) {
     bad |= !(__builtin_isfinite(sum) && __builtin_isfinite(cu));
     if (bad && a.found_inf) *a.found_inf = 1.0f;
@@ -593,6 +670,13 @@
   __syncthreads();
   float* C = S;            // c[u]
   float* HD = S + 128;     // sum dlogit * y
+  float* C1 = S + 160;     // NB2: c1[u], sum d1 * y
+  float* HD1 = S + 256;
+  if constexpr (NB2) {
+    if (tid < 96) C1[tid] = cu1;
+    if (vi == 10 || vi == 11) HD1[j + 16 * (vi & 1)] = sum;
+    if (vi == 12 && j < 2) P[NP_HEADB + j] = sum;
+  }
   if (tid < 96) C[tid] = cu;
   if (vi < 10) {
     const int f = j + 16 * (vi & 1);
@@ -623,6 +707,16 @@
         P[DP_WC + f * kHP + 16 * it + li] = fmaf(head_vec(f), C[16 * it + li], gwc[n][r]);
       }
     }
+  } else if constexpr (NB2) {     // d w_k = sum d_k y + Wc C_k;  d Wc = w0 (x) C0 + w1 (x) C1
+    if (tid < 64) {
+      const int k = tid >> 5, f = tid & 31;
+      const float* Ck = k ? C1 : C;
+      float s2 = k ? HD1[f] : HD[f];
+      for (int u = 0; u < H; ++u) s2 = fmaf(a.mlp.wct[u * 32 + f], Ck[u], s2);
+      P[(k ? NP_HEADW1 : DP_HEADW) + f] = s2;
+    }
+    for (int idx = tid; idx < 32 * kHP; idx += kThreads)
+      P[DP_WC + idx] = fmaf(a.head_w[idx / kHP], C[idx % kHP], a.head_w[32 + idx / kHP] * C1[idx % kHP]);
   } else {
   if (tid < 32) {
     float s2 = HD[tid];

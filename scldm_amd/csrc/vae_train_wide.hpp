@@ -842,6 +842,10 @@ static_assert(M_BYTES <= 80 * 1024, "two workgroups per CU");
 constexpr int X_WC = M_FLOATS, X_HID = X_WC + 96 * kP, X_XB = X_HID + 16 * kQ, X_FLOATS = X_XB + 16 * kP;
 constexpr int MG_BYTES = X_FLOATS * 4;
 static_assert(MG_BYTES <= 160 * 1024, "one workgroup per CU");
+// the unshared-theta NB form's floats behind the NB map (dec_gene_bwd_nb2_kernel): the second gradient row, head row 1
+constexpr int N_DL2 = M_FLOATS, N_W1 = N_DL2 + 16, N_FLOATS = N_W1 + 32;
+constexpr int N_BYTES = N_FLOATS * 4;
+static_assert(N_BYTES <= 80 * 1024, "two workgroups per CU (unshared-theta form)");
 __device__ __forceinline__ f32x4 mfma16(float x, float y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0); }
 #ifndef SCLDM_VAE_PHASE_CLOCKS
 #define SCLDM_VAE_PHASE_CLOCKS 0   // 1: one workgroup prints its cycles per phase of dec_gene_bwd_mfma2_kernel (tools only)
@@ -873,9 +877,10 @@ __device__ __forceinline__ f32x4 mfma32h(f16x8 x, f16x8 y, f32x4 c) { return __b
 // The body is vae_train_gene_bwd.inc, shared with the Gaussian-head kernel below (GAUSS, hln_w / hln_b are the include's parameters).
 template <bool F16, bool ROWS = false>
 __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const DecBwdArgs a) {
-  constexpr bool GAUSS = false;
+  constexpr bool GAUSS = false, NB2 = false;
   const float* const hln_w = nullptr;
   const float* const hln_b = nullptr;
+  const float* const dl2 = nullptr;
 #include "vae_train_gene_bwd.inc"
 }
 
@@ -898,10 +903,34 @@ __global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_mfma2_kernel(const D
 // LDS: the NB map + a 96 x kP image of Wc^T + the HID and XB rows = 104 128 bytes, so ONE workgroup per CU (up to 512 registers).
 template <bool ROWS>
 __global__ __launch_bounds__(kThreads, 1) void dec_gene_bwd_gauss_kernel(const DecBwdGaussArgs ga) {
-  constexpr bool GAUSS = true, F16 = false;
+  constexpr bool GAUSS = true, F16 = false, NB2 = false;
   const DecBwdArgs& a = ga.nb;
   const float* const hln_w = ga.hln_w;
   const float* const hln_b = ga.hln_b;
+  const float* const dl2 = nullptr;
+#include "vae_train_gene_bwd.inc"
+}
+
+// ---- unshared-theta NB head (stochastic_layers.py:94-116): params is Linear(32, 2); l0 = w0 . yo + b0 is the softmax logit, theta =
+// exp(l1) with l1 = w1 . yo + b1, one dispersion per cell and gene.  With d0 = d loss / d l0 (the shared head's d logit) and
+// d1 = d loss / d l1 = dtheta theta the gradient entering the MLP is RANK TWO per gene, and both head vectors are launch constants:
+//   d yo  = d0 w0 + d1 w1
+//   d hid = d0 c0 + d1 c1, c_k = Wc^T w_k                    (two 96-vectors per launch)
+//   d Wc  = w0 (x) C0 + w1 (x) C1, C_k = sum_genes d_k hid   (two 96-vectors of running sums)
+//   d w_k = sum d_k y + Wc C_k,  d b_k = sum d_k             (the MLP output is never formed)
+// so Wc stays out of the per-gene path and no MFMA is added to the shared head's 416 per step: a third kernel over the same body
+// text (NB2; the two kernels above keep their symbols and instructions).  Per step it prefetches d1 beside d0, keeps a second
+// gradient row, folds d1 c1 into phase A's d hid, and carries C1 and head row 1 as running sums; the two bias sums are one pass
+// over the chunk's d0 | d1 at the flush (two registers less across the gene loop: the fp32 forms sit at 256).  LDS: the NB map
+// + the second gradient row and head row 1 (192 bytes of the 320 that were left); c1 does not fit beside c0, but a lane reads only
+// the entries of its own two hidden-unit tiles, so after the prologue they live in two registers: N_BYTES, two workgroups per CU.
+template <bool F16, bool ROWS = false>
+__global__ __launch_bounds__(kThreads, 2) void dec_gene_bwd_nb2_kernel(const DecBwdNb2Args na) {
+  constexpr bool GAUSS = false, NB2 = true;
+  const DecBwdArgs& a = na.nb;
+  const float* const hln_w = nullptr;
+  const float* const hln_b = nullptr;
+  const float* const dl2 = na.dl2;
 #include "vae_train_gene_bwd.inc"
 }
 

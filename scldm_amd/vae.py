@@ -222,6 +222,11 @@ class TransformerVAE(nn.Module):
     # before that head had a backward; True = forward returns differentiable {"mu"}, z through the Gaussian per-gene backward
     # (scldm_vae_train_gaussian_forward / _backward; `precision` "fp32" only).  `deterministic` selects the ordered mode as for NB.
     train_gaussian_head: bool = False
+    # Training of the unshared-theta NB head (NegativeBinomialTransformerLayer(shared_theta=False): params is Linear(32, 2), theta =
+    # exp of its second output, no table): False = forward under autograd raises NotImplementedError, as it did before that head had a
+    # backward; True = forward returns differentiable {"mu", "theta"}, z through `_VAETrainFn` (the C entries route on the handle:
+    # wide::dec_gene_bwd_nb2_kernel), `precision` "fp32" or "fp16", `deterministic` as for the shared head.
+    train_unshared_theta: bool = False
     last_table_gradient_mode: str | None = None      # "ordered" / "atomic": the mode of the last backward
 
     def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer | GaussianTransformerLayer,
@@ -468,7 +473,8 @@ class TransformerVAE(nn.Module):
         """(params, z) with params = {"mu", "theta"}, or {"mu"} for the Gaussian head (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
         are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
         (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()); the Gaussian head with
-        `train_gaussian_head = True`, in fp32 (`_VAEGaussTrainFn`).  As in the
+        `train_gaussian_head = True`, in fp32 (`_VAEGaussTrainFn`); the unshared-theta NB head with `train_unshared_theta = True`
+        (`_VAETrainFn`: theta is then the per-element (B, G) dispersion).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if self.gaussian_head and not self.train_gaussian_head:
@@ -490,9 +496,10 @@ class TransformerVAE(nn.Module):
             if self.gaussian_head:
                 mu, z = _VAEGaussTrainFn.apply(self, cs, gs, g, *tuple(self.parameters()))
                 return {"mu": mu}, z
-            if self.decoder_head.theta is None:
-                raise NotImplementedError("the HIP training backward is built for the shared-theta NB head (vae_base.yaml:62); "
-                                          "the unshared-theta head (stochastic_layers.py:94-96) decodes only")
+            if self.decoder_head.theta is None and not self.train_unshared_theta:
+                raise NotImplementedError("the HIP training backward runs the shared-theta NB head (vae_base.yaml:62) by default; training "
+                                          "the unshared-theta head (stochastic_layers.py:94-96) is switched off: set "
+                                          "`train_unshared_theta = True` on the module, or call forward under torch.no_grad()")
             if self.precision not in ("fp32", "fp16"):
                 raise NotImplementedError(f"TransformerVAE training runs in fp32 or fp16 (precision={self.precision!r})")
             params = tuple(self.parameters())
