@@ -297,6 +297,78 @@ int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ulabels, int 
 int scldm_sde_noise(float* out, long long n_rows_local, int e, unsigned long long seed, int step, int half, long long cell_offset,
                     long long cells_total, void* stream);
 
+/* Adaptive Dormand-Prince 5(4) sampling: the reference's DEFAULT sampler (`sample_ode()` with no arguments -> torchdiffeq dopri5 at
+ * atol = rtol = 1e-5: transport.py:324-331, integrators.py:100-112) over forward_with_cfg, as one call.  Semantics are those of
+ * scldm_amd.transport.Sampler._sample_dopri5, decision for decision and bit for bit: FSAL tableau, ONE step size for the whole
+ * (2B, S, Din) state, mixed rms error ratio, accept iff ratio <= 1, h *= 10 for ratio == 0 and otherwise
+ * h *= min(10, max(0.9 / ratio^0.2, ratio < 1 ? 1 : 0.2)), steps never clipped to the save times, the quartic interpolant of the last
+ * accepted step evaluated at the fp32 linspace(0, 1, num_save) save times.  Times and step sizes are host float64; a stage time is
+ * rounded to fp32 once; a tableau weight is (float)(h * w) formed in double (structural zeros skipped); state arithmetic is fp32 with
+ * every product and sum rounded on its own.
+ * z (2B,S,Din): in, and out = the state at t = 1 (first B rows unconditional, last B guided); labels / passes as scldm_sample_ode.
+ * first_step > 0: the first attempted step; <= 0: the automatic initial step (Hairer / Norsett / Wanner), which costs one more
+ *   evaluation, f(t0 + h0, y0 + h0 f0), beside the f(t0, y0) every solve starts with.
+ * traj: NULL, or device (num_save, 2B, S*Din) receiving every save point, traj[0] being the initial z.
+ * stats (host, may be NULL) and step_log (host (step_log_cap, 3) doubles: t0, dt, accepted (1.0 / 0.0) of each attempted step in
+ *   order, at most step_log_cap of them; may be NULL) describe the solve.
+ * ws: scldm_sample_ode_dopri5_workspace_bytes(h, B, n_pass, n_urows) bytes, 256-byte aligned; it holds the slopes k1..k7, two state
+ *   buffers and the four interpolation coefficients (an accepted step swaps pointers, nothing is copied) and the adaLN vectors of one
+ *   step's six new evaluations (prepared in one batched pass per attempted step).
+ * The call reads the error ratio once per attempted step: it synchronises `stream` that often and CANNOT be captured into a graph.
+ * SCLDM_ERR_SHAPE with nothing launched: a handle outside the fused family (checked before any HIP call), num_save < 2, atol <= 0 or
+ *   rtol < 0, B < 1, NULL z / ws, an unknown precision, a capturing stream.  SCLDM_ERR_STATE: weights not loaded.
+ * SCLDM_ERR_SOLVER: the step size underflowed (t + h == t) or more than 100 000 evaluations were made; z, traj and stats hold what the
+ *   solve had reached (stats->status says which). */
+#define SCLDM_ERR_SOLVER (-4)
+#define SCLDM_DOPRI5_OK 0
+#define SCLDM_DOPRI5_UNDERFLOW 1
+#define SCLDM_DOPRI5_MAX_EVALS 2
+typedef struct {
+  long long evaluations;   /* model evaluations (one CFG evaluation = one) */
+  long long accepted, rejected;   /* attempted steps by outcome */
+  double first_step;       /* the first attempted step size */
+  int status;              /* SCLDM_DOPRI5_* */
+  int step_log_len;        /* rows written to step_log */
+} scldm_dopri5_stats;
+size_t scldm_sample_ode_dopri5_workspace_bytes(const scldm_dit* h, int B, int n_pass, int n_urows);
+int scldm_sample_ode_dopri5(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                            const uint32_t* pass_mask, const float* pass_scale, int num_save, double atol, double rtol, double first_step,
+                            float* traj, scldm_dopri5_stats* stats, double* step_log, int step_log_cap, int precision, void* ws,
+                            void* stream);
+/* The same solve with the save times given: save_times is a HOST array of num_save non-decreasing fp32 times, the first 0.
+ * scldm_sample_ode_dopri5 forms them itself as start + step * i below the middle and end - step * (n - 1 - i) from it on, in fp32 - the
+ * element-wise definition of torch.linspace, which torch's vectorised CPU kernel does not reproduce to the last bit at every index; a
+ * caller that wants the interpolant at exactly the values ITS linspace holds (scldm_amd does: the host-composed solver and the
+ * reference take them from torch on the host) passes them here.  The steps never depend on the save times. */
+int scldm_sample_ode_dopri5_at(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                               const uint32_t* pass_mask, const float* pass_scale, int num_save, const float* save_times, double atol,
+                               double rtol, double first_step, float* traj, scldm_dopri5_stats* stats, double* step_log, int step_log_cap,
+                               int precision, void* ws, void* stream);
+
+/* The solve's controller, handle-free and without a HIP call (csrc/dopri5_ctl.hpp): what the host decides between the kernels.
+ * scldm_dopri5_stage_plan: for an attempted step from t0 with size h - the fp32 times of the six new evaluations, the fp32 weights
+ *   (float)(h * w) of the six stage points (a[i][j]: slope j in stage point i), of the error estimate and of the mid-point, with a mask
+ *   bit per weight that is NOT a structural zero of the tableau, and (float)h, (float)(2h) for the interpolant.
+ * scldm_dopri5_control: after that step, given its error ratio - accepted or not, where the next step starts (t1), its size, and
+ *   whether that next step underflows (t1 + h_next == t1).
+ * scldm_dopri5_initial_h0 / _initial_step: the automatic first step from d0 = rms(y0 / scale), d1 = rms(f0 / scale) (the trial step
+ *   h0), then from d2 = rms((f(t0 + h0, y0 + h0 f0) - f0) / scale) / h0; scale = atol + rtol |y0|. */
+typedef struct {
+  float t_stage[6];
+  float a[6][7];
+  float err[7], mid[7];
+  unsigned a_mask[6], err_mask, mid_mask;
+  float h, two_h;
+} scldm_dopri5_plan;
+typedef struct {
+  int accepted, underflow;
+  double t1, h_next;
+} scldm_dopri5_control_out;
+void scldm_dopri5_stage_plan(double t0, double h, scldm_dopri5_plan* out);
+void scldm_dopri5_control(double t0, double h, double ratio, scldm_dopri5_control_out* out);
+double scldm_dopri5_initial_h0(double d0, double d1);
+double scldm_dopri5_initial_step(double h0, double d1, double d2);
+
 /* Options of a handle (read by the calls that follow).
  * SCLDM_OPT_CFG1_DIRECT (default 0): with ONE conditional pass of guidance scale exactly 1.0 and a scalar t (scldm_sample_ode,
  *   scldm_dit_forward_cfg with t_stride 0), DiT.forward_with_cfg's guided half u2 + 1.0 * (c2 - u2) (nnets.py:368,376) is c2 up to

@@ -76,6 +76,26 @@ class TrainStepBuffers(C.Structure):
                                                                       "ticket", "saved", "ws")]
 
 
+class Dopri5Stats(C.Structure):
+    """scldm_dopri5_stats (include/scldm_hip.h)."""
+    _fields_ = [("evaluations", C.c_longlong), ("accepted", C.c_longlong), ("rejected", C.c_longlong), ("first_step", C.c_double),
+                ("status", C.c_int), ("step_log_len", C.c_int)]
+
+
+class Dopri5Plan(C.Structure):
+    """scldm_dopri5_plan (include/scldm_hip.h)."""
+    _fields_ = [("t_stage", C.c_float * 6), ("a", (C.c_float * 7) * 6), ("err", C.c_float * 7), ("mid", C.c_float * 7),
+                ("a_mask", C.c_uint * 6), ("err_mask", C.c_uint), ("mid_mask", C.c_uint), ("h", C.c_float), ("two_h", C.c_float)]
+
+
+class Dopri5Control(C.Structure):
+    """scldm_dopri5_control_out (include/scldm_hip.h)."""
+    _fields_ = [("accepted", C.c_int), ("underflow", C.c_int), ("t1", C.c_double), ("h_next", C.c_double)]
+
+
+ERR_SOLVER = -4   # SCLDM_ERR_SOLVER
+
+
 class ScldmError(RuntimeError):
     pass
 
@@ -140,6 +160,21 @@ def lib() -> C.CDLL:
     L.scldm_sample_sde.argtypes = [C.c_void_p, C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), c_float_p,
                                    C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_longlong,
                                    C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_sample_ode_dopri5_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.scldm_sample_ode_dopri5_workspace_bytes.restype = C.c_size_t
+    L.scldm_sample_ode_dopri5.argtypes = [C.c_void_p, C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), c_float_p,
+                                          C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.POINTER(Dopri5Stats), C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p]
+    a = L.scldm_sample_ode_dopri5.argtypes
+    L.scldm_sample_ode_dopri5_at.argtypes = a[:10] + [c_float_p] + a[10:]     # the same call with the host array of save times after num_save
+    L.scldm_dopri5_stage_plan.argtypes = [C.c_double, C.c_double, C.POINTER(Dopri5Plan)]
+    L.scldm_dopri5_stage_plan.restype = None
+    L.scldm_dopri5_control.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(Dopri5Control)]
+    L.scldm_dopri5_control.restype = None
+    L.scldm_dopri5_initial_h0.argtypes = [C.c_double, C.c_double]
+    L.scldm_dopri5_initial_h0.restype = C.c_double
+    L.scldm_dopri5_initial_step.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.scldm_dopri5_initial_step.restype = C.c_double
     L.scldm_sde_noise.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
     L.scldm_mfma_sustained_tflops.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.scldm_dit_block_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -268,7 +303,9 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_vae_train_split",
            "scldm_vae_train_gaussian_forward", "scldm_vae_train_gaussian_backward", "scldm_gaussian_recon_loss_bwd",
            "scldm_dit_infer_workspace_bytes", "scldm_dit_infer_cond_rows", "scldm_dit_infer_forward_rows", "scldm_dit_infer_forward_cfg",
-           "scldm_dit_infer_sample_ode"]
+           "scldm_dit_infer_sample_ode",
+           "scldm_sample_ode_dopri5_workspace_bytes", "scldm_sample_ode_dopri5", "scldm_sample_ode_dopri5_at", "scldm_dopri5_stage_plan", "scldm_dopri5_control",
+           "scldm_dopri5_initial_h0", "scldm_dopri5_initial_step"]
 
 
 def check(rc: int, what: str) -> None:

@@ -15,6 +15,8 @@
 #include "dit_handle.hpp"
 #include "ode_rk.hpp"
 #include "sde.hpp"
+#include "dopri5_ctl.hpp"
+#include "dopri5_fused.hpp"
 
 using namespace scldm;
 
@@ -176,6 +178,7 @@ extern "C" int scldm_dit_create(const scldm_dit_config* cfg, scldm_dit** out) {
   if (e == hipSuccess) e = hipMemset(h->d_fp_state, 0, 16);
   if (e == hipSuccess) e = alloc((void**)&h->d_dirty, 8);
   if (e == hipSuccess) e = hipMemset(h->d_dirty, 0, 8);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->rk_host, 32, hipHostMallocDefault);   // read-back slot of scldm_sample_ode_dopri5
   if (e != hipSuccess) {
     int rc = fail(SCLDM_ERR_HIP, "hipMalloc failed in scldm_dit_create: %s", hipGetErrorString(e));
     scldm_dit_destroy(h);
@@ -207,6 +210,7 @@ extern "C" void scldm_dit_destroy(scldm_dit* h) {
   if (h->bwd_pack_ev) (void)hipEventDestroy(h->bwd_pack_ev);
   if (h->cond_stream) (void)hipStreamDestroy(h->cond_stream);
   if (h->cond_all) (void)hipFree(h->cond_all);
+  if (h->rk_host) (void)hipHostFree(h->rk_host);
   for (hipEvent_t ev : {h->ev_cond[0], h->ev_cond[1], h->ev_free[0], h->ev_free[1], h->ev_ready})
     if (ev) (void)hipEventDestroy(ev);
   delete h;
@@ -1098,6 +1102,9 @@ extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ul
   }
   return SCLDM_OK;
 }
+
+// ---- adaptive Dormand-Prince 5(4) sampling (dopri5_ctl.hpp, dopri5_fused.hpp) ----
+#include "dopri5_api.inc"
 
 // ---- SDE sampling (sde.hpp) -----------------------------------------------------------------------------------------------------------
 // torch.linspace(0, t1, steps) in fp32: linspace01's symmetric fill for any end point (step = (t1 - 0) / (steps - 1) in fp32)

@@ -765,6 +765,14 @@ struct CfgArgs {
   float* z;        // optional (Euler step fused into the blend, round 4): z[idx] += hstep * dz[idx] instead of storing dz
   float hstep;
 };
+// one conditional pass of the blend, r += scale * (c - u), for one element (float) or four (f32x4).  Defined HERE so that every kernel
+// that blends - cfg_blend_kernel below and the fused Dormand-Prince kernels of dopri5_fused.hpp, whose own arithmetic is compiled with
+// contraction off - gets the expression under this header's contraction mode: the same instructions, the same bits
+template <typename T>
+__device__ __forceinline__ T cfg_blend_term(T r, const T c, const T u, float scale) {
+  r += scale * (c - u);
+  return r;
+}
 __global__ void cfg_blend_kernel(const CfgArgs a) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t half = (size_t)a.B * a.e;
@@ -772,7 +780,7 @@ __global__ void cfg_blend_kernel(const CfgArgs a) {
   float r = a.v[idx];
   if (idx >= half) {
     const float u = r;
-    for (int p = 0; p < a.P; ++p) r += a.scale[p] * (a.v[2 * half + (size_t)p * half + (idx - half)] - u);
+    for (int p = 0; p < a.P; ++p) r = cfg_blend_term(r, a.v[2 * half + (size_t)p * half + (idx - half)], u, a.scale[p]);
   }
   if (a.z) a.z[idx] = a.z[idx] + a.hstep * r;   // (the expression of axpy_kernel: same bits as blend + axpy)
   else a.dz[idx] = r;

@@ -65,6 +65,7 @@ struct scldm_dit {
   bool cond_all_on = true;
   void* cond_all = nullptr;
   size_t cond_all_bytes = 0;
+  double* rk_host = nullptr;   // pinned host slot the adaptive solve reads its error ratio through (allocated once, at create)
   bool cond_ahead = false;  // SCLDM_COND_AHEAD=1: opt-in (measured +0.5 % at 1 024 joint-conditioned cells, -0.8 % at 512, -0.2 % at 4 096: off)
   int force_ft, force_x3_ft, force_x3_ntt;
   bool small_ntt = true;   // 32-token tiles for launches of at most 256 of them (SCLDM_SMALL_NTT=0: off)

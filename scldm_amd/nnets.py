@@ -332,6 +332,9 @@ class DiT(nn.Module):
             # shapes outside the fused family, eval mode: the record-free inference entries (scldm_dit_infer_*) serve forward,
             # forward_with_cfg and the fixed-grid sampler; SCLDM_WIDE_INFER=0 keeps them composed from scldm_dit_train_forward calls
             self.__dict__["_wide_infer"] = os.environ.get("SCLDM_WIDE_INFER", "1") != "0"
+            # the adaptive default sampler of a fused shape in eval mode: one C call (scldm_sample_ode_dopri5); SCLDM_DOPRI5_FUSED=0 keeps
+            # the host-driven solve over forward_with_cfg (same steps, same bits: A/B runs and the parity tests)
+            self.__dict__["_dopri5_fused"] = os.environ.get("SCLDM_DOPRI5_FUSED", "1") != "0"
         return L, self._handle
 
     def found_inf_flag(self) -> torch.Tensor:
@@ -425,7 +428,7 @@ class DiT(nn.Module):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _ws=None, _dedup_cache={})
         for k in ("_wstruct_cache", "_grad_offsets", "_grad_numel", "_grad_segs", "_pos_idx", "_param_list", "_prepared_key", "_grad_sync",
-                  "_train_step_sync", "_fp16_checked", "_found_inf", "_found_inf_handle", "_dense_rows", "_label_bad", "_wide_infer", "_ws_wide"):   # (_found_inf is registered with the handle that does not travel)
+                  "_train_step_sync", "_fp16_checked", "_found_inf", "_found_inf_handle", "_dense_rows", "_label_bad", "_wide_infer", "_ws_wide", "_dopri5_fused", "_ws_dopri5"):   # (_found_inf is registered with the handle that does not travel)
             state.pop(k, None)
         return state
 
@@ -959,19 +962,28 @@ class DiT(nn.Module):
     # ------------------------------------------------------------------ fused sampler (transport.py:324-369 + models.py:801-812)
     @torch.no_grad()
     def sample_ode_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
-                       num_steps: int, sampling_method: str = "euler", atol: float = 1e-5, rtol: float = 1e-5) -> torch.Tensor:
+                       num_steps: int, sampling_method: str = "euler", atol: float = 1e-5, rtol: float = 1e-5, *,
+                       first_step: float | None = None, return_trajectory: bool = False) -> torch.Tensor:
         """Integrate dz/dt = forward_with_cfg(z, t) over linspace(0, 1, num_steps) entirely on device.
 
         `z` is the doubled state cat([z0, z0]) (2B,S,C); `condition` the doubled label dict; `num_steps` has the
         reference meaning (grid POINTS: num_steps-1 Euler evaluations).  Returns the final state (what the
         reference indexes with [-1], models.py:812).
+
+        "dopri5" (the reference's default `sample_ode()`): adaptive Dormand-Prince 5(4) at `atol` / `rtol`; `num_steps` is then the
+        number of SAVE points (the steps never depend on it), `first_step` replaces the automatic initial step and
+        `return_trajectory` returns the (num_steps, 2B, S, C) stack of save points instead of its last entry.  A fused shape in eval
+        mode runs the solve as one C call (scldm_sample_ode_dopri5: it synchronises the stream once per attempted step and raises
+        under graph capture); a module in training mode, a shape outside the fused family and SCLDM_DOPRI5_FUSED=0 (read when the native
+        handle is created) run `Sampler._sample_dopri5` over `forward_with_cfg` - the same steps, the same bits.  Either way
+        `last_solver_stats` then holds evaluations, rejected, accepted_steps / rejected_steps ((t0, dt) lists) and first_step.
         """
+        if sampling_method.lower() == "dopri5":
+            return self._sample_dopri5_cfg(z, condition, cfg_scale, num_steps, atol, rtol, first_step, return_trajectory)
         if num_steps < 2:
             raise ValueError("num_steps must be >= 2 (grid points)")
-        if sampling_method.lower() == "dopri5":   # adaptive solve: host-driven steps over the fused forward_with_cfg
-            from .transport import Sampler, create_transport
-            fn = Sampler(create_transport()).sample_ode(sampling_method="dopri5", num_steps=2, atol=atol, rtol=rtol)
-            return fn(_require_cuda_f32("z", z), self.forward_with_cfg, condition=condition, cfg_scale=cfg_scale)[-1]
+        if first_step is not None or return_trajectory:
+            raise ValueError("first_step / return_trajectory belong to sampling_method='dopri5'")
         if self._wide_infer_on():
             # shapes outside the fused family: the whole solve as one call over the generic kernels (scldm_dit_infer_sample_ode)
             self._need_null_row("CFG sampling (the unconditional pass)")
@@ -1026,6 +1038,65 @@ class DiT(nn.Module):
                                           self._prec(), ws, _stream_ptr()), "scldm_sample_ode")
         del keep
         return z
+
+    # ------------------------------------------------------------------ the reference's default sampler: adaptive dopri5
+    last_solver_stats: dict | None = None    # of the last sample_ode_cfg(..., "dopri5") call
+
+    def _sample_dopri5_cfg(self, z, condition, cfg_scale, num_steps, atol, rtol, first_step, return_trajectory):
+        z = _require_cuda_f32("z", z)
+        fused = self.fused_shape and not self.training
+        if fused:
+            self._native_handle()
+            fused = bool(self.__dict__.get("_dopri5_fused", True))
+        if not fused:
+            # host-driven steps over forward_with_cfg, one evaluation per call (Sampler._sample_dopri5): training mode, shapes outside
+            # the fused family, SCLDM_DOPRI5_FUSED=0
+            if num_steps < 2:
+                raise ValueError("num_steps must be >= 2 (save points)")
+            from .transport import Sampler, create_transport
+            fn = Sampler(create_transport())._sample_dopri5(num_steps if return_trajectory else 2, atol, rtol, first_step)
+            traj = fn(z, self.forward_with_cfg, condition=condition, cfg_scale=cfg_scale)
+            st = dict(fn.last_stats)
+            steps = sorted(st["accepted_steps"] + st["rejected_steps"])
+            st["first_step"] = steps[0][1] if steps else None
+            self.last_solver_stats = st
+            return traj if return_trajectory else traj[-1]
+        self._need_null_row("CFG sampling (the unconditional pass)")
+        n = z.shape[0]
+        B = n // 2
+        if z.dim() != 3 or n != 2 * B or B < 1 or z.shape[1:] != (self.seq_len, self.n_embed_input):
+            raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+        L, h = self._native()
+        z = z.clone()
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+        need = L.scldm_sample_ode_dopri5_workspace_bytes(h, B, n_pass, n_u)
+        ws = self.__dict__.get("_ws_dopri5")
+        if ws is None or ws.numel() < need or ws.device != z.device:
+            self.__dict__["_ws_dopri5"] = ws = None   # (the old block is released before the new one is requested)
+            self.__dict__["_ws_dopri5"] = ws = torch.empty(need, dtype=torch.uint8, device=z.device)
+        traj = torch.empty(num_steps, *z.shape, device=z.device, dtype=torch.float32) if return_trajectory and num_steps >= 2 else None
+        stats = _lib.Dopri5Stats()
+        cap = 100000 // 6 + 2      # every attempted step the evaluation limit admits
+        log = (C.c_double * (3 * cap))()
+        # the save times as the host-composed solver and the reference hold them: torch.linspace on the host (integrators.py:95)
+        ts = torch.linspace(0.0, 1.0, max(int(num_steps), 1)).tolist()
+        times = (C.c_float * len(ts))(*ts)
+        with torch.cuda.device(z.device):
+            rc = L.scldm_sample_ode_dopri5_at(h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass,
+                                              masks, scales, num_steps, times, float(atol), float(rtol), float(first_step) if first_step else 0.0,
+                                              traj.data_ptr() if traj is not None else None, C.byref(stats), log, cap, self._prec(),
+                                              ws.data_ptr(), _stream_ptr())
+        del keep
+        if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
+            raise ValueError(L.scldm_last_error().decode())
+        steps = [(log[3 * i], log[3 * i + 1], log[3 * i + 2] != 0.0) for i in range(min(stats.step_log_len, cap))]
+        self.last_solver_stats = {"evaluations": int(stats.evaluations), "rejected": int(stats.rejected),
+                                  "accepted_steps": [(t, d) for t, d, ok in steps if ok], "rejected_steps": [(t, d) for t, d, ok in steps if not ok],
+                                  "first_step": stats.first_step}
+        if rc == _lib.ERR_SOLVER:
+            raise RuntimeError("dopri5: step size underflow / too many evaluations")
+        _lib.check(rc, "scldm_sample_ode_dopri5")
+        return traj if return_trajectory else z
 
     # ------------------------------------------------------------------ fused SDE sampler (transport.py:269-322 + integrators.py:7-75)
     def sde_noise(self, seed: int, step: int, B: int, cell_offset: int = 0, cells_total: int | None = None) -> torch.Tensor:

@@ -19,8 +19,10 @@ def shard_bounds(n: int, rank: int, world: int) -> tuple[int, int]:
 
 @torch.no_grad()
 def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | None, guidance_weight: dict[str, float] | None,
-                   num_steps: int = 101, sampling_method: str = "euler", sde: dict | None = None) -> torch.Tensor:
+                   num_steps: int = 101, sampling_method: str = "euler", sde: dict | None = None, atol: float = 1e-5,
+                   rtol: float = 1e-5) -> torch.Tensor:
     """z0 (B,S,C) noise -> final latents (2B,S,C): rows [0,B) unconditional, rows [B,2B) guided (models.py:801-812).
+    `atol` / `rtol`: the tolerances of sampling_method="dopri5" (the reference's default sampler and its defaults; a fixed grid ignores them).
 
     `sde`: None integrates the ODE (`DiT.sample_ode_cfg`); a dict selects the stochastic sampler instead and holds the keyword arguments
     of `DiT.sample_sde_cfg` beyond the grid and the method (diffusion_form, diffusion_norm, last_step, last_step_size, seed, noise, and
@@ -38,17 +40,20 @@ def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | N
     cond2 = None if condition is None else {k: torch.cat([v, v], dim=0) for k, v in condition.items()}
     if sde is not None:
         return dit.sample_sde_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, **sde)
+    if str(sampling_method).lower() == "dopri5":
+        return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, atol=atol, rtol=rtol)
     return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method)
 
 
 @torch.no_grad()
 def sample_cells(dit, vae, condition, guidance_weight, batch_size: int, genes: torch.Tensor, size_factors: torch.Tensor | None,
                  num_steps: int = 101, sampling_method: str = "euler", z0: torch.Tensor | None = None, draw_counts: bool = True,
-                 size_factor_sampler: "SizeFactorSampler | None" = None, seed: int | None = None, sde: dict | None = None):
+                 size_factor_sampler: "SizeFactorSampler | None" = None, seed: int | None = None, sde: dict | None = None,
+                 atol: float = 1e-5, rtol: float = 1e-5):
     """Reference `LatentDiffusion.sample` (models.py:766-819): returns (counts or NB distribution, latents) with
     2*batch_size rows, unconditional first.  Log size factors are either given or drawn on device by a
     `SizeFactorSampler` (models.py:785 -> _sample_log_size_factors).  `seed`: the negative-binomial draw's (default: from torch's
-    host generator).  `sde`: as `sample_latents` (None: the ODE sampler)."""
+    host generator).  `sde`: as `sample_latents` (None: the ODE sampler); `atol` / `rtol`: the tolerances of sampling_method="dopri5"."""
     if size_factors is None:
         if size_factor_sampler is None:
             raise ValueError("pass size_factors or a size_factor_sampler")
@@ -58,7 +63,7 @@ def sample_cells(dit, vae, condition, guidance_weight, batch_size: int, genes: t
     dev = dit.pos_embed.device
     if z0 is None:
         z0 = torch.randn((batch_size, dit.seq_len, vae.encoder.latent_embedding), device=dev)
-    z = sample_latents(dit, z0, condition, guidance_weight, num_steps, sampling_method, sde=sde)
+    z = sample_latents(dit, z0, condition, guidance_weight, num_steps, sampling_method, sde=sde, atol=atol, rtol=rtol)
     genes2 = torch.cat([genes, genes], dim=0)
     lib = torch.exp(size_factors).view(-1, 1)
     lib2 = torch.cat([lib, lib], dim=0)
@@ -68,7 +73,8 @@ def sample_cells(dit, vae, condition, guidance_weight, batch_size: int, genes: t
 
 
 def generate_cells_stream(dit, vae, batches, guidance_weight, genes: torch.Tensor, num_steps: int = 101, sampling_method: str = "euler",
-                          size_factor_sampler: "SizeFactorSampler | None" = None, seeds=None, merge_batches: int = 1):
+                          size_factor_sampler: "SizeFactorSampler | None" = None, seeds=None, merge_batches: int = 1, atol: float = 1e-5,
+                          rtol: float = 1e-5):
     """The reference's prediction loop (`trainer.predict` -> `predict_step` per batch -> `.cpu()`, src/scldm/models.py:707-764,742)
     as a two-stage pipeline over an iterable of batches: while batch i + 1's CFG ODE runs on the caller's stream, batch i's MCAB
     decode + negative-binomial draw, CSR assembly and pinned device-to-host copies run on a second HIP stream - the ODE kernel is
@@ -82,7 +88,10 @@ def generate_cells_stream(dit, vae, batches, guidance_weight, genes: torch.Tenso
     `merge_batches=k`: k consecutive batches share ONE solve (their noise and size factors are still drawn batch by batch, their rows
     decoded and yielded batch by batch: the same arrays, since a cell's trajectory does not depend on its batch) - throughput for small
     batches (the reference generates with 128 cells per batch, generation.yaml:16: 4 batches per solve are 1.8 x the cells per second) at the
-    price of the first result waiting for k batches of input."""
+    price of the first result waiting for k batches of input.
+    `atol` / `rtol`: the tolerances of sampling_method="dopri5".  An adaptive solve shares ONE step size across its whole state, so with
+    `merge_batches > 1` the merged batch takes the steps its combined error norm dictates: its arrays are tolerance-close to those of the
+    per-batch solves, not identical to them (the fixed-grid methods stay identical)."""
     from .datamodule import dense_to_csr, to_host
     dev = dit.pos_embed.device
     if dev.type != "cuda":
@@ -121,12 +130,13 @@ def generate_cells_stream(dit, vae, batches, guidance_weight, genes: torch.Tenso
     # to run ahead of): dense label-tuple rows, out-of-range labels clamped on the device and raised by check_labels() after the loop.
     # (the flag is set around each solve only - not across `yield`, where it would change the consumer's own calls)
     yield from _stream_loop(dit, vae, batches, guidance_weight, genes, num_steps, sampling_method, size_factor_sampler, seeds, dev, finish,
-                            max(1, int(merge_batches)))
+                            max(1, int(merge_batches)), atol, rtol)
     if hasattr(dit, "check_labels"):
         dit.check_labels()
 
 
-def _stream_loop(dit, vae, batches, guidance_weight, genes, num_steps, sampling_method, size_factor_sampler, seeds, dev, finish, merge=1):
+def _stream_loop(dit, vae, batches, guidance_weight, genes, num_steps, sampling_method, size_factor_sampler, seeds, dev, finish, merge=1,
+                 atol=1e-5, rtol=1e-5):
     import contextlib
     from .nnets import weights_unchanged
     B = genes.shape[0]
@@ -147,7 +157,7 @@ def _stream_loop(dit, vae, batches, guidance_weight, genes, num_steps, sampling_
             dit.deferred_label_check = True
         try:
             with (weights_unchanged() if solved_any else contextlib.nullcontext()):   # (the first solve checked the DiT's packed weights)
-                z = sample_latents(dit, z0, cond, guidance_weight, num_steps, sampling_method)      # queued; the host does not wait
+                z = sample_latents(dit, z0, cond, guidance_weight, num_steps, sampling_method, atol=atol, rtol=rtol)      # queued; the host does not wait
         finally:
             if had_flag is not None:
                 dit.deferred_label_check = had_flag

@@ -201,7 +201,7 @@ class Sampler:
         self.drift = transport.get_drift()
         self.score = transport.get_score()
 
-    def _sample_dopri5(self, num_steps: int, atol: float, rtol: float):
+    def _sample_dopri5(self, num_steps: int, atol: float, rtol: float, first_step: float | None = None):
         """Adaptive Dormand-Prince 5(4) - what `torchdiffeq.odeint(method="dopri5")` computes for the reference's default
         `sample_ode()` (integrators.py:100-112; models.py:793).  The driver follows torchdiffeq's documented scheme step for
         step (oracle/transport.py: sample_ode_dopri5 is its float64 restatement and the checker): FSAL tableau, mixed rms error
@@ -210,7 +210,10 @@ class Sampler:
         the save times (the solver steps past them, past t = 1 too) and the quartic interpolant of the last accepted step
         evaluated at the float32 `linspace(0, 1, num_steps)` save times.  PARITY UNPINNED at torchdiffeq itself (un-vendored,
         unpinned).  State arithmetic in the state's dtype on its device; times and step sizes are host float64; every step
-        costs one host read of the error ratio.  `fn.last_stats` = evaluations, accepted / rejected (t0, dt) lists."""
+        costs one host read of the error ratio.  `fn.last_stats` = evaluations, accepted / rejected (t0, dt) lists.
+        `first_step` (None: the automatic initial step) is taken as the first attempted step size and saves that step's extra
+        evaluation: two solves started from the same value can be compared step for step.  A scldm_amd DiT of the fused shape
+        family runs this solve as one C call (`DiT.sample_ode_cfg(..., "dopri5")` -> scldm_sample_ode_dopri5)."""
         drift = self.drift
 
         @torch.no_grad()
@@ -312,12 +315,15 @@ class Sampler:
         def _solve(f, comb, error_ratio, dense_fit, dense_eval, ts, x, y0, f0, n_eval_now):
             dev = x.is_cuda and x.dtype == torch.float32 and x.numel() % 4 == 0
             # initial step (Hairer / Norsett / Wanner II.4, rms norm, exponent 1 / 5)
-            scale = atol + rtol * y0.abs()
-            d0, d1 = _rms(y0 / scale), _rms(f0 / scale)
-            h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
-            d2 = _rms((f(y0 + h0 * f0, ts[0] + h0) - f0) / scale) / h0
-            h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1.0 / 5.0)
-            h = min(100.0 * h0, h1)
+            if first_step is not None and first_step > 0:
+                h = float(first_step)
+            else:
+                scale = atol + rtol * y0.abs()
+                d0, d1 = _rms(y0 / scale), _rms(f0 / scale)
+                h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
+                d2 = _rms((f(y0 + h0 * f0, ts[0] + h0) - f0) / scale) / h0
+                h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1.0 / 5.0)
+                h = min(100.0 * h0, h1)
             t0 = t1 = ts[0]
             coeff = None
             out = [x]
