@@ -538,6 +538,34 @@ int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z, const int
  * (2, cells_total, e) state: values in {-1, +1}.  out: device (n_rows_local, e), 16-byte aligned; e % 4 == 0. */
 int scldm_logp_probe(float* out, long long n_rows_local, int e, unsigned long long seed, int evaluation, int half, long long cell_offset,
                      long long cells_total, void* stream);
+/* The same likelihood with the reference's default solver (Sampler.sample_ode_likelihood(sampling_method="dopri5", atol=1e-6,
+ * rtol=1e-3)): adaptive Dormand-Prince 5(4) over the augmented state (x (2B, S Din), delta_logp (2B)) with the slopes (-v, logp_grad)
+ * of scldm_logp_ode's evaluation, as one call on a handle of the fused shape family.  The controller is the one of
+ * scldm_sample_ode_dopri5 (scldm_dopri5_stage_plan / _control / _initial_h0 / _initial_step): FSAL, one host read of the error ratio
+ * per attempted step, steps never clipped to s = 1 (the solver steps past it: the model is then evaluated at slightly negative t), the
+ * result is the quartic interpolant of the accepted step that contains s = 1, and logp = prior_logp(x_end) - delta_logp.
+ * Error norm: ONE mixed rms norm over all 2B (S Din + 1) components with one atol / rtol (the packed state of
+ * Sampler.sample_ode_likelihood): ratio = sqrt(mean((err / (atol + rtol max(|y0|, |y1|)))^2)); the automatic first step (first_step <= 0)
+ * uses the same norm.  All cells of a call share the step size, so a shard of a solve does NOT reproduce the whole solve's rows.
+ * Probes: evaluation index = the running count in execution order (f0 is 0, the initial-step probe evaluation 1 - absent when
+ * first_step is given -, then six per attempted step, rejected steps included).  probe_per_solve != 0 holds ONE probe for the whole
+ * solve (the usual FFJORD form): index 0 of the generator, or the given `probe` (2B, S Din); a given probe with probe_per_solve == 0 is
+ * refused (the number of evaluations is not known ahead).
+ *   z, labels / passes, seed / cell_offset / cells_total, logp, saved: as scldm_logp_ode.  dlogp_out: NULL or (2B) delta_logp at s = 1.
+ *   stats: as scldm_sample_ode_dopri5.  step_log: NULL or step_log_cap x FOUR doubles per attempted step: t0, h, accepted (1.0 / 0.0),
+ *       the error ratio the controller was given.
+ *   ws: scldm_logp_ode_dopri5_workspace_bytes bytes (0 for a NULL handle, a handle outside the fused family or a bad argument), 256-byte
+ *       aligned.
+ * SCLDM_ERR_SHAPE with nothing launched (checked before any HIP call): a NULL pointer, atol <= 0 or rtol < 0, B < 1, cells_total <
+ *   cell_offset + B, a probe without probe_per_solve, misaligned z / probe / ws, a handle outside the fused family; and a capturing
+ *   stream.  SCLDM_ERR_STATE: a handle without its read-back slot.  SCLDM_ERR_SOLVER: step-size underflow or more than 100 000
+ *   evaluations; z then holds the state reached and stats->status says which. */
+size_t scldm_logp_ode_dopri5_workspace_bytes(const scldm_dit* h, int B, int n_pass, int precision);
+int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                          const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, double atol,
+                          double rtol, double first_step, const float* probe, int probe_per_solve, unsigned long long seed,
+                          long long cell_offset, long long cells_total, float* logp_out, float* dlogp_out, scldm_dopri5_stats* stats,
+                          double* step_log, int step_log_cap, int precision, void* saved, void* ws, void* stream);
 
 /* Flow-matching training step around the model call (Transport.training_losses, src/scldm/transport/transport.py:110-150 with
  * ICPlan.plan, path.py:148-151): the eager reference spends ~20 elementwise launches here per step.

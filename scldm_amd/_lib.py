@@ -217,7 +217,13 @@ def lib() -> C.CDLL:
     L.scldm_dit_infer_sample_ode.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(C.c_uint32), c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_logp_probe.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]
-    L.scldm_fm_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.scldm_logp_ode_dopri5_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.scldm_logp_ode_dopri5_workspace_bytes.restype = C.c_size_t
+    L.scldm_logp_ode_dopri5.argtypes = [C.c_void_p, C.POINTER(DitWeights), C.c_void_p, c_void_pp, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.POINTER(C.c_uint32), c_float_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_uint64,
+                                        C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(Dopri5Stats), C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    L.scldm_fm_mix.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_vae_create.argtypes = [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]
@@ -305,7 +311,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_infer_workspace_bytes", "scldm_dit_infer_cond_rows", "scldm_dit_infer_forward_rows", "scldm_dit_infer_forward_cfg",
            "scldm_dit_infer_sample_ode",
            "scldm_sample_ode_dopri5_workspace_bytes", "scldm_sample_ode_dopri5", "scldm_sample_ode_dopri5_at", "scldm_dopri5_stage_plan", "scldm_dopri5_control",
-           "scldm_dopri5_initial_h0", "scldm_dopri5_initial_step"]
+           "scldm_dopri5_initial_h0", "scldm_dopri5_initial_step",
+           "scldm_logp_ode_dopri5_workspace_bytes", "scldm_logp_ode_dopri5"]
 
 
 def check(rc: int, what: str) -> None:

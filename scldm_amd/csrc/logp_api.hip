@@ -166,3 +166,5 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
+
+#include "logp_dopri5_api.inc"   // scldm_logp_ode_dopri5: the adaptive solve over the same evaluation

@@ -1196,10 +1196,12 @@ class DiT(nn.Module):
         return out
 
     def log_likelihood_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
-                           num_steps: int = 50, sampling_method: str = "euler", *, seed: int | None = None, probe: torch.Tensor | None = None,
-                           cell_offset: int = 0, cells_total: int | None = None, return_trace: bool = False):
+                           num_steps: int = 50, sampling_method: str = "euler", *, atol: float = 1e-6, rtol: float = 1e-3,
+                           first_step: float | None = None, probe_per: str = "evaluation", seed: int | None = None,
+                           probe: torch.Tensor | None = None, cell_offset: int = 0, cells_total: int | None = None, return_trace: bool = False):
         """The reference's `Sampler.sample_ode_likelihood` over `forward_with_cfg` on the fixed grid linspace(0, 1, num_steps)
-        ("euler" / "heun"; `num_steps` grid points as sample_ode_cfg).  `z` is the doubled state cat([x, x]) (2B,S,C) of real latents,
+        ("euler" / "heun"; `num_steps` grid points as sample_ode_cfg), or with its default adaptive solver ("dopri5", below).
+        `z` is the doubled state cat([x, x]) (2B,S,C) of real latents,
         `condition` the doubled label dict.  Returns (logp (2B), z_end (2B,S,C)) - first B rows under the unconditional field, last B
         under the guided field; z_end is the noise-end latent of each row (the inversion).  With `return_trace` a third value: the
         (n_evaluations, 2B) logp_grad of every evaluation.
@@ -1212,10 +1214,30 @@ class DiT(nn.Module):
         only - with `cell_offset` / `cells_total` a shard of a larger solve draws what the whole solve would.
         Fused shape in eval mode: the whole solve is one C call (scldm_logp_ode: recording forward + input-gradient-only backward per
         evaluation, no host read).  Anything else: the generic `Sampler.sample_ode_likelihood` over differentiable `forward` calls with the
-        same probes."""
+        same probes.
+
+        "dopri5" (the reference's default: `atol=1e-6, rtol=1e-3`): adaptive Dormand-Prince 5(4) over the augmented state (x, delta_logp)
+        with ONE mixed rms error norm over all 2B (S C + 1) components, as the reference's tuple state; `first_step` (None: automatic) is the
+        first attempted step size.  `num_steps` is the reference's save-point count: only the last point (s = 1) is formed, and the steps
+        do not depend on it.  On a fused shape in eval mode the whole solve is one C call (scldm_logp_ode_dopri5: one host read of the
+        error ratio per attempted step - so it cannot be graph-captured) and `self.last_solver_stats` = {"evaluations", "accepted",
+        "rejected", "accepted_steps", "rejected_steps" ((s0, h) lists), "error_ratios", "first_step", "status"}; training mode and other
+        shapes run the generic `Sampler.sample_ode_likelihood("dopri5")` with the same probes.
+        `probe_per="evaluation"` (default) is the reference's form - a fresh probe at every evaluation, numbered in execution order (f0
+        is 0, the automatic-first-step evaluation 1, then six per attempted step, rejected ones included), drawn by the generator keyed
+        by `seed`; a given `probe` is refused (the evaluation count is not known ahead).  The logp_grad component of the slope is then
+        noise to the step controller.  `probe_per="solve"` ("dopri5" only; the usual FFJORD form) holds one probe for the whole solve:
+        evaluation 0 of the generator, or `probe` (1, 2B, S, C) / (2B, S, C).
+        The step size is shared by the whole batch: a shard of a dopri5 solve does NOT reproduce the whole solve's rows, unlike the fixed
+        grid, even though its probes are the whole solve's.  `return_trace` is not available with "dopri5"."""
         method = str(sampling_method).lower()
+        if method == "dopri5":
+            return self._log_likelihood_dopri5(z, condition, cfg_scale, num_steps, atol, rtol, first_step, probe_per, seed, probe, cell_offset,
+                                               cells_total, return_trace)
         if method not in _lib.METHODS:
-            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented on the fixed grid: 'euler' and 'heun' are")
+            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are")
+        if probe_per != "evaluation":
+            raise ValueError(f"probe_per={probe_per!r}: the fixed-grid solves draw one probe per evaluation (probe_per='solve' is for 'dopri5')")
         if num_steps < 2:
             raise ValueError("num_steps must be >= 2 (grid points)")
         z = _require_cuda_f32("z", z).clone()
@@ -1267,6 +1289,94 @@ class DiT(nn.Module):
         _lib.check(rc, "scldm_logp_ode")
         del keep
         return (logp, z, trace) if return_trace else (logp, z)
+
+    def _log_likelihood_dopri5(self, z, condition, cfg_scale, num_steps, atol, rtol, first_step, probe_per, seed, probe, cell_offset,
+                               cells_total, return_trace):
+        """log_likelihood_cfg(..., "dopri5"): scldm_logp_ode_dopri5, or the generic sampler for training mode / other shapes."""
+        if return_trace:
+            raise ValueError("return_trace is not available with 'dopri5' (the evaluation count of an adaptive solve is not known ahead)")
+        if probe_per not in ("evaluation", "solve"):
+            raise ValueError(f"probe_per={probe_per!r}: 'evaluation' or 'solve'")
+        if not (atol > 0.0) or not (rtol >= 0.0):
+            raise ValueError(f"atol must be > 0 and rtol >= 0 (got {atol}, {rtol})")
+        if first_step is not None and not (first_step > 0.0):
+            raise ValueError(f"first_step must be positive or None (got {first_step})")
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (save points)")
+        z = _require_cuda_f32("z", z).clone()
+        n = z.shape[0]
+        B = n // 2
+        if z.dim() != 3 or n != 2 * B or B < 1 or z.shape[1:] != (self.seq_len, self.n_embed_input):
+            raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+        total = B + cell_offset if cells_total is None else int(cells_total)
+        if cell_offset < 0 or total < cell_offset + B:
+            raise ValueError(f"cells_total ({total}) must cover cell_offset ({cell_offset}) + B ({B})")
+        per_solve = probe_per == "solve"
+        if probe is not None:
+            if not per_solve:
+                raise ValueError("a given probe needs probe_per='solve': the number of evaluations of an adaptive solve is not known ahead")
+            probe = _require_cuda_f32("probe", probe).contiguous()
+            if tuple(probe.shape) == (1, *z.shape):
+                probe = probe[0]
+            if tuple(probe.shape) != tuple(z.shape):
+                raise ValueError(f"expected probe {(1, *z.shape)} or {tuple(z.shape)}, got {tuple(probe.shape)}")
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = int(seed) & (2 ** 64 - 1)
+        self._need_null_row("the likelihood of a CFG field (the unconditional pass)")
+        if self.training or not self.fused_shape:
+            from .transport import Sampler, create_transport
+            count = iter(range(1 << 62))
+            if probe is not None:
+                draw = lambda x: probe
+            elif per_solve:
+                held = self.logp_probe(seed, 0, B, cell_offset, total)
+                draw = lambda x: held
+            else:
+                draw = lambda x: self.logp_probe(seed, next(count), B, cell_offset, total)
+            fn = Sampler(create_transport()).sample_ode_likelihood(sampling_method="dopri5", num_steps=num_steps, atol=atol, rtol=rtol,
+                                                                   first_step=first_step)
+            logp, z_end = fn(z, lambda x, t: self._composed_forward_with_cfg(x, t.contiguous(), condition, cfg_scale), _probe=draw)
+            st = fn.last_stats
+            steps = sorted(st["accepted_steps"] + st["rejected_steps"])
+            self.last_solver_stats = {"evaluations": st["evaluations"], "accepted": len(st["accepted_steps"]), "rejected": st["rejected"],
+                                      "accepted_steps": st["accepted_steps"], "rejected_steps": st["rejected_steps"], "error_ratios": None,
+                                      "first_step": steps[0][1] if steps else None, "status": 0}
+            return logp, z_end
+        L, h = self._native_handle()
+        params = tuple(self.parameters())
+        cached = self.__dict__.get("_param_list")
+        if cached is None or len(cached) != len(params) or any(a is not b for a, b in zip(cached, params)):
+            self.__dict__["_param_list"] = params
+            self.__dict__.pop("_wstruct_cache", None)
+        w, _ = self._weights_struct(params)
+        prec = self._prec()
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+        N = (2 + n_pass) * B
+        saved = torch.empty(L.scldm_dit_train_saved_bytes_for(h, N, prec), dtype=torch.uint8, device=z.device)
+        ws = torch.empty(L.scldm_logp_ode_dopri5_workspace_bytes(h, B, n_pass, prec), dtype=torch.uint8, device=z.device)
+        logp = torch.empty(n, dtype=torch.float32, device=z.device)
+        stats = _lib.Dopri5Stats()
+        cap = 100000 // 6 + 2      # every attempted step the evaluation limit admits
+        log = (C.c_double * (4 * cap))()
+        with torch.cuda.device(z.device):
+            rc = L.scldm_logp_ode_dopri5(h, C.byref(w), z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B,
+                                         n_pass, masks, scales, float(atol), float(rtol), float(first_step) if first_step else 0.0,
+                                         probe.data_ptr() if probe is not None else None, int(per_solve), seed, cell_offset, total,
+                                         logp.data_ptr(), None, C.byref(stats), log, cap, prec, saved.data_ptr(), ws.data_ptr(), _stream_ptr())
+        del keep
+        if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
+            raise ValueError(L.scldm_last_error().decode())
+        steps = [(log[4 * i], log[4 * i + 1], log[4 * i + 2] != 0.0, log[4 * i + 3]) for i in range(min(stats.step_log_len, cap))]
+        self.last_solver_stats = {"evaluations": int(stats.evaluations), "accepted": int(stats.accepted), "rejected": int(stats.rejected),
+                                  "accepted_steps": [(t, d) for t, d, ok, _ in steps if ok],
+                                  "rejected_steps": [(t, d) for t, d, ok, _ in steps if not ok], "error_ratios": [r for _, _, _, r in steps],
+                                  "first_step": stats.first_step, "status": int(stats.status)}
+        if rc == _lib.ERR_SOLVER:
+            raise RuntimeError("dopri5: step size underflow / too many evaluations")
+        _lib.check(rc, "scldm_logp_ode_dopri5")
+        return logp, z
 
     # ------------------------------------------------------------------ bench hook
     def layers_per_launch(self) -> int:

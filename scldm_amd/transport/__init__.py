@@ -442,7 +442,7 @@ class Sampler:
 
         return _sample
 
-    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3):
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, first_step=None):
         """Returns fn(x, model, **model_kwargs) -> (logp, x_end): the reference's likelihood sampler (transport.py:371-430), signature and
         defaults included.  The augmented state (x, delta_logp) is integrated over solver time s from 0 to 1 with
 
@@ -456,8 +456,11 @@ class Sampler:
         "euler" / "heun" step on this project's fixed grid linspace(0, 1, num_steps) (num_steps grid points; Heun's second evaluation
         at the next grid point); "dopri5" runs the Dormand-Prince driver of sample_ode on the packed state (n, x[0].numel() + 1) - the
         reference passes one atol / rtol for both components, i.e. one mixed rms norm over the packed state (parity with torchdiffeq
-        unpinned, as for sample_ode).  After a call `fn.last_trace` = {"t": [...], "logp_grad": [...]} of every evaluation.
-        A scldm_amd DiT runs the fixed-grid solve on device through `DiT.log_likelihood_cfg`."""
+        unpinned, as for sample_ode).  After a call `fn.last_trace` = {"t": [...], "logp_grad": [...]} of every evaluation, and after a
+        "dopri5" solve `fn.last_stats` = the driver's evaluations and accepted / rejected (t0, dt) lists.  `first_step` ("dopri5" only;
+        None: the automatic initial step) is the first attempted step size, as for `_sample_dopri5`.
+        A scldm_amd DiT runs these solves on device through `DiT.log_likelihood_cfg` (fixed grid: scldm_logp_ode; "dopri5":
+        scldm_logp_ode_dopri5)."""
         method = str(sampling_method).lower()
         if method not in ("euler", "heun", "dopri5"):
             raise NotImplementedError(f"sampling_method={sampling_method!r}: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are provided")
@@ -493,7 +496,9 @@ class Sampler:
                     dxv, lg = likelihood_drift(y[:, :-1].reshape(shape), s)
                     return torch.cat([dxv.reshape(n, -1), lg.reshape(n, 1).to(dxv.dtype)], dim=1)
 
-                y = Sampler(transport)._sample_dopri5(num_steps, atol, rtol)(torch.cat([x.reshape(n, -1), dl.reshape(n, 1)], dim=1), packed)[-1]
+                solve = Sampler(transport)._sample_dopri5(num_steps, atol, rtol, first_step)
+                y = solve(torch.cat([x.reshape(n, -1), dl.reshape(n, 1)], dim=1), packed)[-1]
+                _sample_fn.last_stats = solve.last_stats
                 x, dl = y[:, :-1].reshape(shape), y[:, -1]
             else:
                 ts = torch.linspace(0.0, 1.0, num_steps)
