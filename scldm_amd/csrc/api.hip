@@ -1104,6 +1104,16 @@ extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ul
 }
 
 // ---- adaptive Dormand-Prince 5(4) sampling (dopri5_ctl.hpp, dopri5_fused.hpp) ----
+// the handle-free controller entries: dopri5_ctl.hpp's decisions with a C face
+extern "C" void scldm_dopri5_stage_plan(double t0, double h, scldm_dopri5_plan* out) {
+  if (out) scldm::dopri5::stage_plan(t0, h, out);
+}
+extern "C" void scldm_dopri5_control(double t0, double h, double ratio, scldm_dopri5_control_out* out) {
+  if (out) scldm::dopri5::control(t0, h, ratio, out);
+}
+extern "C" double scldm_dopri5_initial_h0(double d0, double d1) { return scldm::dopri5::initial_h0(d0, d1); }
+extern "C" double scldm_dopri5_initial_step(double h0, double d1, double d2) { return scldm::dopri5::initial_step(h0, d1, d2); }
+
 #include "dopri5_api.inc"
 
 // ---- SDE sampling (sde.hpp) -----------------------------------------------------------------------------------------------------------

@@ -1,16 +1,10 @@
 // scldm_sample_ode_dopri5: the reference's default sampler as one call (include/scldm_hip.h).  Part of api.hip's translation unit: it uses
-// that file's plan, conditioning and trunk helpers.  The controller is dopri5_ctl.hpp (plain C++), the state kernels are dopri5_fused.hpp.
+// that file's plan, conditioning and trunk helpers.  The step loop and its decisions are dopri5_ctl.hpp (plain C++: solve(), shared with
+// scldm_logp_ode_dopri5); this file is the problem that loop drives.  The state kernels are dopri5_fused.hpp.
 //
 // One attempted step = one batched conditioning pass over its six new evaluation times (time list -> t_embed_list_kernel ->
 // cond_rows_kernel over (rows, 6) -> one adaLN projection over 6 x rows rows: cond_all_prepare's scheme with n_evals = 6), the first
 // stage point (combine_kernel), six trunks each followed by ONE state kernel, error_final_kernel, and an 8-byte read of the error ratio.
-
-// libm's pow as a call the optimiser cannot rewrite (pow(x, 0.5) would become a square root: correctly rounded, where the host-composed
-// solver's Python `x ** 0.5` is libm's pow - the two routes have to take the same decisions from the same doubles)
-static double d5_pow(double x, double y) {
-  volatile double yv = y;
-  return std::pow(x, yv);
-}
 
 struct D5Ws {
   float *h, *v, *mod, *silu;
@@ -52,27 +46,6 @@ extern "C" size_t scldm_sample_ode_dopri5_workspace_bytes(const scldm_dit* h, in
   return d5_carve(h, nullptr, B, n_pass, n_urows).total;
 }
 
-extern "C" void scldm_dopri5_stage_plan(double t0, double h, scldm_dopri5_plan* out) {
-  if (out) scldm::dopri5::stage_plan(t0, h, out);
-}
-extern "C" void scldm_dopri5_control(double t0, double h, double ratio, scldm_dopri5_control_out* out) {
-  if (out) scldm::dopri5::control(t0, h, ratio, out);
-}
-extern "C" double scldm_dopri5_initial_h0(double d0, double d1) { return scldm::dopri5::initial_h0(d0, d1); }
-extern "C" double scldm_dopri5_initial_step(double h0, double d1, double d2) { return scldm::dopri5::initial_step(h0, d1, d2); }
-
-// weights with their mask -> the compacted (pointer, coefficient) list the state kernels take
-static scldm::rk::CombArgs d5_comb(const float* w, unsigned mask, float* const* k) {
-  scldm::rk::CombArgs a{};
-  for (int j = 0; j < 7; ++j)
-    if ((mask >> j) & 1u) {
-      a.k[a.n_k] = k[j];
-      a.c[a.n_k] = w[j];
-      ++a.n_k;
-    }
-  return a;
-}
-
 // save_times: host, num_save non-decreasing fp32 times, the first 0 (the state there is the initial z)
 static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
                     const uint32_t* pass_mask, const float* pass_scale, int num_save, const float* save_times, double atol, double rtol,
@@ -94,23 +67,18 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
       if (!(save_times[i] >= save_times[i - 1]) || !(save_times[i] <= 1e30f))
         return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5_at: save times must be finite and non-decreasing (entry %d)", i);
   }
-  if (!(atol > 0.0) || !(rtol >= 0.0)) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: atol must be > 0 and rtol >= 0 (got %g, %g)", atol, rtol);
   if (B < 1) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: B must be positive");
-  if (step_log && step_log_cap < 0) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: step_log_cap must be >= 0");
-  if (((uintptr_t)z & 15) || ((uintptr_t)traj & 15) || ((uintptr_t)ws_ & 255)) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: z and traj must be 16-byte, ws 256-byte aligned");
-  int rc = check_ready(h, precision);
+  int rc = dopri5_check_tolerances("scldm_sample_ode_dopri5", atol, rtol, step_log, step_log_cap);
   if (rc) return rc;
+  if (((uintptr_t)z & 15) || ((uintptr_t)traj & 15) || ((uintptr_t)ws_ & 255)) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: z and traj must be 16-byte, ws 256-byte aligned");
+  if ((rc = check_ready(h, precision))) return rc;
   CfgPlan pl;
   if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
   const int e_row = 16 * h->cfg.n_embed_input;
   const size_t n = (size_t)2 * B * e_row, n4 = n / 4;
   if (n4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: state too large (at most 2^33 elements)");
-  if (!h->rk_host) return fail(SCLDM_ERR_STATE, "scldm_sample_ode_dopri5: the handle has no read-back slot");
   hipStream_t st = (hipStream_t)stream_;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(st, &cap));
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_dopri5: the stream is capturing - the solve reads its error ratio once per step and cannot be captured into a graph");
+  if ((rc = dopri5_check_stream("scldm_sample_ode_dopri5", h->rk_host, st))) return rc;
 
   D5Ws w = d5_carve(h, ws_, B, pl.P, pl.U);
   const float atol_f = (float)atol, rtol_f = (float)rtol;
@@ -128,6 +96,11 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
   geom.direct = pl.direct ? 1 : 0;
   for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) geom.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
 
+  float* K[7];
+  for (int i = 0; i < 7; ++i) K[i] = w.k[i];
+  // three state buffers in rotation: the start of the last accepted step (c0 of its interpolant), the current state, the stage point
+  float *c0 = w.y[1], *y0 = z, *stg = w.y[0];
+
   // the adaLN vectors of `cnt` evaluations at the given fp32 times -> w.mod, evaluation j in rows [j n_rows, (j + 1) n_rows)
   auto conditioning = [&](const float* times, int cnt) -> int {
     d5::Times tt{};
@@ -142,151 +115,123 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
   auto run_trunk = [&](const float* x, int slot) -> int {
     return trunk(h, x, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, w.mod + (size_t)slot * pl.n_rows * h->mod_w, w.ridx, w.h, w.v, precision, st);
   };
+  // weights with their mask -> the compacted (pointer, coefficient) list the state kernels take
+  auto comb = [&](const float* wt, unsigned mask) {
+    rk::CombArgs a{};
+    a.n_k = d5::compact(wt, mask, [&](int i, int j, float c) { a.k[i] = K[j]; a.c[i] = c; });
+    return a;
+  };
   // slope alone (out == nullptr) or slope + next stage point
-  auto blend_stage = [&](float* k_new, float* out, const float* y0, const rk::CombArgs& c) -> int {
+  auto blend_stage = [&](float* k_new, float* out, const float* y_from, const rk::CombArgs& c) -> int {
     d5::StageArgs a{};
     a.g = geom;
     a.k_new = k_new;
     a.out = out;
-    a.y0 = y0;
+    a.y0 = y_from;
     a.c = c;
     d5::blend_stage_kernel<<<sblocks, 256, 0, st>>>(a);
     LAUNCH_CHECK();
     return SCLDM_OK;
   };
   // mean of squares of (a - b) / (atol + rtol |y0|) -> red[1022]
-  auto norm = [&](const float* a, const float* b, const float* y0, double* red) -> int {
+  auto norm = [&](const float* a, const float* b, double* red) -> int {
     d5::scaled_norm_kernel<<<eblocks, 256, 0, st>>>(a, b, y0, (long)n4, atol_f, rtol_f, red);
     rk::error_final_kernel<<<1, 256, 0, st>>>(red, eblocks, (long)n, red + 1022);
     LAUNCH_CHECK();
     return SCLDM_OK;
   };
+  // f(t, x) into slope k
+  auto slope_at = [&](float t, const float* x, float* k) -> int {
+    int rc;
+    if ((rc = conditioning(&t, 1))) return rc;
+    if ((rc = run_trunk(x, 0))) return rc;
+    return blend_stage(k, nullptr, nullptr, rk::CombArgs{});
+  };
 
-  float* K[7];
-  for (int i = 0; i < 7; ++i) K[i] = w.k[i];
-  // three state buffers in rotation: the start of the last accepted step (c0 of its interpolant), the current state, the stage point
-  float *c0 = w.y[1], *y0 = z, *stg = w.y[0];
-  long long n_eval = 0, n_acc = 0, n_rej = 0;
-  int n_log = 0, status = SCLDM_DOPRI5_OK;
-  volatile double* host = h->rk_host;
-
-  // f0 = f(0, y0)
-  const float t_first = 0.0f;
-  if ((rc = conditioning(&t_first, 1))) return rc;
-  if ((rc = run_trunk(y0, 0))) return rc;
-  if ((rc = blend_stage(K[0], nullptr, nullptr, rk::CombArgs{}))) return rc;
-  ++n_eval;
-  double hstep = first_step;
-  if (!(first_step > 0.0)) {
-    if ((rc = norm(y0, nullptr, y0, w.red))) return rc;
-    if ((rc = norm(K[0], nullptr, y0, w.red2))) return rc;
+  // what dopri5_ctl.hpp's solve() calls, each in the order it enqueues
+  auto first_slope = [&]() -> int { return slope_at(0.0f, y0, K[0]); };
+  auto start_norms = [&](double* ms) -> int {
+    int rc;
+    if ((rc = norm(y0, nullptr, w.red))) return rc;
+    if ((rc = norm(K[0], nullptr, w.red2))) return rc;
+    volatile double* host = h->rk_host;
     HIP_TRY(hipMemcpyAsync((void*)(host + 0), w.red + 1022, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync((void*)(host + 1), w.red2 + 1022, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const double dn0 = std::sqrt(host[0]), dn1 = std::sqrt(host[1]);
-    const double h0 = d5::initial_h0(dn0, dn1);
+    ms[0] = host[0];
+    ms[1] = host[1];
+    return SCLDM_OK;
+  };
+  auto probe = [&](double h0, double* ms) -> int {
     rk::CombArgs c1{};
     c1.n_k = 1;
     c1.k[0] = K[0];
     c1.c[0] = (float)h0;
     rk::combine_kernel<<<sblocks, 256, 0, st>>>(stg, y0, c1, (long)n4);   // y0 + h0 f0
-    const float t_probe = (float)(0.0 + h0);
-    if ((rc = conditioning(&t_probe, 1))) return rc;
-    if ((rc = run_trunk(stg, 0))) return rc;
-    if ((rc = blend_stage(K[1], nullptr, nullptr, rk::CombArgs{}))) return rc;
-    ++n_eval;
-    if ((rc = norm(K[1], K[0], y0, w.red))) return rc;
-    HIP_TRY(hipMemcpyAsync((void*)(host + 0), w.red + 1022, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    hstep = d5::initial_step(h0, dn1, std::sqrt(host[0]) / h0);
-  }
-  const double first = hstep;
-  double t0 = 0.0, t1 = 0.0;
-  bool underflow = !(t1 + hstep > t1);
-  // without a trajectory only the state at the last save time (t = 1) is formed: the steps do not depend on the save times
-  for (int si = traj ? 1 : num_save - 1; si < num_save && status == SCLDM_DOPRI5_OK; ++si) {
-    const double next_t = (double)(save_times ? save_times[si] : linspace01(si, num_save));
-    while (next_t > t1) {   // advance until the save time lies inside the last accepted step
-      if (underflow) { status = SCLDM_DOPRI5_UNDERFLOW; break; }
-      if (n_eval > 100000) { status = SCLDM_DOPRI5_MAX_EVALS; break; }
-      const double ta = t1;
-      scldm_dopri5_plan plan;
-      d5::stage_plan(ta, hstep, &plan);
-      if ((rc = conditioning(plan.t_stage, d5::kStages))) return rc;
-      rk::combine_kernel<<<sblocks, 256, 0, st>>>(stg, y0, d5_comb(plan.a[0], plan.a_mask[0], K), (long)n4);
-      LAUNCH_CHECK();
-      for (int i = 0; i < d5::kStages; ++i) {
-        if ((rc = run_trunk(stg, i))) return rc;
-        if (i + 1 < d5::kStages) {
-          if ((rc = blend_stage(K[i + 1], stg, y0, d5_comb(plan.a[i + 1], plan.a_mask[i + 1], K)))) return rc;
-        } else {   // the last stage point is the 5th-order solution y1 (FSAL: K[6] = f(ta + h, y1))
-          d5::ErrorArgs ea{};
-          ea.g = geom;
-          ea.k_new = K[6];
-          ea.y0 = y0;
-          ea.y1 = stg;
-          ea.c = d5_comb(plan.err, plan.err_mask, K);
-          ea.n = (long)n;
-          ea.atol = atol_f;
-          ea.rtol = rtol_f;
-          ea.partial = w.red;
-          d5::blend_error_kernel<<<eblocks, 256, 0, st>>>(ea);
-          rk::error_final_kernel<<<1, 256, 0, st>>>(w.red, eblocks, (long)n, w.red + 1022);
-          LAUNCH_CHECK();
-        }
+    int rc;
+    if ((rc = slope_at((float)(0.0 + h0), stg, K[1]))) return rc;
+    if ((rc = norm(K[1], K[0], w.red))) return rc;
+    return dopri5_read_back(h->rk_host, w.red + 1022, 1, ms, st);
+  };
+  auto save_time = [&](int si) { return (double)(save_times ? save_times[si] : linspace01(si, num_save)); };
+  auto attempt = [&](const d5::Step& step, double* ms) -> int {
+    const scldm_dopri5_plan& plan = step.plan;
+    int rc;
+    if ((rc = conditioning(plan.t_stage, d5::kStages))) return rc;
+    rk::combine_kernel<<<sblocks, 256, 0, st>>>(stg, y0, comb(plan.a[0], plan.a_mask[0]), (long)n4);
+    LAUNCH_CHECK();
+    for (int i = 0; i < d5::kStages; ++i) {
+      if ((rc = run_trunk(stg, i))) return rc;
+      if (i + 1 < d5::kStages) {
+        if ((rc = blend_stage(K[i + 1], stg, y0, comb(plan.a[i + 1], plan.a_mask[i + 1])))) return rc;
+      } else {   // the last stage point is the 5th-order solution y1 (FSAL: K[6] = f(ta + h, y1))
+        d5::ErrorArgs ea{};
+        ea.g = geom;
+        ea.k_new = K[6];
+        ea.y0 = y0;
+        ea.y1 = stg;
+        ea.c = comb(plan.err, plan.err_mask);
+        ea.n = (long)n;
+        ea.atol = atol_f;
+        ea.rtol = rtol_f;
+        ea.partial = w.red;
+        d5::blend_error_kernel<<<eblocks, 256, 0, st>>>(ea);
+        rk::error_final_kernel<<<1, 256, 0, st>>>(w.red, eblocks, (long)n, w.red + 1022);
+        LAUNCH_CHECK();
       }
-      n_eval += d5::kStages;
-      HIP_TRY(hipMemcpyAsync((void*)host, w.red + 1022, 8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));      // the step's one host read
-      const double ratio = d5_pow(host[0], 0.5);
-      scldm_dopri5_control_out co;
-      d5::control(ta, hstep, ratio, &co);
-      if (step_log && n_log < step_log_cap) {
-        step_log[3 * n_log] = ta;
-        step_log[3 * n_log + 1] = hstep;
-        step_log[3 * n_log + 2] = co.accepted ? 1.0 : 0.0;
-        ++n_log;
-      }
-      if (co.accepted) {
-        ++n_acc;
-        if (next_t <= co.t1) {   // a save time falls inside this step: fit its interpolant (the weights of THIS step)
-          rk::dense_kernel<<<cdiv(n, 256), 256, 0, st>>>(y0, stg, d5_comb(plan.mid, plan.mid_mask, K), K[0], K[6], plan.h, plan.two_h, (long)n, w.c[0],
-                                                         w.c[1], w.c[2], w.c[3]);
-          LAUNCH_CHECK();
-        }
-        float* freed = c0;
-        c0 = y0;
-        y0 = stg;
-        stg = freed;
-        std::swap(K[0], K[6]);
-        t0 = ta;
-        t1 = co.t1;
-      } else ++n_rej;
-      hstep = co.h_next;
-      underflow = co.underflow != 0;
     }
-    if (status != SCLDM_DOPRI5_OK) break;
-    const double s = (next_t - t0) / (t1 - t0);
-    const float s1 = (float)s, s2 = (float)(s * s), s3 = (float)(s * s * s), s4 = (float)(s * s * s * s);
-    if (traj) rk::poly_kernel<<<sblocks, 256, 0, st>>>(traj + (size_t)si * n, c0, w.c[0], w.c[1], w.c[2], w.c[3], s1, s2, s3, s4, (long)n4);
+    return dopri5_read_back(h->rk_host, w.red + 1022, 1, ms, st);      // the step's one host read
+  };
+  auto accept = [&](const d5::Step& step, bool fit_dense) -> int {
+    if (fit_dense) {
+      rk::dense_kernel<<<cdiv(n, 256), 256, 0, st>>>(y0, stg, comb(step.plan.mid, step.plan.mid_mask), K[0], K[6], step.plan.h, step.plan.two_h, (long)n,
+                                                     w.c[0], w.c[1], w.c[2], w.c[3]);
+      LAUNCH_CHECK();
+    }
+    float* freed = c0;
+    c0 = y0;
+    y0 = stg;
+    stg = freed;
+    std::swap(K[0], K[6]);
+    return SCLDM_OK;
+  };
+  auto emit = [&](int si, double s) -> int {
+    const d5::Quartic q = d5::quartic_at(s);
+    if (traj) rk::poly_kernel<<<sblocks, 256, 0, st>>>(traj + (size_t)si * n, c0, w.c[0], w.c[1], w.c[2], w.c[3], q.s1, q.s2, q.s3, q.s4, (long)n4);
     if (si == num_save - 1) {
       // (z may be the buffer c0 lives in: a thread writes the four elements it has just read, nothing else)
-      rk::poly_kernel<<<sblocks, 256, 0, st>>>(z, c0, w.c[0], w.c[1], w.c[2], w.c[3], s1, s2, s3, s4, (long)n4);
+      rk::poly_kernel<<<sblocks, 256, 0, st>>>(z, c0, w.c[0], w.c[1], w.c[2], w.c[3], q.s1, q.s2, q.s3, q.s4, (long)n4);
     }
     LAUNCH_CHECK();
-  }
-  if (status != SCLDM_DOPRI5_OK && y0 != z) HIP_TRY(hipMemcpyAsync(z, y0, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // what the solve had reached
-  if (stats) {
-    stats->evaluations = n_eval;
-    stats->accepted = n_acc;
-    stats->rejected = n_rej;
-    stats->first_step = first;
-    stats->status = status;
-    stats->step_log_len = n_log;
-  }
-  if (status == SCLDM_DOPRI5_UNDERFLOW) return fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (t = %.17g, h = %.3g)", t1, hstep);
-  if (status == SCLDM_DOPRI5_MAX_EVALS) return fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (%lld evaluations)", n_eval);
-  return SCLDM_OK;
+    return SCLDM_OK;
+  };
+  auto reached = [&]() -> int {   // what the solve had reached
+    if (y0 != z) HIP_TRY(hipMemcpyAsync(z, y0, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return SCLDM_OK;
+  };
+  d5::Problem problem{first_slope, start_norms, probe, save_time, attempt, accept, emit, reached};
+  // without a trajectory only the state at the last save time (t = 1) is formed: the steps do not depend on the save times
+  return d5::solve(problem, first_step, traj ? 1 : num_save - 1, num_save, step_log, step_log_cap, 3, stats);
 }
 
 extern "C" int scldm_sample_ode_dopri5(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,

@@ -1,12 +1,16 @@
-// Host-side controller of the adaptive Dormand-Prince 5(4) solve (scldm_sample_ode_dopri5): plain C++, no HIP, no handle.  It restates, in
-// the same float64 operations and the same order, what scldm_amd.transport.Sampler._sample_dopri5 does between its kernel launches - the
-// tableau weights handed to the state kernels, the accept / next-step rule and the automatic initial step - so the fused solve and the
-// host-composed one take identical decisions from identical error ratios.  The scldm_dopri5_stage_plan / _control / _initial_h0 /
-// _initial_step entries of the C ABI are thin wrappers over these functions: the controller is testable on a machine without a GPU.
+// Host side of the fused adaptive Dormand-Prince 5(4) solves (scldm_sample_ode_dopri5, scldm_logp_ode_dopri5): plain C++, no HIP, no
+// handle.  It restates, in the same float64 operations and the same order, what scldm_amd.transport.Sampler._sample_dopri5 does between
+// its kernel launches - the tableau weights handed to the state kernels, the accept / next-step rule, the automatic initial step and, in
+// solve() at the end of this file, the step loop itself - so the fused solves and the host-composed one take identical decisions from
+// identical error ratios.  The scldm_dopri5_stage_plan / _control / _initial_h0 / _initial_step entries of the C ABI are thin wrappers
+// over these functions, and tests/dopri5_driver_shim.cpp gives solve() a C face: all of it is tested on a machine without a GPU.
 #pragma once
 #include <cmath>
+#include <cstddef>
 
 #include "../../include/scldm_hip.h"
+
+int scldm_fail(int code, const char* fmt, ...);   // records the message of scldm_last_error() (api.hip; a test shim brings its own)
 
 #pragma clang fp contract(off)   // every product and sum rounded on its own, as Python's float arithmetic
 
@@ -75,5 +79,111 @@ inline double initial_step(double h0, double d1, double d2) {
   return pymin(100.0 * h0, h1);
 }
 
+// libm's pow as a call the optimiser cannot rewrite (pow(x, 0.5) would become a square root: correctly rounded, where the host-composed
+// solver's Python `x ** 0.5` is libm's pow - the two routes have to take the same decisions from the same doubles)
+inline double libm_pow(double x, double y) {
+  volatile double yv = y;
+  return std::pow(x, yv);
+}
+
+// weights with their mask -> keep(i, j, w[j]) for the i-th slope j that is not a structural zero; the number kept.  The state kernels
+// take such compacted (pointer, coefficient) lists, each solve in its own struct
+template <class Keep>
+inline int compact(const float* w, unsigned mask, Keep&& keep) {
+  int n = 0;
+  for (int j = 0; j < 7; ++j)
+    if ((mask >> j) & 1u) keep(n++, j, w[j]);
+  return n;
+}
+
+// where the quartic interpolant of an accepted step is evaluated: s in [0, 1] held in double, its powers rounded to fp32 once each
+struct Quartic {
+  float s1, s2, s3, s4;
+};
+inline Quartic quartic_at(double s) { return Quartic{(float)s, (float)(s * s), (float)(s * s * s), (float)(s * s * s * s)}; }
+
+struct Step {               // one attempted step as the problem sees it
+  double t0, h;             // float64, as the decisions hold them; the state kernels take the plan's fp32 roundings
+  long long n_eval;         // evaluations made before this step, rejected steps included
+  scldm_dopri5_plan plan;
+};
+// What differs between the solves, as callables (each entry passes its lambdas).  All but save_time return an SCLDM_* code.
+template <class FirstSlope, class StartNorms, class Probe, class SaveTime, class Attempt, class Accept, class Emit, class Reached>
+struct Problem {
+  FirstSlope first_slope;   // ()                          f(0, y0) into slope 0
+  StartNorms start_norms;   // (double ms[2])              the mean squares of y0 / scale and f0 / scale, scale = atol + rtol |y0|
+  Probe probe;              // (double h0, double* ms)     y0 + h0 f0, its evaluation at (float)(0 + h0) into slope 1, the mean square of (f1 - f0) / scale
+  SaveTime save_time;       // (int si) -> double
+  Attempt attempt;          // (const Step&, double* ms)   the step's six evaluations and its one host read: the mean squared error ratio
+  Accept accept;            // (const Step&, bool fit)     fit the interpolant (THIS step's weights) if asked, then end -> current state, last slope -> first
+  Emit emit;                // (int si, double s)          save point si from the last accepted step's interpolant at s (quartic_at)
+  Reached reached;          // ()                          the solve failed: hand out the current state
+};
+template <class... F>
+Problem(F...) -> Problem<F...>;
+
+// The step loop of both fused solves: the first step, attempted steps until every save time first_save .. num_save - 1 lies inside an
+// accepted one (time runs from 0; steps are never clipped to a save time), the statistics and the step log (NULL, or step_log_cap rows
+// of log_stride doubles: t0, h, accepted (1.0 / 0.0) and, with 4, the error ratio).  The float64 decisions are Sampler._sample_dopri5's,
+// in its order.  A problem's non-zero code ends the solve and is returned as it is, stats untouched; SCLDM_ERR_SOLVER comes with stats.
+template <class P>
+int solve(P& p, double first_step, int first_save, int num_save, double* step_log, int step_log_cap, int log_stride, scldm_dopri5_stats* stats) {
+  int rc;
+  scldm_dopri5_stats n{};   // the counters, in the struct they are reported in
+  if ((rc = p.first_slope())) return rc;
+  n.evaluations = 1;
+  double hstep = first_step;
+  if (!(first_step > 0.0)) {
+    double ms[2];
+    if ((rc = p.start_norms(ms))) return rc;
+    const double dn0 = std::sqrt(ms[0]), dn1 = std::sqrt(ms[1]);
+    const double h0 = initial_h0(dn0, dn1);
+    if ((rc = p.probe(h0, ms))) return rc;
+    ++n.evaluations;
+    hstep = initial_step(h0, dn1, std::sqrt(ms[0]) / h0);
+  }
+  n.first_step = hstep;
+  double t0 = 0.0, t1 = 0.0;
+  bool underflow = !(t1 + hstep > t1);
+  for (int si = first_save; si < num_save && n.status == SCLDM_DOPRI5_OK; ++si) {
+    const double next_t = p.save_time(si);
+    while (next_t > t1) {   // advance until the save time lies inside the last accepted step
+      if (underflow) { n.status = SCLDM_DOPRI5_UNDERFLOW; break; }
+      if (n.evaluations > 100000) { n.status = SCLDM_DOPRI5_MAX_EVALS; break; }
+      Step step{t1, hstep, n.evaluations, {}};
+      stage_plan(step.t0, step.h, &step.plan);
+      double ms;
+      if ((rc = p.attempt(step, &ms))) return rc;
+      n.evaluations += kStages;
+      const double ratio = libm_pow(ms, 0.5);
+      scldm_dopri5_control_out co;
+      control(step.t0, step.h, ratio, &co);
+      if (step_log && n.step_log_len < step_log_cap) {
+        double* row = step_log + (size_t)log_stride * n.step_log_len++;
+        row[0] = step.t0;
+        row[1] = step.h;
+        row[2] = co.accepted ? 1.0 : 0.0;
+        if (log_stride > 3) row[3] = ratio;
+      }
+      if (co.accepted) {
+        ++n.accepted;
+        if ((rc = p.accept(step, next_t <= co.t1))) return rc;
+        t0 = step.t0;
+        t1 = co.t1;
+      } else ++n.rejected;
+      hstep = co.h_next;
+      underflow = co.underflow != 0;
+    }
+    if (n.status != SCLDM_DOPRI5_OK) break;
+    if ((rc = p.emit(si, (next_t - t0) / (t1 - t0)))) return rc;
+  }
+  if (n.status != SCLDM_DOPRI5_OK && (rc = p.reached())) return rc;
+  if (stats) *stats = n;
+  if (n.status == SCLDM_DOPRI5_UNDERFLOW) return scldm_fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (t = %.17g, h = %.3g)", t1, hstep);
+  if (n.status == SCLDM_DOPRI5_MAX_EVALS) return scldm_fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (%lld evaluations)", n.evaluations);
+  return SCLDM_OK;
+}
+
 }  // namespace dopri5
 }  // namespace scldm
+

@@ -1,8 +1,8 @@
 // scldm_logp_ode_dopri5: the reference's default likelihood solve (Sampler.sample_ode_likelihood(sampling_method="dopri5")) as one call
 // (include/scldm_hip.h).  Part of logp_api.hip's translation unit: it uses that file's workspace layout and logp.hpp's evaluation kernels.
-// The controller is dopri5_ctl.hpp (plain C++, shared with scldm_sample_ode_dopri5), the state kernels are logp_dopri5.hpp; the dense
-// output of the accepted step that contains s = 1 goes through scldm_rk_dense / scldm_rk_poly (the delta_logp arrays are padded to a
-// multiple of four with zeros for them).
+// The step loop and its decisions are dopri5_ctl.hpp (plain C++: solve(), shared with scldm_sample_ode_dopri5); this file is the problem
+// that loop drives.  The state kernels are logp_dopri5.hpp; the dense output of the accepted step that contains s = 1 goes through
+// scldm_rk_dense / scldm_rk_poly (the delta_logp arrays are padded to a multiple of four with zeros for them).
 //
 // One attempted step = the first stage point (scldm_rk_combine on x and on delta_logp), then six evaluations - seed kernel, recording
 // forward, input-gradient-only backward, ONE state kernel each - the row-sum kernel, and an 8-byte read of the mean squared error ratio.
@@ -12,13 +12,6 @@
 #include "logp_dopri5.hpp"
 
 namespace {
-
-// libm's pow as a call the optimiser cannot rewrite (d5_pow of dopri5_api.inc: pow(x, 0.5) would become a square root, where the
-// host-composed solver's Python `x ** 0.5` is libm's pow - the routes have to take the same decisions from the same doubles)
-double ld5_pow(double x, double y) {
-  volatile double yv = y;
-  return std::pow(x, yv);
-}
 
 struct LogpD5Ws {
   LogpWs ev;          // the evaluation's buffers (train workspace in front)
@@ -74,13 +67,13 @@ extern "C" int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, f
   if (stats) *stats = scldm_dopri5_stats{};
   // (every argument check before any HIP call)
   if (!h || !w || !z || !logp_out || !saved || !ws_) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: null pointer argument (handle / weights / z / logp_out / saved / ws)");
-  if (!(atol > 0.0) || !(rtol >= 0.0)) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: atol must be > 0 and rtol >= 0 (got %g, %g)", atol, rtol);
   if (B < 1) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: B must be positive");
+  int rc = dopri5_check_tolerances("scldm_logp_ode_dopri5", atol, rtol, step_log, step_log_cap);
+  if (rc) return rc;
   if (cell_offset < 0 || cells_total < cell_offset + B)
     return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: cells_total (%lld) < cell_offset (%lld) + B (%d)", cells_total, cell_offset, B);
   if (probe && !probe_per_solve)
     return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: a given probe needs probe_per_solve (the number of evaluations of an adaptive solve is not known ahead)");
-  if (step_log && step_log_cap < 0) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: step_log_cap must be >= 0");
   if (n_pass < 0 || n_pass > SCLDM_MAX_CLASSES) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: n_pass out of range");
   if (n_pass > 0 && (!ulabels || !pass_mask || !pass_scale || n_urows <= 0)) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: conditional passes need labels/masks/scales");
   if (n_pass > 0 && !cell_row && n_urows != B) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: cell_row is NULL but n_urows (%d) != B (%d)", n_urows, B);
@@ -95,12 +88,8 @@ extern "C" int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, f
   const int e = 16 * c.n_embed_input, R = 2 * B;
   const long long N = (long long)(2 + n_pass) * B;
   if (c.seq_len != 16 || e % 4 || N * (e / 4) > 0x7fffffffll || N > 0x7fffffffll) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: state too large or unsupported shape");
-  if (!h->rk_host) return fail(SCLDM_ERR_STATE, "scldm_logp_ode_dopri5: the handle has no read-back slot");
   hipStream_t st = (hipStream_t)stream_;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(st, &cap));
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_dopri5: the stream is capturing - the solve reads its error ratio once per step and cannot be captured into a graph");
+  if ((rc = dopri5_check_stream("scldm_logp_ode_dopri5", h->rk_host, st))) return rc;
 
   const LogpD5Ws k = carve_logp_d5(h, B, n_pass, precision, ws_);
   const long long n = (long long)R * e, R4 = (R + 3) / 4 * 4;
@@ -143,46 +132,42 @@ extern "C" int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, f
   geom.B = B; geom.e = e; geom.P = n_pass;
   for (int p = 0; p < n_pass; ++p) geom.scale[p] = pass_scale[p];
 
-  long long n_eval = 0;
-  // forward and seeded backward at state x and solver time s (the model sees t = 1 - s); the evaluation index is the running count in
-  // execution order (rejected steps included), or 0 throughout with one probe per solve
-  auto evaluate = [&](const float* x, float s) -> int {
+  float *KX[7], *KL[7];
+  for (int i = 0; i < 7; ++i) { KX[i] = k.kx[i]; KL[i] = k.kl[i]; }
+  // three state buffers in rotation: the start of the last accepted step (c0 of its interpolant), the current state, the stage point
+  float *c0x = k.yx[1], *y0x = z, *stx = k.yx[0];
+  float *c0l = k.yl[2], *y0l = k.yl[0], *stl = k.yl[1];
+
+  // forward and seeded backward at state x and solver time s (the model sees t = 1 - s); `index` is the evaluation's place in execution
+  // order (rejected steps included): it selects the probe, unless one probe serves the whole solve
+  auto evaluate = [&](const float* x, float s, long long index) -> int {
     sa.x = x;
     sa.tval = 1.0f - s;
-    sa.g.step = probe_per_solve ? 0u : (uint32_t)n_eval;
-    ++n_eval;
+    sa.g.step = probe_per_solve ? 0u : (uint32_t)index;
     logp::seed_kernel<<<cdiv(N * (e / 4), 256), 256, 0, st>>>(sa);
     LAUNCH_CHECK();
     int rc = scldm_dit_train_forward(h, w, k.ev.xin, k.ev.t, c.n_classes > 0 ? lab_ptr : nullptr, (int)N, k.ev.out, precision, saved, ws_, st);
     if (rc) return rc;
     return scldm_dit_train_backward_dx(h, w, k.ev.xin, c.n_classes > 0 ? lab_ptr : nullptr, k.ev.dout, (int)N, k.ev.dxr, precision, saved, ws_, st);
   };
-  float *KX[7], *KL[7];
-  for (int i = 0; i < 7; ++i) { KX[i] = k.kx[i]; KL[i] = k.kl[i]; }
   // weights with their mask -> the compacted list the state kernels take
   auto comb = [&](const float* wt, unsigned mask) {
     ld::Comb a{};
-    for (int j = 0; j < 7; ++j)
-      if ((mask >> j) & 1u) {
-        a.kx[a.n_k] = KX[j];
-        a.kl[a.n_k] = KL[j];
-        a.c[a.n_k] = wt[j];
-        ++a.n_k;
-      }
+    a.n_k = d5::compact(wt, mask, [&](int i, int j, float cj) { a.kx[i] = KX[j]; a.kl[i] = KL[j]; a.c[i] = cj; });
     return a;
   };
-  auto slopes = [&](int slot, const float* y0x, const float* y0l, float* outx, float* outl, const ld::Comb& cb) -> int {
+  auto slopes = [&](int slot, const float* y_fromx, const float* y_froml, float* outx, float* outl, const ld::Comb& cb) -> int {
     ld::StageArgs a{};
     a.g = geom;
     a.kx_new = KX[slot]; a.kl_new = KL[slot];
-    a.y0x = y0x; a.y0l = y0l; a.outx = outx; a.outl = outl;
+    a.y0x = y_fromx; a.y0l = y_froml; a.outx = outx; a.outl = outl;
     a.c = cb;
     ld::stage_kernel<<<rblocks, 256, 0, st>>>(a);
     LAUNCH_CHECK();
     return SCLDM_OK;
   };
   // mean over the packed state of ((a - b) / (atol + rtol |y0|))^2 -> mean[slot]
-  auto norm = [&](const float* ax, const float* al, const float* bx, const float* bl, const float* y0x, const float* y0l, int slot) -> int {
+  auto norm = [&](const float* ax, const float* al, const float* bx, const float* bl, int slot) -> int {
     const ld::NormArgs a{ax, al, bx, bl, y0x, y0l, R, e, atol_f, rtol_f, k.partial};
     ld::norm_kernel<<<rblocks, 256, 0, st>>>(a);
     ld::mean_kernel<<<1, 256, 0, st>>>(k.partial, R, (double)R * (double)(e + 1), k.mean + slot);
@@ -190,53 +175,41 @@ extern "C" int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, f
     return SCLDM_OK;
   };
 
-  // three state buffers in rotation: the start of the last accepted step (c0 of its interpolant), the current state, the stage point
-  float *c0x = k.yx[1], *y0x = z, *stx = k.yx[0];
-  float *c0l = k.yl[2], *y0l = k.yl[0], *stl = k.yl[1];
-  long long n_acc = 0, n_rej = 0;
-  int n_log = 0, status = SCLDM_DOPRI5_OK, rc;
-  volatile double* host = h->rk_host;
-
-  // f0 = f(0, y0)
-  if ((rc = evaluate(y0x, 0.0f))) return rc;
-  if ((rc = slopes(0, nullptr, nullptr, nullptr, nullptr, ld::Comb{}))) return rc;
-  double hstep = first_step;
-  if (!(first_step > 0.0)) {
-    if ((rc = norm(y0x, y0l, nullptr, nullptr, y0x, y0l, 0))) return rc;
-    if ((rc = norm(KX[0], KL[0], nullptr, nullptr, y0x, y0l, 1))) return rc;
-    HIP_TRY(hipMemcpyAsync((void*)host, k.mean, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const double dn0 = std::sqrt(host[0]), dn1 = std::sqrt(host[1]);
-    const double h0 = d5::initial_h0(dn0, dn1);
+  // what dopri5_ctl.hpp's solve() calls, each in the order it enqueues
+  auto first_slope = [&]() -> int {
+    int rc;
+    if ((rc = evaluate(y0x, 0.0f, 0))) return rc;
+    return slopes(0, nullptr, nullptr, nullptr, nullptr, ld::Comb{});
+  };
+  auto start_norms = [&](double* ms) -> int {
+    int rc;
+    if ((rc = norm(y0x, y0l, nullptr, nullptr, 0))) return rc;
+    if ((rc = norm(KX[0], KL[0], nullptr, nullptr, 1))) return rc;
+    return dopri5_read_back(h->rk_host, k.mean, 2, ms, st);
+  };
+  auto trial = [&](double h0, double* ms) -> int {
     const float h0f = (float)h0;
     const float* kp[1] = {KX[0]};
+    int rc;
     if ((rc = scldm_rk_combine(stx, y0x, kp, &h0f, 1, n, st))) return rc;   // y0 + h0 f0
     kp[0] = KL[0];
     if ((rc = scldm_rk_combine(stl, y0l, kp, &h0f, 1, R4, st))) return rc;
-    if ((rc = evaluate(stx, (float)(0.0 + h0)))) return rc;
+    if ((rc = evaluate(stx, (float)(0.0 + h0), 1))) return rc;
     if ((rc = slopes(1, nullptr, nullptr, nullptr, nullptr, ld::Comb{}))) return rc;
-    if ((rc = norm(KX[1], KL[1], KX[0], KL[0], y0x, y0l, 0))) return rc;
-    HIP_TRY(hipMemcpyAsync((void*)host, k.mean, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    hstep = d5::initial_step(h0, dn1, std::sqrt(host[0]) / h0);
-  }
-  const double first = hstep;
-  const double next_t = 1.0;    // the one save point that is formed
-  double t0 = 0.0, t1 = 0.0;
-  bool underflow = !(t1 + hstep > t1);
-  while (next_t > t1) {   // advance until s = 1 lies inside the last accepted step (steps are never clipped to it)
-    if (underflow) { status = SCLDM_DOPRI5_UNDERFLOW; break; }
-    if (n_eval > 100000) { status = SCLDM_DOPRI5_MAX_EVALS; break; }
-    const double ta = t1;
-    scldm_dopri5_plan plan;
-    d5::stage_plan(ta, hstep, &plan);
+    if ((rc = norm(KX[1], KL[1], KX[0], KL[0], 0))) return rc;
+    return dopri5_read_back(h->rk_host, k.mean, 1, ms, st);
+  };
+  auto save_time = [](int) { return 1.0; };   // the one save point that is formed (steps are never clipped to it)
+  auto attempt = [&](const d5::Step& step, double* ms) -> int {
+    const scldm_dopri5_plan& plan = step.plan;
+    int rc;
     {   // the first stage point from the step's first slope (FSAL)
       const ld::Comb cb = comb(plan.a[0], plan.a_mask[0]);
       if ((rc = scldm_rk_combine(stx, y0x, cb.kx, cb.c, cb.n_k, n, st))) return rc;
       if ((rc = scldm_rk_combine(stl, y0l, cb.kl, cb.c, cb.n_k, R4, st))) return rc;
     }
     for (int i = 0; i < d5::kStages; ++i) {
-      if ((rc = evaluate(stx, plan.t_stage[i]))) return rc;
+      if ((rc = evaluate(stx, plan.t_stage[i], step.n_eval + i))) return rc;
       if (i + 1 < d5::kStages) {
         if ((rc = slopes(i + 1, y0x, y0l, stx, stl, comb(plan.a[i + 1], plan.a_mask[i + 1])))) return rc;
       } else {   // the last stage point is the 5th-order solution y1 (FSAL: K[6] = f(ta + h, y1))
@@ -252,60 +225,41 @@ extern "C" int scldm_logp_ode_dopri5(scldm_dit* h, const scldm_dit_weights* w, f
         LAUNCH_CHECK();
       }
     }
-    HIP_TRY(hipMemcpyAsync((void*)host, k.mean, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));      // the step's one host read
-    const double ratio = ld5_pow(host[0], 0.5);
-    scldm_dopri5_control_out co;
-    d5::control(ta, hstep, ratio, &co);
-    if (step_log && n_log < step_log_cap) {
-      step_log[4 * n_log] = ta;
-      step_log[4 * n_log + 1] = hstep;
-      step_log[4 * n_log + 2] = co.accepted ? 1.0 : 0.0;
-      step_log[4 * n_log + 3] = ratio;
-      ++n_log;
+    return dopri5_read_back(h->rk_host, k.mean, 1, ms, st);      // the step's one host read
+  };
+  auto accept = [&](const d5::Step& step, bool fit_dense) -> int {
+    if (fit_dense) {   // s = 1 falls inside this step
+      const scldm_dopri5_plan& plan = step.plan;
+      const ld::Comb cb = comb(plan.mid, plan.mid_mask);
+      int rc;
+      if ((rc = scldm_rk_dense(y0x, stx, cb.kx, cb.c, cb.n_k, KX[0], KX[6], plan.h, plan.two_h, n, k.cx[0], k.cx[1], k.cx[2], k.cx[3], st))) return rc;
+      if ((rc = scldm_rk_dense(y0l, stl, cb.kl, cb.c, cb.n_k, KL[0], KL[6], plan.h, plan.two_h, R4, k.cl[0], k.cl[1], k.cl[2], k.cl[3], st))) return rc;
     }
-    if (co.accepted) {
-      ++n_acc;
-      if (next_t <= co.t1) {   // s = 1 falls inside this step: fit its interpolant
-        const ld::Comb cb = comb(plan.mid, plan.mid_mask);
-        if ((rc = scldm_rk_dense(y0x, stx, cb.kx, cb.c, cb.n_k, KX[0], KX[6], plan.h, plan.two_h, n, k.cx[0], k.cx[1], k.cx[2], k.cx[3], st))) return rc;
-        if ((rc = scldm_rk_dense(y0l, stl, cb.kl, cb.c, cb.n_k, KL[0], KL[6], plan.h, plan.two_h, R4, k.cl[0], k.cl[1], k.cl[2], k.cl[3], st))) return rc;
-      }
-      float* freed = c0x;
-      c0x = y0x; y0x = stx; stx = freed;
-      freed = c0l;
-      c0l = y0l; y0l = stl; stl = freed;
-      std::swap(KX[0], KX[6]);
-      std::swap(KL[0], KL[6]);
-      t0 = ta;
-      t1 = co.t1;
-    } else ++n_rej;
-    hstep = co.h_next;
-    underflow = co.underflow != 0;
-  }
-  if (status == SCLDM_DOPRI5_OK) {
-    const double s = (next_t - t0) / (t1 - t0);
-    const float s1 = (float)s, s2 = (float)(s * s), s3 = (float)(s * s * s), s4 = (float)(s * s * s * s);
+    float* freed = c0x;
+    c0x = y0x; y0x = stx; stx = freed;
+    freed = c0l;
+    c0l = y0l; y0l = stl; stl = freed;
+    std::swap(KX[0], KX[6]);
+    std::swap(KL[0], KL[6]);
+    return SCLDM_OK;
+  };
+  auto emit = [&](int, double s) -> int {
+    const d5::Quartic q = d5::quartic_at(s);
+    int rc;
     // (z may be the buffer c0 lives in: a thread writes the four elements it has just read, nothing else)
-    if ((rc = scldm_rk_poly(z, c0x, k.cx[0], k.cx[1], k.cx[2], k.cx[3], s1, s2, s3, s4, n, st))) return rc;
-    if ((rc = scldm_rk_poly(k.l_end, c0l, k.cl[0], k.cl[1], k.cl[2], k.cl[3], s1, s2, s3, s4, R4, st))) return rc;
+    if ((rc = scldm_rk_poly(z, c0x, k.cx[0], k.cx[1], k.cx[2], k.cx[3], q.s1, q.s2, q.s3, q.s4, n, st))) return rc;
+    if ((rc = scldm_rk_poly(k.l_end, c0l, k.cl[0], k.cl[1], k.cl[2], k.cl[3], q.s1, q.s2, q.s3, q.s4, R4, st))) return rc;
     const float cz = (float)(-0.5 * (double)e * std::log(2.0 * 3.14159265358979323846));
     logp::final_kernel<<<rblocks, 256, 0, st>>>(z, k.l_end, R, e, cz, logp_out);
     LAUNCH_CHECK();
     if (dlogp_out) HIP_TRY(hipMemcpyAsync(dlogp_out, k.l_end, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else {   // what the solve had reached
+    return SCLDM_OK;
+  };
+  auto reached = [&]() -> int {   // what the solve had reached
     if (y0x != z) HIP_TRY(hipMemcpyAsync(z, y0x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (dlogp_out) HIP_TRY(hipMemcpyAsync(dlogp_out, y0l, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
-  }
-  if (stats) {
-    stats->evaluations = n_eval;
-    stats->accepted = n_acc;
-    stats->rejected = n_rej;
-    stats->first_step = first;
-    stats->status = status;
-    stats->step_log_len = n_log;
-  }
-  if (status == SCLDM_DOPRI5_UNDERFLOW) return fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (s = %.17g, h = %.3g)", t1, hstep);
-  if (status == SCLDM_DOPRI5_MAX_EVALS) return fail(SCLDM_ERR_SOLVER, "dopri5: step size underflow / too many evaluations (%lld evaluations)", n_eval);
-  return SCLDM_OK;
+    return SCLDM_OK;
+  };
+  d5::Problem problem{first_slope, start_norms, trial, save_time, attempt, accept, emit, reached};
+  return d5::solve(problem, first_step, 0, 1, step_log, step_log_cap, 4, stats);
 }

@@ -1087,16 +1087,25 @@ class DiT(nn.Module):
                                               traj.data_ptr() if traj is not None else None, C.byref(stats), log, cap, self._prec(),
                                               ws.data_ptr(), _stream_ptr())
         del keep
-        if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
+        self._dopri5_finish(rc, "scldm_sample_ode_dopri5", stats, log, cap, 3)
+        return traj if return_trajectory else z
+
+    def _dopri5_finish(self, rc, entry, stats, log, cap, width):
+        """After a fused dopri5 entry returned: rejected arguments raise with the library's message; otherwise `last_solver_stats` is decoded
+        from stats and the step log (`width` 3: t0, dt, accepted; 4: + the error ratio and the likelihood solve's keys), then failures raise."""
+        L = _lib.lib()
+        if rc == -1:    # SCLDM_ERR_SHAPE
             raise ValueError(L.scldm_last_error().decode())
-        steps = [(log[3 * i], log[3 * i + 1], log[3 * i + 2] != 0.0) for i in range(min(stats.step_log_len, cap))]
-        self.last_solver_stats = {"evaluations": int(stats.evaluations), "rejected": int(stats.rejected),
-                                  "accepted_steps": [(t, d) for t, d, ok in steps if ok], "rejected_steps": [(t, d) for t, d, ok in steps if not ok],
-                                  "first_step": stats.first_step}
+        rows = [log[width * i:width * (i + 1)] for i in range(min(stats.step_log_len, cap))]
+        st = {"evaluations": int(stats.evaluations), "rejected": int(stats.rejected),
+              "accepted_steps": [(r[0], r[1]) for r in rows if r[2] != 0.0], "rejected_steps": [(r[0], r[1]) for r in rows if r[2] == 0.0],
+              "first_step": stats.first_step}
+        if width == 4:
+            st.update(accepted=int(stats.accepted), error_ratios=[r[3] for r in rows], status=int(stats.status))
+        self.last_solver_stats = st
         if rc == _lib.ERR_SOLVER:
             raise RuntimeError("dopri5: step size underflow / too many evaluations")
-        _lib.check(rc, "scldm_sample_ode_dopri5")
-        return traj if return_trajectory else z
+        _lib.check(rc, entry)
 
     # ------------------------------------------------------------------ fused SDE sampler (transport.py:269-322 + integrators.py:7-75)
     def sde_noise(self, seed: int, step: int, B: int, cell_offset: int = 0, cells_total: int | None = None) -> torch.Tensor:
@@ -1366,16 +1375,7 @@ class DiT(nn.Module):
                                          probe.data_ptr() if probe is not None else None, int(per_solve), seed, cell_offset, total,
                                          logp.data_ptr(), None, C.byref(stats), log, cap, prec, saved.data_ptr(), ws.data_ptr(), _stream_ptr())
         del keep
-        if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
-            raise ValueError(L.scldm_last_error().decode())
-        steps = [(log[4 * i], log[4 * i + 1], log[4 * i + 2] != 0.0, log[4 * i + 3]) for i in range(min(stats.step_log_len, cap))]
-        self.last_solver_stats = {"evaluations": int(stats.evaluations), "accepted": int(stats.accepted), "rejected": int(stats.rejected),
-                                  "accepted_steps": [(t, d) for t, d, ok, _ in steps if ok],
-                                  "rejected_steps": [(t, d) for t, d, ok, _ in steps if not ok], "error_ratios": [r for _, _, _, r in steps],
-                                  "first_step": stats.first_step, "status": int(stats.status)}
-        if rc == _lib.ERR_SOLVER:
-            raise RuntimeError("dopri5: step size underflow / too many evaluations")
-        _lib.check(rc, "scldm_logp_ode_dopri5")
+        self._dopri5_finish(rc, "scldm_logp_ode_dopri5", stats, log, cap, 4)
         return logp, z
 
     # ------------------------------------------------------------------ bench hook

@@ -1,6 +1,7 @@
 """CPU-side checks of the fused adaptive sampler (scldm_sample_ode_dopri5): the ABI surface, the refusal of a handle outside the fused
-family (before any HIP call) and the solve's controller - the handle-free scldm_dopri5_* entries, plain C++ - against the float64 oracle
-(oracle/transport.py: sample_ode_dopri5) and against the weights the host-composed solver hands to its kernels."""
+family (before any HIP call) and the solve's host side, plain C++ (csrc/dopri5_ctl.hpp) - the handle-free scldm_dopri5_* entries and the
+step loop both fused solves run, compiled into a test shim - against the float64 oracle (oracle/transport.py: sample_ode_dopri5) and
+against the weights the host-composed solver hands to its kernels."""
 import ctypes as C
 import os
 import re
@@ -107,47 +108,141 @@ def test_stage_plan_is_bitwise_what_the_composed_solver_hands_to_its_kernels(t0,
     assert _bits([p.h, p.two_h]) == _bits([f32(h), f32(2 * h)])
 
 
-def _c_stepper(L, x, model_fn, num_steps, atol, rtol):
-    """Dormand-Prince in float64 numpy with the oracle's state arithmetic; the stage times, the structural zeros, the accept decision, the
-    next step and the initial step come from the C controller."""
-    from oracle.transport import _DP_BETA, _DP_C_ERROR, _rms64
-    shape, nb = tuple(x.shape), x.shape[0]
-    n_eval = 0
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    """The shipped step loop (scldm::dopri5::solve, csrc/dopri5_ctl.hpp) behind tests/dopri5_driver_shim.cpp, compiled with the first host
+    compiler there is.  No compiler is a failure, not a skip: the loop would go untested."""
+    import shutil
+    import subprocess
+    from scldm_amd import _lib
+    cxx = next((c for c in ("c++", "g++", "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if shutil.which(c)), None)
+    assert cxx, "no host C++ compiler (c++, g++, ROCm's clang++): the dopri5 step loop cannot be tested"
+    so = str(tmp_path_factory.mktemp("dopri5_driver") / "dopri5_driver_shim.so")
+    cmd = [cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(ROOT, "tests", "dopri5_driver_shim.cpp"), "-o", so]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, " ".join(cmd) + "\n" + r.stderr
 
-    def f(t32, y):
-        nonlocal n_eval
-        n_eval += 1
-        tv = torch.full((nb,), float(t32), dtype=torch.float32)
-        return model_fn(torch.from_numpy(y.reshape(shape).copy()), tv).detach().to(torch.float64).numpy().reshape(-1)
+    class Step(C.Structure):          # scldm::dopri5::Step
+        _fields_ = [("t0", C.c_double), ("h", C.c_double), ("n_eval", C.c_longlong), ("plan", _lib.Dopri5Plan)]
 
+    pd = C.POINTER(C.c_double)
+    members = [("first_slope", C.CFUNCTYPE(C.c_int)), ("start_norms", C.CFUNCTYPE(C.c_int, pd)), ("probe", C.CFUNCTYPE(C.c_int, C.c_double, pd)),
+               ("save_time", C.CFUNCTYPE(C.c_double, C.c_int)), ("attempt", C.CFUNCTYPE(C.c_int, C.POINTER(Step), pd)),
+               ("accept", C.CFUNCTYPE(C.c_int, C.POINTER(Step), C.c_int)), ("emit", C.CFUNCTYPE(C.c_int, C.c_int, C.c_double)),
+               ("reached", C.CFUNCTYPE(C.c_int))]
+
+    class Callbacks(C.Structure):     # shim_callbacks of the shim, in its order
+        _fields_ = members
+
+    D = C.CDLL(so)
+    D.Callbacks = Callbacks
+    D.dopri5_shim_solve.argtypes = [C.POINTER(Callbacks), C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                    C.POINTER(_lib.Dopri5Stats)]
+    D.dopri5_shim_solve.restype = C.c_int
+    D.dopri5_shim_message.restype = C.c_char_p
+    return D
+
+
+def _drive(D, problem, save_times, first_step=0.0, first_save=1, cap=4096, stride=3):
+    """One solve of the shipped loop over `problem` (an object with the members the loop calls, save_time apart): return code, stats, the
+    step log's written rows (the rest of the buffer must be untouched) and how often emit / reached were called."""
+    from scldm_amd import _lib
+    calls = {"emit": [], "reached": 0}
+    raised = []
+
+    def guard(fn):                # an exception must not pass through the C frames: it ends the solve with a code and is raised after it
+        def run(*a):
+            try:
+                return fn(*a) or 0
+            except BaseException as e:     # noqa: BLE001
+                raised.append(e)
+                return -99
+        return run
+
+    def emit(si, s):
+        calls["emit"].append((si, s))
+        return problem.emit(si, s)
+
+    def reached():
+        calls["reached"] += 1
+        return problem.reached()
+
+    members = dict(first_slope=guard(problem.first_slope), start_norms=guard(problem.start_norms), probe=guard(problem.probe),
+                   save_time=lambda si: float(save_times[si]), attempt=guard(problem.attempt), accept=guard(problem.accept), emit=guard(emit),
+                   reached=guard(reached))
+    cb = D.Callbacks(**{name: typ(members[name]) for name, typ in D.Callbacks._fields_})
+    slack = 4                     # rows past the cap, which must stay as they are
+    log = (C.c_double * (stride * (cap + slack)))(*([-7.0] * (stride * (cap + slack))))
+    stats = _lib.Dopri5Stats()
+    rc = D.dopri5_shim_solve(C.byref(cb), float(first_step), first_save, len(save_times), log, cap, stride, C.byref(stats))
+    if raised:
+        raise raised[0]
+    rows = [tuple(log[stride * i:stride * (i + 1)]) for i in range(stats.step_log_len)]
+    assert all(v == -7.0 for v in log[stride * stats.step_log_len:]), "the step log was written past step_log_len rows"
+    return rc, stats, rows, calls
+
+
+class _OracleArithmetic:
+    """Dormand-Prince's state arithmetic in float64 numpy exactly as oracle/transport.py writes it (its `@` products and torch.sin fix the
+    bits); WHEN each piece runs, with which step, is the shipped loop's business."""
+
+    def __init__(self, x, model_fn, atol, rtol):
+        self.shape, self.nb, self.model_fn, self.atol, self.rtol = tuple(x.shape), x.shape[0], model_fn, atol, rtol
+        self.y0 = x.detach().to(torch.float64).numpy().reshape(-1).copy()
+        self.n_eval = 0
+
+    def f(self, t32, y):
+        self.n_eval += 1
+        tv = torch.full((self.nb,), float(t32), dtype=torch.float32)
+        return self.model_fn(torch.from_numpy(y.reshape(self.shape).copy()), tv).detach().to(torch.float64).numpy().reshape(-1)
+
+    @staticmethod
+    def _ms(a):                   # _rms64 before its square root
+        return float(np.mean(np.square(np.abs(a))))
+
+    def first_slope(self):
+        self.f0 = self.f(np.float32(0.0), self.y0)
+
+    def start_norms(self, ms):
+        self.scale = self.atol + np.abs(self.y0) * self.rtol
+        ms[0], ms[1] = self._ms(self.y0 / self.scale), self._ms(self.f0 / self.scale)
+
+    def probe(self, h0, ms):
+        ms[0] = self._ms((self.f(np.float32(0.0 + h0), self.y0 + h0 * self.f0) - self.f0) / self.scale)
+
+    def attempt(self, step, ms):
+        from oracle.transport import _DP_BETA, _DP_C_ERROR
+        st, y0 = step.contents, self.y0
+        assert st.n_eval == self.n_eval
+        dt, p = st.h, st.plan
+        k = np.empty((7, y0.size))
+        k[0] = self.f0
+        for i, beta in enumerate(_DP_BETA):
+            assert p.a_mask[i] == sum(1 << j for j, b in enumerate(beta) if b != 0.0)
+            yi = y0 + (beta * dt) @ k[:i + 1]
+            k[i + 1] = self.f(p.t_stage[i], yi)
+        ms[0] = self._ms(((dt * _DP_C_ERROR) @ k) / (self.atol + self.rtol * np.maximum(np.abs(y0), np.abs(yi))))
+        self.y1, self.f1 = yi, k[6]
+
+    def accept(self, step, fit_dense):
+        self.y0, self.f0 = self.y1, self.f1
+
+    def emit(self, si, s):
+        assert 0.0 <= s <= 1.0, s
+
+    def reached(self):
+        pass
+
+
+def _c_stepper(D, x, model_fn, num_steps, atol, rtol, **kw):
+    """The shipped loop over the oracle's arithmetic: (accepted, rejected) (t0, dt) lists from the loop's own step log, the number of
+    model evaluations made, and what _drive returns."""
+    problem = _OracleArithmetic(x, model_fn, atol, rtol)
     ts = torch.linspace(0.0, 1.0, num_steps).to(torch.float64).numpy()
-    y0 = x.detach().to(torch.float64).numpy().reshape(-1).copy()
-    f0 = f(np.float32(ts[0]), y0)
-    scale = atol + np.abs(y0) * rtol
-    d0, d1 = _rms64(y0 / scale), _rms64(f0 / scale)
-    h0 = L.scldm_dopri5_initial_h0(d0, d1)
-    d2 = _rms64((f(np.float32(float(ts[0]) + h0), y0 + h0 * f0) - f0) / scale) / h0
-    dt = L.scldm_dopri5_initial_step(h0, d1, d2)
-    t1 = float(ts[0])
-    accepted, rejected = [], []
-    for next_t in ts[1:]:
-        while next_t > t1:
-            assert t1 + dt > t1
-            p = _plan(L, t1, dt)
-            k = np.empty((7, y0.size))
-            k[0] = f0
-            for i, beta in enumerate(_DP_BETA):
-                assert p.a_mask[i] == sum(1 << j for j, b in enumerate(beta) if b != 0.0)
-                yi = y0 + (beta * dt) @ k[:i + 1]
-                k[i + 1] = f(p.t_stage[i], yi)
-            ratio = _rms64(((dt * _DP_C_ERROR) @ k) / (atol + rtol * np.maximum(np.abs(y0), np.abs(yi))))
-            c = _control(L, t1, dt, ratio)
-            (accepted if c.accepted else rejected).append((t1, dt))
-            if c.accepted:
-                y0, f0 = yi, k[6]
-            assert not c.underflow
-            t1, dt = c.t1, c.h_next
-    return accepted, rejected, n_eval
+    rc, stats, rows, calls = _drive(D, problem, ts, **kw)
+    accepted, rejected = [r[:2] for r in rows if r[2] == 1.0], [r[:2] for r in rows if r[2] == 0.0]
+    assert len(accepted) + len(rejected) == len(rows)
+    return accepted, rejected, problem.n_eval, (rc, stats, rows, calls)
 
 
 def _forced(x, t):            # y' = -y + sin(8 t), every unknown with its own start value
@@ -162,19 +257,62 @@ def _rotation(x, t):          # (u, v)' = w (-v, u), a different angular velocit
 
 @pytest.mark.parametrize("system", [_forced, _rotation], ids=["forced_decay", "rotation"])
 @pytest.mark.parametrize("tol", [1e-5, 1e-7])
-def test_controller_reproduces_the_oracle_step_sequence(system, tol):
-    """64 unknowns, 50 save points: exactly the oracle's accepted and rejected (t0, dt) lists and its evaluation count."""
+def test_controller_reproduces_the_oracle_step_sequence(driver, system, tol):
+    """64 unknowns, 50 save points: exactly the oracle's accepted and rejected (t0, dt) lists and its evaluation count - the lists as the
+    shipped step loop logs them - and the loop's statistics agree with its log."""
     from oracle.transport import sample_ode_dopri5
-    from scldm_amd import _lib
-    L = _lib.lib()
     x0 = torch.randn(4, 16, generator=torch.Generator().manual_seed(11), dtype=torch.float64)
     _, st = sample_ode_dopri5(x0, system, 50, tol, tol, return_stats=True)
-    acc, rej, n_eval = _c_stepper(L, x0, system, 50, tol, tol)
+    acc, rej, n_eval, (rc, stats, rows, calls) = _c_stepper(driver, x0, system, 50, tol, tol)
     print(f"[dopri5 controller] {system.__name__} tol {tol:g}: {len(acc)} accepted, {len(rej)} rejected, {n_eval} evaluations")
     assert len(st["accepted"]) >= 3
     assert acc == [(float(a), float(b)) for a, b in st["accepted"]]
     assert rej == [(float(a), float(b)) for a, b in st["rejected"]]
     assert n_eval == st["evaluations"]
+    assert rc == 0 and stats.status == 0 and stats.evaluations == n_eval
+    assert (stats.accepted, stats.rejected, stats.step_log_len) == (len(acc), len(rej), len(rows))
+    assert stats.first_step == rows[0][1] and rows[0][0] == 0.0
+    assert [si for si, _ in calls["emit"]] == list(range(1, 50)) and calls["reached"] == 0
+
+
+class _Scripted:
+    """A problem without a state: attempt k reports the k-th scripted mean squared error ratio (the last one from then on)."""
+
+    def __init__(self, mean_squares):
+        self.script, self.attempts = list(mean_squares), 0
+        self.first_slope = self.start_norms = self.probe = self.accept = self.emit = self.reached = lambda *a: 0
+
+    def attempt(self, step, ms):
+        ms[0] = self.script[min(self.attempts, len(self.script) - 1)]
+        self.attempts += 1
+
+
+def test_loop_flags_a_step_that_cannot_advance_the_time(driver):
+    """The underflow exit of the shipped loop.  Time starts at 0, where every positive step advances it, so no given first step underflows
+    before the first attempt; the shortest way there is one accepted step to t = 0.5 and then rejections, each shrinking the step to a fifth,
+    until 0.5 + h == 0.5.  The loop must stop exactly there: SCLDM_ERR_SOLVER, status SCLDM_DOPRI5_UNDERFLOW, reached() once, no save point."""
+    h, attempts = 0.5 * 0.9, 1                # ratio 1 is accepted and the next step is 0.9 of it
+    while 0.5 + h > 0.5:
+        h, attempts = h * 0.2, attempts + 1   # ratio 1e150: min(10, max(0.9 / ratio^0.2, 0.2)) == 0.2
+    problem = _Scripted([1.0, 1e300])
+    rc, stats, rows, calls = _drive(driver, problem, [0.0, 1.0], first_step=0.5)
+    assert rc == -4 and stats.status == 1, (rc, stats.status)
+    assert b"dopri5: step size underflow / too many evaluations" in driver.dopri5_shim_message()
+    assert problem.attempts == attempts and stats.evaluations == 1 + 6 * attempts
+    assert (stats.accepted, stats.rejected, stats.first_step, stats.step_log_len) == (1, attempts - 1, 0.5, attempts)
+    assert rows[0] == (0.0, 0.5, 1.0) and all(r[0] == 0.5 and r[2] == 0.0 for r in rows[1:]) and 0.5 + rows[-1][1] * 0.2 == 0.5
+    assert calls["reached"] == 1 and calls["emit"] == []
+
+
+def test_step_log_cap_bounds_the_log_not_the_solve(driver):
+    """A step log of 2 rows on a solve with more attempts: exactly 2 rows are written (_drive checks the buffer behind them), with the
+    ratio in the fourth column of the 4-wide layout, and the solve still finishes."""
+    x0 = torch.randn(4, 16, generator=torch.Generator().manual_seed(11), dtype=torch.float64)
+    acc, rej, n_eval, (rc, stats, rows, calls) = _c_stepper(driver, x0, _forced, 3, 1e-5, 1e-5, cap=2, stride=4)
+    assert rc == 0 and stats.status == 0 and stats.step_log_len == 2 and len(rows) == 2
+    assert stats.accepted + stats.rejected > 2 and stats.evaluations == n_eval == 2 + 6 * (stats.accepted + stats.rejected)
+    assert all(r[3] > 0.0 and (r[3] <= 1.0) == (r[2] == 1.0) for r in rows)
+    assert [si for si, _ in calls["emit"]] == [1, 2]
 
 
 def test_control_rule_and_underflow_flag():
