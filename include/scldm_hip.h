@@ -614,6 +614,56 @@ int scldm_dit_train_step(scldm_dit* h, const scldm_dit_weights* w, const scldm_d
 int scldm_fm_loss(const float* pred, const float* ut, float* loss, int n, int e, void* stream);
 int scldm_fm_loss_bwd(const float* pred, const float* ut, const float* gloss, float* dpred, int n, int e, void* stream);
 
+/* The rest of the reference's transport family (src/scldm/transport/path.py:24-151,190-208; transport.py:69-202): the GVP path, noise
+ * and score prediction, the three loss weights.  With alpha, alpha', sigma, sigma' the path coefficients and their derivatives at t
+ * (Linear: t, 1, 1 - t, -1; GVP: sin(pi t/2), pi/2 cos(pi t/2), cos(pi t/2), -pi/2 sin(pi t/2)) and
+ * Dv = (alpha'/alpha) sigma^2 - sigma sigma':
+ *   plan       xt = alpha x1 + sigma x0,  ut = alpha' x1 + sigma' x0
+ *   loss row   w mean((c m - tgt)^2),  (c, tgt) = (1, ut) velocity | (1, x0) noise | (sigma, -x0) score,
+ *              w = 1 | (Dv/sigma)^2 | Dv/sigma^2 for the weights none | velocity | likelihood (a velocity model ignores the weight)
+ *   drift      f = a x + b m,  (a, b) = (0, 1) velocity | (alpha'/alpha, Dv) score | (alpha'/alpha, -Dv/sigma) noise
+ *   interval   a velocity model trains and integrates over [0, 1]; noise / score models over [eps, 1 - eps] (train_eps, sample_eps).
+ * The VP path is not provided.  Every entry below returns SCLDM_ERR_SHAPE for an unknown enum, VP, a negative eps or an eps >= 0.5. */
+enum { SCLDM_PATH_LINEAR = 0, SCLDM_PATH_GVP = 1 };
+enum { SCLDM_MODEL_VELOCITY = 0, SCLDM_MODEL_NOISE = 1, SCLDM_MODEL_SCORE = 2 };
+enum { SCLDM_WEIGHT_NONE = 0, SCLDM_WEIGHT_VELOCITY = 1, SCLDM_WEIGHT_LIKELIHOOD = 2 };
+typedef struct { int path, model, weight; float train_eps, sample_eps; } scldm_transport;
+typedef struct { double alpha, d_alpha, sigma, d_sigma, ratio /* alpha'/alpha */, dv, a, b, c, w; } scldm_transport_coef;
+/* The coefficients at one t, in double: no handle, no device.  A field the formula makes infinite at an end point (ratio at t = 0)
+ * is returned as it comes; a velocity model gets (a, b, c, w) = (0, 1, 1, 1) without reading one. */
+int scldm_transport_coef_at(const scldm_transport* tr, double t, scldm_transport_coef* out);
+/* scldm_sample_ode for a noise / score model: fixed-grid Euler / Heun of the probability-flow drift f = a(t) x + b(t) m over the fp32
+ * linspace(sample_eps, 1 - sample_eps, n_steps + 1), m the CFG-blended model output; arguments, workspace and precision as
+ * scldm_sample_ode.  Per evaluation one elementwise kernel after the trunk blends, forms f and (Euler) steps the state; (a, b) are
+ * evaluated in double at the fp32 grid time and rounded once.  A velocity model (either path) is handed to scldm_sample_ode.
+ * SCLDM_ERR_SHAPE also for a noise / score transport with sample_eps == 0 (the drift is singular at the end points). */
+int scldm_sample_ode_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                               const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method, const scldm_transport* tr,
+                               int precision, void* ws, void* stream);
+/* Training around the model call, unfused (the generalisation of scldm_fm_mix / scldm_fm_loss / scldm_fm_loss_bwd):
+ *   scldm_fm_plan:      one launch writes xt, the loss target tgt (ut | x0 | -x0) and rowc[b] = {c, w} (n, 2); each product is rounded
+ *                       on its own, then the sum, like the eager form.  x1, x0, xt, tgt are (n, e) fp32, t is (n).
+ *   scldm_fm_wloss:     loss[b] = w mean_e (c m - tgt)^2, summed in scldm_fm_loss's order
+ *   scldm_fm_wloss_bwd: dm[b][:] = gloss[b] w (2/e) c (c m - tgt) */
+int scldm_fm_plan(const scldm_transport* tr, const float* x1, const float* x0, const float* t, float* xt, float* tgt, float* rowc, int n,
+                  int e, void* stream);
+int scldm_fm_wloss(const float* m, const float* tgt, const float* rowc, float* loss, int n, int e, void* stream);
+int scldm_fm_wloss_bwd(const float* m, const float* tgt, const float* rowc, const float* gloss, float* dm, int n, int e, void* stream);
+/* The same with nothing left to the host (see scldm_fm_prepare / scldm_fm_loss_grad): the same Philox calls and counters, the row's
+ * uniform u mapped to t = u (t1 - t0) + t0 (t1 = 1 - train_eps, t0 = train_eps, the span and t0 rounded to fp32 on the host, product
+ * and sum rounded separately); tgt goes where scldm_fm_prepare writes ut, rowc is (n, 2). */
+int scldm_fm_prepare_transport(const scldm_transport* tr, const float* x1, const int64_t* const* labels_in, const int* null_tokens,
+                               int n_classes, int strategy, int drop, float p_drop, const unsigned long long* rng_state, int n, int e,
+                               float* t, float* x0, float* xt, float* tgt, float* rowc, int64_t* labels_out, void* stream);
+int scldm_fm_wloss_grad(const float* m, const float* tgt, const float* rowc, int n, int e, float* loss_rows, float* loss_mean, float* dm,
+                        unsigned int* ticket, unsigned long long* rng_state, void* stream);
+/* scldm_dit_train_step under a transport: the two entries above around the same forward / backward / AdamW calls; buffers->ut holds
+ * tgt.  Launches and event records only, capturable like scldm_dit_train_step. */
+int scldm_dit_train_step_transport(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* grads, const float* x1,
+                                   const int64_t* const* labels_in, const int* null_tokens, int n_classes, int strategy, float p_drop,
+                                   unsigned long long* rng_state, int n, int precision, const scldm_train_step_buffers* buffers,
+                                   const scldm_transport* tr, float* rowc, const scldm_adamw_launch* opt /* may be NULL */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * TransformerVAE encode / decode (MCAB pooling / unpooling + negative-binomial head), fp32.
  * Shape family of the reference (experiments/configs/model/vae_base.yaml:8-19,64-73): n_embed 32, 16 inducing

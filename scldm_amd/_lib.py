@@ -93,6 +93,16 @@ class Dopri5Control(C.Structure):
     _fields_ = [("accepted", C.c_int), ("underflow", C.c_int), ("t1", C.c_double), ("h_next", C.c_double)]
 
 
+class TransportC(C.Structure):
+    """scldm_transport (include/scldm_hip.h): path 0 Linear | 1 GVP, model 0 velocity | 1 noise | 2 score, weight 0 none | 1 velocity | 2 likelihood."""
+    _fields_ = [("path", C.c_int), ("model", C.c_int), ("weight", C.c_int), ("train_eps", C.c_float), ("sample_eps", C.c_float)]
+
+
+class TransportCoef(C.Structure):
+    """scldm_transport_coef (include/scldm_hip.h)."""
+    _fields_ = [(n, C.c_double) for n in ("alpha", "d_alpha", "sigma", "d_sigma", "ratio", "dv", "a", "b", "c", "w")]
+
+
 ERR_SOLVER = -4   # SCLDM_ERR_SOLVER
 
 
@@ -226,6 +236,17 @@ def lib() -> C.CDLL:
     L.scldm_fm_mix.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_loss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.scldm_transport_coef_at.argtypes = [C.POINTER(TransportC), C.c_double, C.POINTER(TransportCoef)]
+    a = L.scldm_sample_ode.argtypes
+    L.scldm_sample_ode_transport.argtypes = a[:11] + [C.POINTER(TransportC)] + a[11:]
+    L.scldm_fm_plan.argtypes = [C.POINTER(TransportC)] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    L.scldm_fm_wloss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.scldm_fm_wloss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.scldm_fm_prepare_transport.argtypes = [C.POINTER(TransportC)] + L.scldm_fm_prepare.argtypes[:14] + [C.c_void_p] + L.scldm_fm_prepare.argtypes[14:]
+    L.scldm_fm_wloss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+    a = L.scldm_dit_train_step.argtypes
+    L.scldm_dit_train_step_transport.argtypes = a[:13] + [C.POINTER(TransportC), C.c_void_p] + a[13:]
     L.scldm_vae_create.argtypes = [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]
     L.scldm_vae_destroy.argtypes = [C.c_void_p]
     L.scldm_vae_destroy.restype = None
@@ -312,7 +333,9 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_infer_sample_ode",
            "scldm_sample_ode_dopri5_workspace_bytes", "scldm_sample_ode_dopri5", "scldm_sample_ode_dopri5_at", "scldm_dopri5_stage_plan", "scldm_dopri5_control",
            "scldm_dopri5_initial_h0", "scldm_dopri5_initial_step",
-           "scldm_logp_ode_dopri5_workspace_bytes", "scldm_logp_ode_dopri5"]
+           "scldm_logp_ode_dopri5_workspace_bytes", "scldm_logp_ode_dopri5",
+           "scldm_transport_coef_at", "scldm_sample_ode_transport", "scldm_fm_plan", "scldm_fm_wloss", "scldm_fm_wloss_bwd", "scldm_fm_prepare_transport", "scldm_fm_wloss_grad",
+           "scldm_dit_train_step_transport"]
 
 
 def check(rc: int, what: str) -> None:

@@ -15,6 +15,7 @@
 #include "dit_handle.hpp"
 #include "ode_rk.hpp"
 #include "sde.hpp"
+#include "transport_path.hpp"
 #include "dopri5_ctl.hpp"
 #include "dopri5_fused.hpp"
 
@@ -1289,6 +1290,147 @@ extern "C" int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ul
     } else if (last_step == SCLDM_SDE_LAST_TWEEDIE) a_v = (float)(1.0 - (double)t1);   // x / t1 + (1 - t1)^2 / t1 score = x + (1 - t1) v
     if ((rc = eval(z, z, a_x, a_v, 0.f, n_steps, tr))) return rc;
   } else if (tr) HIP_TRY(hipMemcpyAsync(tr, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // the reference appends the unchanged state
+  return SCLDM_OK;
+}
+
+// ---- ODE sampling under a noise / score transport (transport_path.hpp) ------------------------------------------------------------------
+// The probability-flow drift of such a model is f = a(t) x + b(t) m with m the CFG-blended model output (transport.py:152-183), over
+// linspace(sample_eps, 1 - sample_eps, n_steps + 1).  The conditioning, the trunk and the Heun kernels are scldm_sample_ode's; the
+// evaluation times go through the explicit list of the SDE entry; ONE elementwise kernel after the trunk blends, maps and (Euler) steps.
+namespace {
+struct DriftArgs {
+  const float* v;       // trunk output: 2B unconditional rows, then P conditional passes of B rows (direct: 2B rows, the result itself)
+  const float* x;       // (2B, e) the state the evaluation was made at
+  float* f;             // (2B, e) receives f = a x + b m, or NULL
+  float* z;             // Euler: the state, z += h f; or NULL
+  int B, e, P, direct;
+  float scale[kMaxClasses];
+  float a, b, h;        // rounded to fp32 once on the host
+};
+// thread = 4 consecutive elements (16 bytes), no LDS
+__global__ __launch_bounds__(256) void cfg_blend_drift_kernel(const DriftArgs a) {
+#pragma clang fp contract(off)   // every product and sum rounded on its own (the blend keeps cfg_blend_kernel's contracted statement)
+  const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t half = (size_t)a.B * a.e, half4 = half >> 2;
+  if (q >= 2 * half4) return;
+  const size_t i = q * 4;
+  f32x4 r = reinterpret_cast<const f32x4*>(a.v)[q];
+  if (!a.direct && q >= half4) {
+    const float* vc = a.v + 2 * half + (i - half);   // pass 0 of these elements; pass p is p * half further
+    const f32x4 u = r;
+    for (int p = 0; p < a.P; ++p) r = sde::cfg_blend_pass(r, *reinterpret_cast<const f32x4*>(vc + (size_t)p * half), u, a.scale[p]);
+  }
+  const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[q];
+  const f32x4 f = x * a.a + r * a.b;
+  if (a.f) reinterpret_cast<f32x4*>(a.f)[q] = f;
+  if (a.z) {
+    f32x4* zp = reinterpret_cast<f32x4*>(a.z);
+    zp[q] = zp[q] + f * a.h;
+  }
+}
+// torch.linspace(t0, t1, steps) in fp32: linspace0's symmetric fill between any two end points
+float linspace_ab(int idx, int steps, float t0, float t1) {
+  const float step = (t1 - t0) / (float)(steps - 1);
+  return (idx < steps / 2) ? t0 + step * (float)idx : t1 - step * (float)(steps - idx - 1);
+}
+}  // namespace
+
+extern "C" int scldm_sample_ode_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B,
+                                          int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method,
+                                          const scldm_transport* tr, int precision, void* ws_, void* stream_) {
+  if (!tpath::transport_valid(tr))
+    return fail(SCLDM_ERR_SHAPE, "scldm_sample_ode_transport: bad transport (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5)");
+  if (tr->model == SCLDM_MODEL_VELOCITY)   // a velocity model's drift is the model output over [0, 1] on either path: the existing solve
+    return scldm_sample_ode(h, z, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, n_steps, method, precision, ws_, stream_);
+  int rc = check_ready(h, precision);
+  if (rc) return rc;
+  if (!z || !ws_) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
+  if ((uintptr_t)z & 15) return fail(SCLDM_ERR_SHAPE, "z must be 16-byte aligned");
+  if (n_steps < 1) return fail(SCLDM_ERR_SHAPE, "n_steps must be >= 1");
+  if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
+  if (!(tr->sample_eps > 0.f))
+    return fail(SCLDM_ERR_SHAPE, "a noise / score model needs sample_eps > 0: its drift is singular at t = 0 (alpha'/alpha) and at t = 1 (noise: 1 / sigma)");
+  CfgPlan pl;
+  if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
+  hipStream_t st = (hipStream_t)stream_;
+  Ws w = carve(h, ws_, pl.n_fwd, pl.n_rows, 2 * B);
+  const int e_row = 16 * h->cfg.n_embed_input;
+  const size_t n = (size_t)2 * B * e_row;
+  if (e_row % 4 || n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state rows must be a multiple of 4 elements, at most 2^33 elements in all");
+  const bool heun = method == SCLDM_METHOD_HEUN;
+  const int steps = n_steps + 1, n_evals = (heun ? 2 : 1) * n_steps;
+  double td0, td1;
+  tpath::transport_interval(tr, true, &td0, &td1);
+  const float ta = (float)td0, tb = (float)td1;
+  std::vector<float> tl;
+  tl.reserve(n_evals);
+  for (int i = 0; i < n_steps; ++i) {
+    tl.push_back(linspace_ab(i, steps, ta, tb));
+    if (heun) tl.push_back(linspace_ab(i + 1, steps, ta, tb));
+  }
+  fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, cell_row, 2 * B, 1, B, pl.U, pl.P, nullptr, pl.direct);
+  LAUNCH_CHECK();
+  float* tscal = w.silu + (size_t)pl.n_rows * 256;   // device scalar t (solves beyond kMaxTembEvals): the spare row after the silu rows
+  const bool pre = n_evals <= kMaxTembEvals;
+  float* mod_all = nullptr;
+  if (pre) {
+    float* tlist = w.h;   // (read by the embedding launch before the first trunk launch overwrites it: stream order, as scldm_sample_sde)
+    for (int c0 = 0; c0 < n_evals; c0 += sde::kTChunk) {
+      sde::TChunk ch{};
+      const int m = std::min(sde::kTChunk, n_evals - c0);
+      for (int j = 0; j < m; ++j) ch.t[j] = tl[c0 + j];
+      sde::set_tlist_kernel<<<1, sde::kTChunk, 0, st>>>(tlist + c0, ch, m);
+    }
+    sde::t_embed_list_kernel<<<n_evals, 256, 0, st>>>(tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
+    LAUNCH_CHECK();
+    if (h->cond_all_on && n_evals > 1)
+      if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
+  }
+  DriftArgs da{};
+  da.v = w.v;
+  da.B = B;
+  da.e = e_row;
+  da.P = pl.P;
+  da.direct = pl.direct ? 1 : 0;
+  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) da.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
+  int e_idx = 0;
+  // one evaluation at zin: f_out = a zin + b m (when given), euler_z += hs f (when given)
+  auto eval = [&](const float* zin, float* f_out, float* euler_z, float hs) -> int {
+    const int e = e_idx++;
+    Ws we = w;
+    if (mod_all) we.mod = mod_all + (size_t)e * pl.n_rows * h->mod_w;
+    else {
+      if (!pre) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tl[e]);
+      int rc2 = cfg_cond(h, pl, tscal, 0, w, precision, st, pre ? w.temb + (size_t)e * 256 : nullptr);
+      if (rc2) return rc2;
+    }
+    int rc2 = trunk(h, zin, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, we.mod, w.ridx, w.h, w.v, precision, st);
+    if (rc2) return rc2;
+    scldm_transport_coef k;
+    tpath::transport_coef(tr->path, tr->model, tr->weight, (double)tl[e], &k);
+    da.x = zin;
+    da.f = f_out;
+    da.z = euler_z;
+    da.a = (float)k.a;
+    da.b = (float)k.b;
+    da.h = hs;
+    cfg_blend_drift_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(da);
+    LAUNCH_CHECK();
+    return SCLDM_OK;
+  };
+  for (int i = 0; i < n_steps; ++i) {
+    const float t0 = linspace_ab(i, steps, ta, tb), t1 = linspace_ab(i + 1, steps, ta, tb);
+    const float hs = t1 - t0;
+    if (!heun) {
+      if ((rc = eval(z, nullptr, z, hs))) return rc;
+    } else {
+      if ((rc = eval(z, w.dz, nullptr, 0.f))) return rc;
+      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.ztmp, hs, n);
+      if ((rc = eval(w.ztmp, w.k2, nullptr, 0.f))) return rc;
+      heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.k2, 0.5f * hs, n);
+    }
+    LAUNCH_CHECK();
+  }
   return SCLDM_OK;
 }
 

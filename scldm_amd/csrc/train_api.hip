@@ -13,6 +13,7 @@
 #include "attn_mfma.hpp"
 #include "train_fused.hpp"
 #include "infer_wide.hpp"
+#include "transport_path.hpp"
 
 using namespace scldm;
 using namespace scldm::train;
@@ -1339,6 +1340,90 @@ extern "C" int scldm_fm_loss_bwd(const float* pred, const float* ut, const float
   if (!pred || !ut || !gloss || !dpred || n < 1 || e < 1) return fail(SCLDM_ERR_SHAPE, "scldm_fm_loss_bwd: bad argument");
   const long total = (long)n * e;
   hipLaunchKernelGGL(fm_loss_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream_, pred, ut, gloss, dpred, total, e);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same three pieces under any transport (transport_path.hpp): plan, weighted row loss, its gradient.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+using namespace scldm::tpath;
+constexpr int kPlanChunk = 1024;   // elements of one row per workgroup
+// workgroup = one chunk of one row: thread 0 evaluates the row's coefficients (double) once, every thread then takes elements
+// tid, tid + 256, ... of the chunk
+__global__ __launch_bounds__(256) void fm_plan_kernel(int path, int model, int weight, const float* __restrict__ x1, const float* __restrict__ x0,
+                                                      const float* __restrict__ t, float* __restrict__ xt, float* __restrict__ tgt,
+                                                      float* __restrict__ rowc, int e, int chunks) {
+  __shared__ RowCoef sk;
+  const long row = blockIdx.x / chunks;
+  const int chunk = blockIdx.x % chunks;
+  if (threadIdx.x == 0) {
+    sk = row_coef(path, model, weight, t[row]);
+    if (chunk == 0) { rowc[2 * row] = sk.c; rowc[2 * row + 1] = sk.w; }
+  }
+  __syncthreads();
+  const RowCoef k = sk;
+  const int end = min(e, (chunk + 1) * kPlanChunk);
+  for (int i = chunk * kPlanChunk + threadIdx.x; i < end; i += 256) {
+    const float a = x1[row * e + i], b = x0[row * e + i];
+    xt[row * e + i] = plan_xt(k, a, b);
+    tgt[row * e + i] = plan_tgt(k, model, a, b);
+  }
+}
+// fm_loss_kernel with the row's {c, w}: the same thread-to-element map and the same tree
+__global__ __launch_bounds__(256) void fm_wloss_kernel(const float* __restrict__ m, const float* __restrict__ tgt, const float* __restrict__ rowc,
+                                                       float* __restrict__ loss, int e) {
+  __shared__ float red[4];
+  const long b = blockIdx.x;
+  const float c = rowc[2 * b], w = rowc[2 * b + 1];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < e; i += 256) {
+    const float d = wl_diff(c, m[b * e + i], tgt[b * e + i]);
+    s = fmaf(d, d, s);
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[b] = wl_row(w, (red[0] + red[1]) + (red[2] + red[3]), e);
+}
+__global__ void fm_wloss_bwd_kernel(const float* __restrict__ m, const float* __restrict__ tgt, const float* __restrict__ rowc,
+                                    const float* __restrict__ gloss, float* __restrict__ dm, long total, int e) {
+  const float k = 2.0f / (float)e;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / e;
+    const float c = rowc[2 * b];
+    dm[i] = wl_grad(gloss[b], rowc[2 * b + 1], k, c, wl_diff(c, m[i], tgt[i]));
+  }
+}
+}  // namespace
+
+extern "C" int scldm_transport_coef_at(const scldm_transport* tr, double t, scldm_transport_coef* out) {
+  if (!out || !transport_valid(tr)) return fail(SCLDM_ERR_SHAPE, "scldm_transport_coef_at: bad argument (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5)");
+  transport_coef(tr->path, tr->model, tr->weight, t, out);
+  return SCLDM_OK;
+}
+extern "C" int scldm_fm_plan(const scldm_transport* tr, const float* x1, const float* x0, const float* t, float* xt, float* tgt, float* rowc,
+                             int n, int e, void* stream_) {
+  if (!transport_valid(tr)) return fail(SCLDM_ERR_SHAPE, "scldm_fm_plan: bad transport (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5)");
+  if (!x1 || !x0 || !t || !xt || !tgt || !rowc || n < 1 || e < 1) return fail(SCLDM_ERR_SHAPE, "scldm_fm_plan: bad argument");
+  const int chunks = (e + kPlanChunk - 1) / kPlanChunk;
+  if ((long)n * chunks > 0x7fffffffL) return fail(SCLDM_ERR_SHAPE, "scldm_fm_plan: n * ceil(e / %d) exceeds the grid", kPlanChunk);
+  hipLaunchKernelGGL(fm_plan_kernel, dim3((unsigned)((long)n * chunks)), dim3(256), 0, (hipStream_t)stream_, tr->path, tr->model, tr->weight, x1, x0, t,
+                     xt, tgt, rowc, e, chunks);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+extern "C" int scldm_fm_wloss(const float* m, const float* tgt, const float* rowc, float* loss, int n, int e, void* stream_) {
+  if (!m || !tgt || !rowc || !loss || n < 1 || e < 1) return fail(SCLDM_ERR_SHAPE, "scldm_fm_wloss: bad argument");
+  hipLaunchKernelGGL(fm_wloss_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream_, m, tgt, rowc, loss, e);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+extern "C" int scldm_fm_wloss_bwd(const float* m, const float* tgt, const float* rowc, const float* gloss, float* dm, int n, int e, void* stream_) {
+  if (!m || !tgt || !rowc || !gloss || !dm || n < 1 || e < 1) return fail(SCLDM_ERR_SHAPE, "scldm_fm_wloss_bwd: bad argument");
+  const long total = (long)n * e;
+  hipLaunchKernelGGL(fm_wloss_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream_, m, tgt, rowc, gloss, dm, total, e);
   LAUNCH_CHECK();
   return SCLDM_OK;
 }

@@ -15,42 +15,12 @@
 
 #include "api_common.hpp"
 #include "common.hpp"
+#include "fm_step_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace scldm {
 namespace fmstep {
-
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ float u01(uint32_t w) { return ((w >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0, 1), 24 bits
-__device__ __forceinline__ float u01_closed0(uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }   // [0, 1): torch.rand's range
-
-enum : uint32_t { TAG_X0 = 0x78300000u, TAG_ROW = 0x726f7700u, TAG_STEP = 0x73746570u };
-
-struct PrepArgs {
-  const float* x1;                  // (n, e)
-  const int64_t* labels_in[8];      // per class (sorted-name order): (n) labels, or nullptr = class absent from `condition`
-  int null_token[8];                // class vocabulary size = its null token
-  int n_classes, strategy;          // strategy 0 mutually_exclusive, 1 joint
-  int drop;                         // apply label dropout (training mode / force_drop_ids)
-  float p_drop;
-  const unsigned long long* rng;    // device: [0] seed, [1] step counter
-  float* t;                         // (n)
-  float* x0;                        // (n, e) or nullptr
-  float* xt; float* ut;             // (n, e)
-  int64_t* labels_out;              // (n_classes, n): what the model sees
-  int n, e;
-};
 
 // thread = 4 consecutive elements of (n, e); the first thread of a row also writes t and the row's labels
 __global__ __launch_bounds__(256) void fm_prepare_kernel(const PrepArgs a) {
@@ -104,7 +74,6 @@ __global__ __launch_bounds__(256) void fm_prepare_kernel(const PrepArgs a) {
 // mean() and fm_loss_bwd_kernel: gloss[b] = 1/n); the LAST workgroup to finish (ticket) sums the rows in a fixed order into loss_mean and
 // advances the Philox step counter - deterministic, one launch.  (One workgroup per row was 1 024 same-address ticket atomics at ~20 ns
 // each: 26 us for a 1 MB pass, profiles/r6d; eight rows per workgroup: n / 8 of them.)
-constexpr int kLossRows = 8;
 __global__ __launch_bounds__(256) void fm_loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ ut, float* __restrict__ loss_rows,
                                                            float* __restrict__ loss_mean, float* __restrict__ dpred, int n, int e,
                                                            unsigned int* __restrict__ ticket, unsigned long long* __restrict__ rng) {
@@ -209,6 +178,29 @@ extern "C" int scldm_dit_train_step(scldm_dit* h, const scldm_dit_weights* w, co
   rc = scldm_dit_train_forward(h, w, b->xt, b->t, lab, n, b->pred, precision, b->saved, b->ws, stream);
   if (rc) return rc;
   rc = scldm_fm_loss_grad(b->pred, b->ut, n, e, b->loss_rows, b->loss_mean, b->dpred, b->ticket, rng_state, stream);
+  if (rc) return rc;
+  rc = scldm_dit_train_backward(h, w, grads, b->xt, lab, b->dpred, n, nullptr, precision, b->saved, b->ws, stream);
+  if (rc) return rc;
+  if (opt) rc = scldm_adamw_table_step(opt, stream);
+  return rc;
+}
+
+extern "C" int scldm_dit_train_step_transport(scldm_dit* h, const scldm_dit_weights* w, const scldm_dit_grads* grads, const float* x1,
+                                              const int64_t* const* labels_in, const int* null_tokens, int n_classes, int strategy, float p_drop,
+                                              unsigned long long* rng_state, int n, int precision, const scldm_train_step_buffers* b,
+                                              const scldm_transport* tr, float* rowc, const scldm_adamw_launch* opt, void* stream) {
+  if (!h || !w || !grads || !x1 || !rowc || !b || !b->t || !b->xt || !b->ut || !b->pred || !b->dpred || !b->labels || !b->loss_rows || !b->loss_mean ||
+      !b->ticket || !b->saved || !b->ws)
+    return fail(SCLDM_ERR_SHAPE, "scldm_dit_train_step_transport: bad argument");
+  const int e = b->row_elems;
+  int rc = scldm_fm_prepare_transport(tr, x1, labels_in, null_tokens, n_classes, strategy, 1, p_drop, rng_state, n, e, b->t, b->x0, b->xt, b->ut, rowc,
+                                      b->labels, stream);
+  if (rc) return rc;
+  const int64_t* lab[8];
+  for (int c = 0; c < n_classes; ++c) lab[c] = b->labels + (size_t)c * n;
+  rc = scldm_dit_train_forward(h, w, b->xt, b->t, lab, n, b->pred, precision, b->saved, b->ws, stream);
+  if (rc) return rc;
+  rc = scldm_fm_wloss_grad(b->pred, b->ut, rowc, n, e, b->loss_rows, b->loss_mean, b->dpred, b->ticket, rng_state, stream);
   if (rc) return rc;
   rc = scldm_dit_train_backward(h, w, grads, b->xt, lab, b->dpred, n, nullptr, precision, b->saved, b->ws, stream);
   if (rc) return rc;

@@ -25,6 +25,12 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _default_transport_only(transport, what: str) -> None:
+    if transport is not None and not transport.is_default:
+        raise NotImplementedError(f"{what} serves the Linear path with a velocity model only (its drift, score and last steps are written for "
+                                  "that transport); a GVP path or a noise / score model samples through sample_ode_cfg(..., transport=)")
+
+
 def _require_cuda_f32(name: str, t: torch.Tensor) -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA (ROCm) tensor: scldm_amd runs only on the MI355X HIP path")
@@ -963,7 +969,7 @@ class DiT(nn.Module):
     @torch.no_grad()
     def sample_ode_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
                        num_steps: int, sampling_method: str = "euler", atol: float = 1e-5, rtol: float = 1e-5, *,
-                       first_step: float | None = None, return_trajectory: bool = False) -> torch.Tensor:
+                       first_step: float | None = None, return_trajectory: bool = False, transport=None) -> torch.Tensor:
         """Integrate dz/dt = forward_with_cfg(z, t) over linspace(0, 1, num_steps) entirely on device.
 
         `z` is the doubled state cat([z0, z0]) (2B,S,C); `condition` the doubled label dict; `num_steps` has the
@@ -977,7 +983,15 @@ class DiT(nn.Module):
         under graph capture); a module in training mode, a shape outside the fused family and SCLDM_DOPRI5_FUSED=0 (read when the native
         handle is created) run `Sampler._sample_dopri5` over `forward_with_cfg` - the same steps, the same bits.  Either way
         `last_solver_stats` then holds evaluations, rejected, accepted_steps / rejected_steps ((t0, dt) lists) and first_step.
+
+        `transport` (a `scldm_amd.transport.Transport`): what the model predicts.  None or a velocity transport (either path) is the
+        solve above.  A noise / score transport integrates its probability-flow drift a(t) z + b(t) forward_with_cfg(z, t) over
+        linspace(sample_eps, 1 - sample_eps, num_steps): "euler" / "heun" on a fused shape in eval mode as one C call
+        (scldm_sample_ode_transport); "dopri5", training mode and every other shape through the host-driven `Sampler(transport)`.
         """
+        if transport is not None and transport.model_type.name != "VELOCITY":
+            return self._sample_ode_transport(z, condition, cfg_scale, num_steps, sampling_method, atol, rtol, first_step, return_trajectory,
+                                              transport)
         if sampling_method.lower() == "dopri5":
             return self._sample_dopri5_cfg(z, condition, cfg_scale, num_steps, atol, rtol, first_step, return_trajectory)
         if num_steps < 2:
@@ -1036,6 +1050,45 @@ class DiT(nn.Module):
             _lib.check(L.scldm_sample_ode(h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row,
                                           B, n_pass, masks, scales, num_steps - 1, _lib.METHODS[sampling_method.lower()],
                                           self._prec(), ws, _stream_ptr()), "scldm_sample_ode")
+        del keep
+        return z
+
+    def _sample_ode_transport(self, z, condition, cfg_scale, num_steps, sampling_method, atol, rtol, first_step, return_trajectory, transport):
+        """sample_ode_cfg under a noise / score transport."""
+        method = sampling_method.lower()
+        if method not in ("euler", "heun", "dopri5"):
+            raise KeyError(method)
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (grid points)")
+        if method != "dopri5" and (first_step is not None or return_trajectory):
+            raise ValueError("first_step / return_trajectory belong to sampling_method='dopri5'")
+        if method == "dopri5" or self.training or not self.fused_shape:
+            # host-driven: one forward_with_cfg per evaluation.  (No one-call dopri5 exists for these models, and the wide one-call
+            # sampler serves velocity models only.)
+            from .transport import Sampler
+            fwd = self._generic_forward_with_cfg if not self.fused_shape else self.forward_with_cfg
+            z = _require_cuda_f32("z", z)
+            sampler = Sampler(transport)
+            if method == "dopri5":
+                fn = sampler._sample_dopri5(num_steps if return_trajectory else 2, atol, rtol, first_step)
+            else:
+                fn = sampler.sample_ode(sampling_method=method, num_steps=num_steps)
+            traj = fn(z, lambda x, t, **kw: fwd(x, t, kw["condition"], kw["cfg_scale"]), condition=condition, cfg_scale=cfg_scale)
+            return traj if return_trajectory else traj[-1]
+        self._need_null_row("CFG sampling (the unconditional pass)")
+        L, h = self._native()
+        z = _require_cuda_f32("z", z).clone()
+        n = z.shape[0]
+        B = n // 2
+        if n != 2 * B or z.shape[1:] != (self.seq_len, self.n_embed_input):
+            raise ValueError(f"expected z (2B,{self.seq_len},{self.n_embed_input}), got {tuple(z.shape)}")
+        ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
+        ws = self._workspace(L, 2 * B + n_pass * B, 1 + n_pass * n_u, 2 * B)
+        tr = transport.c_struct()
+        with torch.cuda.device(z.device):
+            _lib.check(L.scldm_sample_ode_transport(h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row,
+                                                    B, n_pass, masks, scales, num_steps - 1, _lib.METHODS[method], C.byref(tr),
+                                                    self._prec(), ws, _stream_ptr()), "scldm_sample_ode_transport")
         del keep
         return z
 
@@ -1126,7 +1179,7 @@ class DiT(nn.Module):
                        num_steps: int = 250, sampling_method: str = "euler", diffusion_form: str = "sigma", diffusion_norm: float = 1.0,
                        last_step: str | None = "Mean", last_step_size: float = 0.04, *, seed: int | None = None,
                        noise: torch.Tensor | None = None, cell_offset: int = 0, cells_total: int | None = None,
-                       return_trajectory: bool = False):
+                       return_trajectory: bool = False, transport=None):
         """The reference's `Sampler.sample_sde` over `forward_with_cfg`, entirely on device (scldm_sample_sde): Euler-Maruyama / stochastic
         Heun steps over linspace(0, 1 - last_step_size, num_steps) with diffusion D(t) of `diffusion_form`, then the noise-free
         `last_step` ("Mean", "Tweedie", "Euler" or None).  `z` is the doubled state cat([z0, z0]) (2B,S,C), `condition` the doubled
@@ -1138,6 +1191,7 @@ class DiT(nn.Module):
         only: with `cell_offset` / `cells_total` a shard of a larger solve draws exactly the noise the whole solve would have drawn for
         its cells.  Under graph capture the seed is baked into the captured launches, so a replay repeats its noise.
         `diffusion_form="SBDM"` and "heun" with `last_step=None` raise ValueError (NaN in the reference under this transport)."""
+        _default_transport_only(transport, "sample_sde_cfg")
         method = str(sampling_method).lower()
         if method not in _lib.METHODS:
             raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'euler' and 'heun' are")
@@ -1221,6 +1275,7 @@ class DiT(nn.Module):
         Probes: `probe` (n_evaluations, 2B, S, C) is used as given; otherwise a counter-based generator keyed by `seed` draws them on
         device (`seed=None`: one drawn from torch's host generator), a value depending on (seed, evaluation, half, global cell, column)
         only - with `cell_offset` / `cells_total` a shard of a larger solve draws what the whole solve would.
+        (The flow is the default transport's - Linear path, velocity model; `Sampler.sample_ode_likelihood` refuses any other.)
         Fused shape in eval mode: the whole solve is one C call (scldm_logp_ode: recording forward + input-gradient-only backward per
         evaluation, no host read).  Anything else: the generic `Sampler.sample_ode_likelihood` over differentiable `forward` calls with the
         same probes.

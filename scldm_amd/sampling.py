@@ -20,9 +20,11 @@ def shard_bounds(n: int, rank: int, world: int) -> tuple[int, int]:
 @torch.no_grad()
 def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | None, guidance_weight: dict[str, float] | None,
                    num_steps: int = 101, sampling_method: str = "euler", sde: dict | None = None, atol: float = 1e-5,
-                   rtol: float = 1e-5) -> torch.Tensor:
+                   rtol: float = 1e-5, transport=None) -> torch.Tensor:
     """z0 (B,S,C) noise -> final latents (2B,S,C): rows [0,B) unconditional, rows [B,2B) guided (models.py:801-812).
     `atol` / `rtol`: the tolerances of sampling_method="dopri5" (the reference's default sampler and its defaults; a fixed grid ignores them).
+    `transport`: what the model predicts (`DiT.sample_ode_cfg`); None or a velocity transport is the plain solve, the SDE sampler takes
+    the default transport only.
 
     `sde`: None integrates the ODE (`DiT.sample_ode_cfg`); a dict selects the stochastic sampler instead and holds the keyword arguments
     of `DiT.sample_sde_cfg` beyond the grid and the method (diffusion_form, diffusion_norm, last_step, last_step_size, seed, noise, and
@@ -39,7 +41,11 @@ def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | N
     z2 = torch.cat([z0, z0], dim=0)
     cond2 = None if condition is None else {k: torch.cat([v, v], dim=0) for k, v in condition.items()}
     if sde is not None:
+        if transport is not None and not transport.is_default:
+            raise NotImplementedError("the SDE sampler serves the Linear path with a velocity model only")
         return dit.sample_sde_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, **sde)
+    if transport is not None and transport.model_type.name != "VELOCITY":
+        return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, atol=atol, rtol=rtol, transport=transport)
     if str(sampling_method).lower() == "dopri5":
         return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, atol=atol, rtol=rtol)
     return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method)

@@ -348,8 +348,10 @@ class FusedTrainStep:
     replayed - per replay the host stages 16 bytes (learning rate, weight decay, EMA action) and copies the batch.  Gradients live in
     one flat fp32 buffer (`.grad` of every parameter is a view), so a data-parallel group reduces it in place between backward and
     optimizer (`group=`; that variant is not graphed).  `grad_clip_norm=` = the trainer's `gradient_clip_val` (global-norm clipping inside
-    the optimizer's launch; `optimizer.last_grad_norm` is the step's norm).  Requires the fused training route (base DiT shape, precision bf16 | fp16), the
-    Linear path with velocity prediction (ldm_base.yaml:30-35) and `scldm_amd.optim.AdamW`.
+    the optimizer's launch; `optimizer.last_grad_norm` is the step's norm).  Requires the fused training route (base DiT shape, precision bf16 | fp16)
+    and `scldm_amd.optim.AdamW`.  `transport`: the Linear path with velocity prediction (ldm_base.yaml:30-35) runs `scldm_dit_train_step`; the
+    GVP path, noise / score prediction and the loss weights run `scldm_dit_train_step_transport` (same forward / backward / optimizer calls,
+    the batch preparation and the loss kernel take the path), graphed alike.
     `__call__(x1, condition)` or `__call__(condition=..., counts=, genes=, counts_subset=, genes_subset=)` with a frozen `vae`; returns the
     step's loss as a STATIC device scalar (overwritten by the next step: `.clone()` or `float()` it to keep a value)."""
 
@@ -371,6 +373,8 @@ class FusedTrainStep:
         if dev.type != "cuda":
             raise RuntimeError("FusedTrainStep needs the model on a CUDA (ROCm) device; there is no CPU path")
         self.dit, self.transport, self.optimizer, self.ema, self.vae = dit, transport, optimizer, ema, vae
+        # the default transport (Linear path, velocity model) keeps scldm_dit_train_step; any other runs scldm_dit_train_step_transport
+        self._tr = None if getattr(transport, "is_default", True) else transport.c_struct()
         self.n, self.group, self.dev = int(batch_size), group, dev
         self.keys = [c for c in dit._class_names if c in set(condition_keys)]
         if not self.keys:
@@ -394,6 +398,7 @@ class FusedTrainStep:
         self.xt, self.ut, self.pred, self.dpred = (torch.empty(n, e, **f32) for _ in range(4))
         self.labels = torch.empty(len(dit._class_names), n, dtype=torch.long, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rowc = torch.empty(n, 2, **f32) if self._tr is not None else None     # per row {c, w} of the weighted loss
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
         self.rng = torch.tensor([seed, 0], dtype=torch.int64, device=dev)         # [0] Philox key, [1] step counter (advanced on the device)
@@ -510,6 +515,13 @@ class FusedTrainStep:
                 finally:
                     self.vae.check_weight_fingerprint = keep
                 self.x1.copy_(z.view_as(self.x1))
+            if self._tr is not None:
+                _lib.check(self._L.scldm_dit_train_step_transport(
+                    self._h, C.byref(self._w), C.byref(self._g), self.x1.data_ptr(), C.cast(self._lab_ptrs, _lib.c_void_pp), self._nulls,
+                    len(dit._class_names), 1 if dit.condition_strategy == "joint" else 0, float(dit.cfg_dropout_prob), self.rng.data_ptr(), self.n,
+                    self.prec, C.byref(self._buf), C.byref(self._tr), self.rowc.data_ptr(), C.byref(self._opt) if self._opt is not None else None, st),
+                    "scldm_dit_train_step_transport")
+                return
             _lib.check(self._L.scldm_dit_train_step(self._h, C.byref(self._w), C.byref(self._g), self.x1.data_ptr(), C.cast(self._lab_ptrs, _lib.c_void_pp),
                                                     self._nulls, len(dit._class_names), 1 if dit.condition_strategy == "joint" else 0,
                                                     float(dit.cfg_dropout_prob), self.rng.data_ptr(), self.n, self.prec, C.byref(self._buf),
@@ -519,6 +531,8 @@ class FusedTrainStep:
         """Device time of each stage of ONE (real, eager) step, in ms: the sub-entry points scldm_dit_train_step itself calls, issued one by
         one with HIP events between them on the current stream (bench.py's `train_e2e` record)."""
         from . import _lib
+        if self._tr is not None:
+            raise NotImplementedError("profile_stages times the default transport's stages (Linear path, velocity model)")
         dit, L, h = self.dit, self._L, self._h
         names = dit._class_names
         lab = _lib.ptr_array([self.labels.data_ptr() + 8 * self.n * i for i in range(len(names))])

@@ -1,9 +1,10 @@
-"""Flow-matching transport with the reference's API (src/scldm/transport/), Linear path + velocity model.
+"""Flow-matching transport with the reference's API (src/scldm/transport/): the Linear and GVP paths, velocity / noise / score models.
 
 `create_transport(...)`, `Transport.training_losses`, `Sampler(transport).sample_ode(...)` / `.sample_sde(...)` keep the
 reference signatures (transport/__init__.py:6-12, transport.py:110,269-332).  Differences, by design:
-  * only (path_type="Linear", prediction="velocity") exists - the one combination every reference config
-    uses (ldm_base.yaml:30-35); anything else raises NotImplementedError;
+  * path_type "Linear" | "GVP" x prediction "velocity" | "noise" | "score" x loss_weight None | "velocity" | "likelihood" exist;
+    (Linear, velocity) is the combination every reference config uses (ldm_base.yaml:30-35) and keeps its own kernels.  The VP
+    path raises NotImplementedError.  `sample_sde` and `sample_ode_likelihood` serve the default (Linear, velocity) transport only;
   * the reference hands stepping to third-party torchdiffeq (integrators.py:111, default dopri5); here the
     fixed-grid "euler" / "heun" schemes are built in (definition + KAT: oracle/transport.py), and when the
     model is a scldm_amd DiT bound through `forward_with_cfg` the whole loop runs inside one C call
@@ -73,6 +74,34 @@ class _FlowMatchLoss(torch.autograd.Function):
         return dpred, None
 
 
+class _WeightedFlowMatchLoss(torch.autograd.Function):
+    """loss_b = w_b mean((c_b m - tgt)^2) with its gradient w.r.t. m (scldm_fm_wloss / scldm_fm_wloss_bwd); rowc (n, 2) holds {c, w}."""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, rowc):
+        from .. import _lib
+        pred = pred.contiguous()
+        n, e = pred.shape[0], pred[0].numel()
+        loss = torch.empty(n, dtype=torch.float32, device=pred.device)
+        with torch.cuda.device(pred.device):
+            _lib.check(_lib.lib().scldm_fm_wloss(pred.data_ptr(), tgt.data_ptr(), rowc.data_ptr(), loss.data_ptr(), n, e, _stream()), "scldm_fm_wloss")
+        ctx.save_for_backward(pred, tgt, rowc)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        from .. import _lib
+        pred, tgt, rowc = ctx.saved_tensors
+        n, e = pred.shape[0], pred[0].numel()
+        gloss = gloss.contiguous().float()
+        dpred = torch.empty_like(pred)
+        with torch.cuda.device(pred.device):
+            _lib.check(_lib.lib().scldm_fm_wloss_bwd(pred.data_ptr(), tgt.data_ptr(), rowc.data_ptr(), gloss.data_ptr(), dpred.data_ptr(), n, e,
+                                                     _stream()), "scldm_fm_wloss_bwd")
+        return dpred, None, None
+
+
 SDE_DIFFUSION_FORMS = ("sigma", "linear", "constant", "decreasing", "inccreasing-decreasing")   # (the reference's spelling, path.py:69)
 SDE_LAST_STEPS = (None, "Mean", "Tweedie", "Euler")
 
@@ -100,14 +129,108 @@ class LinearPath:
         sigma = 1 - te
         return (te * velocity - x) / (sigma ** 2 + te * sigma)
 
+    # the reference's member names (path.py:24-151: ICPlan), same expressions in the same order
+    def compute_alpha_t(self, t):
+        return t, 1
+
+    def compute_sigma_t(self, t):
+        return 1 - t, -1
+
+    def compute_d_alpha_alpha_ratio_t(self, t):
+        return 1 / t
+
+    def compute_drift(self, x, t):
+        """(-alpha'/alpha x, Dv = alpha'/alpha sigma^2 - sigma sigma')  (path.py:42-50)."""
+        t = _expand_like(t, x)
+        alpha_ratio = self.compute_d_alpha_alpha_ratio_t(t)
+        sigma_t, d_sigma_t = self.compute_sigma_t(t)
+        return -(alpha_ratio * x), alpha_ratio * (sigma_t ** 2) - sigma_t * d_sigma_t
+
+    def get_noise_from_velocity(self, velocity, x, t):
+        t = _expand_like(t, x)
+        alpha_t, d_alpha_t = self.compute_alpha_t(t)
+        sigma_t, d_sigma_t = self.compute_sigma_t(t)
+        reverse_alpha_ratio = alpha_t / d_alpha_t
+        return (reverse_alpha_ratio * velocity - x) / (reverse_alpha_ratio * d_sigma_t - sigma_t)
+
+    def get_velocity_from_score(self, score, x, t):
+        drift, var = self.compute_drift(x, t)
+        return var * score - drift
+
+    def compute_mu_t(self, t, x0, x1):
+        t = _expand_like(t, x1)
+        return self.compute_alpha_t(t)[0] * x1 + self.compute_sigma_t(t)[0] * x0
+
+    def compute_xt(self, t, x0, x1):
+        return self.compute_mu_t(t, x0, x1)
+
+    def compute_ut(self, t, x0, x1, xt):
+        t = _expand_like(t, x1)
+        return self.compute_alpha_t(t)[1] * x1 + self.compute_sigma_t(t)[1] * x0
+
+    def plan(self, t, x0, x1):
+        xt = self.compute_xt(t, x0, x1)
+        return t, xt, self.compute_ut(t, x0, x1, xt)
+
+
+class GVPPath(LinearPath):
+    """The GVP path x_t = sin(pi t / 2) x1 + cos(pi t / 2) x0 (path.py:190-208: GVPCPlan)."""
+
+    def compute_alpha_t(self, t):
+        import math
+        return torch.sin(t * math.pi / 2), math.pi / 2 * torch.cos(t * math.pi / 2)
+
+    def compute_sigma_t(self, t):
+        import math
+        return torch.cos(t * math.pi / 2), -math.pi / 2 * torch.sin(t * math.pi / 2)
+
+    def compute_d_alpha_alpha_ratio_t(self, t):
+        import math
+        return math.pi / (2 * torch.tan(t * math.pi / 2))
+
+    def compute_diffusion(self, x, t, form="constant", norm=1.0):
+        if form == "sigma":
+            return norm * self.compute_sigma_t(_expand_like(t, x))[0]
+        return super().compute_diffusion(x, t, form=form, norm=norm)
+
+    def get_score_from_velocity(self, velocity, x, t):
+        """(alpha/alpha' v - x) / (sigma^2 - alpha/alpha' sigma' sigma)  (path.py:79-95)."""
+        t = _expand_like(t, x)
+        alpha_t, d_alpha_t = self.compute_alpha_t(t)
+        sigma_t, d_sigma_t = self.compute_sigma_t(t)
+        reverse_alpha_ratio = alpha_t / d_alpha_t
+        return (reverse_alpha_ratio * velocity - x) / (sigma_t ** 2 - reverse_alpha_ratio * d_sigma_t * sigma_t)
+
+
+_C_PATH = {PathType.LINEAR: 0, PathType.GVP: 1}                                      # SCLDM_PATH_*
+_C_MODEL = {ModelType.VELOCITY: 0, ModelType.NOISE: 1, ModelType.SCORE: 2}           # SCLDM_MODEL_*
+_C_WEIGHT = {WeightType.NONE: 0, WeightType.VELOCITY: 1, WeightType.LIKELIHOOD: 2}   # SCLDM_WEIGHT_*
+
 
 class Transport:
     def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps):
-        if path_type is not PathType.LINEAR or model_type is not ModelType.VELOCITY:
-            raise NotImplementedError("only the Linear path with a velocity model is on the hot path (ldm_base.yaml:30-35)")
+        if path_type not in _C_PATH:
+            raise NotImplementedError("the VP path is not provided: path_type 'Linear' and 'GVP' are (its fp32 arithmetic forms 1 - exp(...) "
+                                      "next to t = 1 and needs a design of its own)")
+        if model_type not in _C_MODEL or loss_type not in _C_WEIGHT:
+            raise NotImplementedError(f"model_type={model_type!r}, loss_type={loss_type!r}")
+        for name, eps in (("train_eps", train_eps), ("sample_eps", sample_eps)):
+            if not 0 <= eps < 0.5:
+                raise ValueError(f"{name} must lie in [0, 0.5), got {eps}")
         self.model_type, self.path_type, self.loss_type = model_type, path_type, loss_type
         self.train_eps, self.sample_eps = train_eps, sample_eps
-        self.path_sampler = LinearPath()
+        self.path_sampler = LinearPath() if path_type is PathType.LINEAR else GVPPath()
+
+    @property
+    def is_default(self) -> bool:
+        """The Linear path with a velocity model: the combination with its own kernels and one-call samplers."""
+        return self.path_type is PathType.LINEAR and self.model_type is ModelType.VELOCITY
+
+    def c_struct(self):
+        """The scldm_transport of the C ABI (include/scldm_hip.h)."""
+        from .. import _lib
+        return _lib.TransportC(path=_C_PATH[self.path_type], model=_C_MODEL[self.model_type], weight=_C_WEIGHT[self.loss_type],
+                               train_eps=float(self.train_eps), sample_eps=float(self.sample_eps))
 
     def prior_logp(self, z: torch.Tensor) -> torch.Tensor:
         """Standard multivariate normal log-density of every row of a batched z: -N/2 log 2 pi - sum z^2 / 2 (transport.py:59-67)."""
@@ -115,31 +238,61 @@ class Transport:
         n = z[0].numel()
         return z.new_tensor(-n / 2.0) * math.log(2 * math.pi) - z.pow(2).flatten(1).sum(1) / 2.0
 
-    def check_interval(self, *a, **k):
-        return 0, 1  # velocity + Linear integrates over exactly [0, 1] (transport.py:86-90)
+    def check_interval(self, train_eps=None, sample_eps=None, *, diffusion_form="SBDM", sde=False, reverse=False, eval=False,
+                       last_step_size=0.0):
+        """(t0, t1) of transport.py:69-95 for the Linear and GVP paths: a velocity model integrates and trains over exactly [0, 1];
+        noise / score models over [eps, 1 - eps] (eps = train_eps, or sample_eps with eval=True).  Arguments left None are the
+        transport's own."""
+        train_eps = self.train_eps if train_eps is None else train_eps
+        sample_eps = self.sample_eps if sample_eps is None else sample_eps
+        t0, t1 = 0, 1
+        eps = train_eps if not eval else sample_eps
+        if self.model_type != ModelType.VELOCITY:
+            # (a velocity model answers (0, 1) with sde=True too, as it always has here: sample_sde forms its own grid end
+            # 1 - last_step_size; the reference's values are returned for sde=False)
+            t0 = eps
+            t1 = 1 - eps if (not sde or last_step_size == 0) else 1 - last_step_size
+        if reverse:
+            t0, t1 = 1 - t0, 1 - t1
+        return t0, t1
 
     def sample(self, x1: torch.Tensor):
-        """x0 ~ N(0, I), t ~ U[0, 1] (transport.py:97-108)."""
+        """x0 ~ N(0, I), t ~ U[t0, t1] as `rand * (t1 - t0) + t0` (transport.py:97-108); [0, 1] for a velocity model."""
         x0 = torch.randn_like(x1)
+        t0, t1 = self.check_interval(self.train_eps, self.sample_eps)
+        scaled = (t0, t1) != (0, 1)
         if x1.is_cuda and torch.cuda.is_current_stream_capturing():
             # inside a HIP-graph capture (scldm_amd.training.GraphedTrainStep) host code does not run again at replay: t comes from
             # the device generator (whose captured draws advance per replay); same distribution as the reference's CPU draw
             t = torch.rand((x1.shape[0],), device=x1.device, dtype=x1.dtype)
+            if scaled:
+                t = t * (t1 - t0) + t0
         elif x1.is_cuda:
             # same CPU generator draw as the reference's `torch.rand((B,)).to(x1)`, but through pinned memory and an asynchronous
             # copy: a pageable host-to-device copy blocks the host until everything queued on the stream has finished, which
             # serialises the host's kernel enqueueing with the previous step's device work
-            t = torch.rand((x1.shape[0],), pin_memory=True).to(x1, non_blocking=True)
+            t = torch.rand((x1.shape[0],), pin_memory=True)
+            if scaled:
+                t = (t * (t1 - t0) + t0).pin_memory()
+            t = t.to(x1, non_blocking=True)
         else:
-            t = torch.rand((x1.shape[0],)).to(x1)
+            t = torch.rand((x1.shape[0],))
+            if scaled:
+                t = t * (t1 - t0) + t0
+            t = t.to(x1)
         return t, x0, x1
 
     def training_losses(self, model, x1, model_kwargs=None):
-        """{"pred", "loss"} with loss_b = mean((model(xt, t) - (x1 - x0))^2) (transport.py:110-150, path.py:148-151)."""
+        """{"pred", "loss"} (transport.py:110-150).  Velocity: loss_b = mean((m - ut)^2), ut = alpha' x1 + sigma' x0 (the loss weight
+        is ignored, as in the reference); noise: w mean((m - x0)^2); score: w mean((m sigma + x0)^2); w = 1 | (Dv/sigma)^2 |
+        Dv/sigma^2.  CUDA fp32 tensors that need no gradient of their own: one kernel plans (scldm_fm_mix on the default transport,
+        scldm_fm_plan otherwise), one forms the row loss, one its gradient; anything else takes the eager expressions."""
         model_kwargs = model_kwargs or {}
         t, x0, x1 = self.sample(x1)
         fused = (x1.is_cuda and x1.dtype == torch.float32 and x0.dtype == torch.float32 and t.dtype == torch.float32
                  and not x1.requires_grad and not x0.requires_grad and not t.requires_grad)
+        if not self.is_default:
+            return self._training_losses_general(model, t, x0, x1, model_kwargs, fused)
         if fused:
             # same arithmetic as below, two launches instead of five (xt bit-identical: every intermediate rounded separately)
             from .. import _lib
@@ -158,25 +311,81 @@ class Transport:
             return {"pred": pred, "loss": _FlowMatchLoss.apply(pred, ut)}
         return {"pred": pred, "loss": ((pred - ut) ** 2).mean(dim=list(range(1, pred.dim())))}
 
+    def _training_losses_general(self, model, t, x0, x1, model_kwargs, fused):
+        import ctypes as C
+        path = self.path_sampler
+        if fused:
+            from .. import _lib
+            x1c, x0c, tc = x1.contiguous(), x0.contiguous(), t.contiguous()
+            xt, tgt = torch.empty_like(x1c), torch.empty_like(x1c)
+            rowc = torch.empty(x1c.shape[0], 2, dtype=torch.float32, device=x1.device)
+            tr = self.c_struct()
+            with torch.cuda.device(x1.device):
+                _lib.check(_lib.lib().scldm_fm_plan(C.byref(tr), x1c.data_ptr(), x0c.data_ptr(), tc.data_ptr(), xt.data_ptr(), tgt.data_ptr(),
+                                                    rowc.data_ptr(), x1c.shape[0], x1c[0].numel(), _stream()), "scldm_fm_plan")
+            pred = model(xt, t, **model_kwargs)
+            assert pred.shape == xt.shape
+            if pred.is_cuda and pred.dtype == torch.float32:
+                return {"pred": pred, "loss": _WeightedFlowMatchLoss.apply(pred, tgt, rowc)}
+            ut = tgt                      # (a model that answers in another dtype: the eager loss below on the planned tensors)
+        else:
+            t, xt, ut = path.plan(t, x0, x1)
+            pred = model(xt, t, **model_kwargs)
+            assert pred.shape == xt.shape
+        dims = list(range(1, pred.dim()))
+        if self.model_type == ModelType.VELOCITY:
+            return {"pred": pred, "loss": ((pred - ut) ** 2).mean(dim=dims)}
+        _, drift_var = path.compute_drift(xt, t)
+        sigma_t, _ = path.compute_sigma_t(_expand_like(t, xt))
+        weight = {WeightType.VELOCITY: (drift_var / sigma_t) ** 2, WeightType.LIKELIHOOD: drift_var / (sigma_t ** 2), WeightType.NONE: 1}[self.loss_type]
+        if self.model_type == ModelType.NOISE:
+            return {"pred": pred, "loss": (weight * ((pred - x0) ** 2)).mean(dim=dims)}
+        return {"pred": pred, "loss": (weight * ((pred * sigma_t + x0) ** 2)).mean(dim=dims)}
+
     def get_drift(self):
+        """body_fn(x, t, model, **kw): the probability-flow drift (transport.py:152-183) - the model output of a velocity model,
+        alpha'/alpha x + Dv m of a score model, alpha'/alpha x + Dv (m / -sigma) of a noise model."""
+        path, model_type = self.path_sampler, self.model_type
+
         def body_fn(x, t, model, **model_kwargs):
-            out = model(x, t, **model_kwargs)
+            if model_type == ModelType.VELOCITY:
+                out = model(x, t, **model_kwargs)
+            else:
+                drift_mean, drift_var = path.compute_drift(x, t)
+                out = model(x, t, **model_kwargs)
+                if model_type == ModelType.NOISE:
+                    out = out / -path.compute_sigma_t(_expand_like(t, x))[0]
+                out = -drift_mean + drift_var * out
             assert out.shape == x.shape, "Output shape from ODE solver must match input shape"
             return out
 
         return body_fn
 
     def get_score(self):
-        """score_fn(x, t, model, **kw) of a velocity model (transport.py:185-202)."""
-        return lambda x, t, model, **kw: self.path_sampler.get_score_from_velocity(model(x, t, **kw), x, t)
+        """score_fn(x, t, model, **kw) (transport.py:185-202): m / -sigma of a noise model, m of a score model, a velocity model's through the path."""
+        path = self.path_sampler
+        if self.model_type == ModelType.NOISE:
+            return lambda x, t, model, **kw: model(x, t, **kw) / -path.compute_sigma_t(_expand_like(t, x))[0]
+        if self.model_type == ModelType.SCORE:
+            return lambda x, t, model, **kw: model(x, t, **kw)
+        return lambda x, t, model, **kw: path.get_score_from_velocity(model(x, t, **kw), x, t)
 
 
 def create_transport(path_type="Linear", prediction="velocity", loss_weight=None, train_eps=None, sample_eps=None):
-    """Same call as scldm.transport.create_transport; eps are forced to 0 for velocity+Linear (transport/__init__.py:55-57)."""
+    """Same call as scldm.transport.create_transport.  A velocity model on the Linear or GVP path: both eps forced to 0
+    (transport/__init__.py:55-57).  A noise / score model: train_eps and sample_eps default to 1e-3 each.  (The reference's line
+    `sample_eps = 1e-3 if train_eps is None else sample_eps` runs after train_eps was reassigned, so it leaves sample_eps = None
+    unless the caller passes one and then fails with TypeError in check_interval(eval=True); None becomes 1e-3 here, the value that
+    line evidently intends.)  path_type="VP" raises NotImplementedError."""
     model_type = {"noise": ModelType.NOISE, "score": ModelType.SCORE}.get(prediction, ModelType.VELOCITY)
     loss_type = {"velocity": WeightType.VELOCITY, "likelihood": WeightType.LIKELIHOOD}.get(loss_weight, WeightType.NONE)
     ptype = {"Linear": PathType.LINEAR, "GVP": PathType.GVP, "VP": PathType.VP}[path_type]
-    return Transport(model_type=model_type, path_type=ptype, loss_type=loss_type, train_eps=0, sample_eps=0)
+    if model_type is ModelType.VELOCITY:
+        train_eps = sample_eps = 0
+    else:
+        train_eps = 1e-3 if train_eps is None else train_eps
+        sample_eps = 1e-3 if sample_eps is None else sample_eps
+    return Transport(model_type=model_type, path_type=ptype, loss_type=loss_type, train_eps=train_eps, sample_eps=sample_eps)
 
 
 # Dormand-Prince 5(4) tableau (Dormand & Prince 1980) and the mid-point weights of the quartic dense output used by
@@ -201,6 +410,15 @@ class Sampler:
         self.drift = transport.get_drift()
         self.score = transport.get_score()
 
+    def _ode_interval(self) -> tuple[float, float]:
+        """(t0, t1) the ODE samplers integrate over: check_interval(..., sde=False, eval=True) - (0, 1) for a velocity model."""
+        t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, sde=False, eval=True, reverse=False)
+        return float(t0), float(t1)
+
+    def _default_only(self, what: str) -> None:
+        if not self.transport.is_default:
+            raise NotImplementedError(f"{what} serves the Linear path with a velocity model only; under another transport use sample_ode")
+
     def _sample_dopri5(self, num_steps: int, atol: float, rtol: float, first_step: float | None = None):
         """Adaptive Dormand-Prince 5(4) - what `torchdiffeq.odeint(method="dopri5")` computes for the reference's default
         `sample_ode()` (integrators.py:100-112; models.py:793).  The driver follows torchdiffeq's documented scheme step for
@@ -215,6 +433,7 @@ class Sampler:
         evaluation: two solves started from the same value can be compared step for step.  A scldm_amd DiT of the fused shape
         family runs this solve as one C call (`DiT.sample_ode_cfg(..., "dopri5")` -> scldm_sample_ode_dopri5)."""
         drift = self.drift
+        t_lo, t_hi = self._ode_interval()
 
         @torch.no_grad()
         def _sample(x, model, **model_kwargs):
@@ -303,7 +522,7 @@ class Sampler:
                         total = total + sp * cf
                     return total
 
-            ts = [float(v) for v in torch.linspace(0.0, 1.0, num_steps).double()]   # integrators.py:95, cast as the solver does
+            ts = [float(v) for v in torch.linspace(t_lo, t_hi, num_steps).double()]   # integrators.py:95, cast as the solver does
             y0 = x
             f0 = f(y0, ts[0])
             # (the first evaluation checked the packed weights against the parameters; no parameter changes inside a solve, so the
@@ -370,6 +589,7 @@ class Sampler:
         Three corners of the reference return NaN under this transport and raise here: diffusion_form="SBDM" - the DEFAULT - is
         (1 - t) / t at the t0 = 0 the solve starts from; "Heun" with last_step=None and "Mean" / "Tweedie" with last_step_size=0
         evaluate the score at t = 1."""
+        self._default_only("sample_sde")
         method = str(sampling_method).lower()
         if method not in ("euler", "heun"):
             raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'Euler' and 'Heun' are")
@@ -461,6 +681,7 @@ class Sampler:
         None: the automatic initial step) is the first attempted step size, as for `_sample_dopri5`.
         A scldm_amd DiT runs these solves on device through `DiT.log_likelihood_cfg` (fixed grid: scldm_logp_ode; "dopri5":
         scldm_logp_ode_dopri5)."""
+        self._default_only("sample_ode_likelihood")
         method = str(sampling_method).lower()
         if method not in ("euler", "heun", "dopri5"):
             raise NotImplementedError(f"sampling_method={sampling_method!r}: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are provided")
@@ -518,6 +739,8 @@ class Sampler:
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-5, rtol=1e-5, reverse=False):
         """Returns fn(x, model, **model_kwargs) -> (num_steps, *x.shape) trajectory; callers take [-1] (models.py:812).
+        The transport's drift is integrated over linspace(t0, t1, num_steps), (t0, t1) = (0, 1) for a velocity model and
+        (sample_eps, 1 - sample_eps) for a noise / score model (transport.py:324-369); host-driven, any callable.
 
         `num_steps` grid points = num_steps-1 steps (integrators.py:95).  The model sees t broadcast to a (B,)
         vector (integrators.py:103-104) - here as a stride-0 view of one device scalar, which a scldm_amd DiT
@@ -531,10 +754,11 @@ class Sampler:
         if method == "dopri5":
             return self._sample_dopri5(num_steps, atol, rtol)
         drift = self.drift
+        t_lo, t_hi = self._ode_interval()
 
         @torch.no_grad()
         def _sample(x, model, **model_kwargs):
-            ts = torch.linspace(0.0, 1.0, num_steps)
+            ts = torch.linspace(t_lo, t_hi, num_steps)
             traj = [x]
 
             def f(xc, tval):
