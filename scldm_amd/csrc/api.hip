@@ -10,6 +10,7 @@
 
 #include <cmath>
 #include "api_common.hpp"
+#include "cfg_plan.hpp"
 #include "dit_aux.hpp"
 #include "dit_forward.hpp"
 #include "dit_handle.hpp"
@@ -18,6 +19,7 @@
 #include "transport_path.hpp"
 #include "dopri5_ctl.hpp"
 #include "dopri5_fused.hpp"
+#include "fixed_grid.hpp"
 
 using namespace scldm;
 
@@ -106,7 +108,6 @@ extern "C" int scldm_dit_create(const scldm_dit_config* cfg, scldm_dit** out) {
   if (const char* e = getenv("SCLDM_ADALN_VALU")) h->adaln_valu = atoi(e) != 0;
   if (const char* e = getenv("SCLDM_ADALN_EXACT")) h->adaln_exact = atoi(e) != 0;
   if (const char* e = getenv("SCLDM_ADALN_ROWTILE")) h->adaln_rowtile = atoi(e) != 0;
-  if (const char* e = getenv("SCLDM_COND_AHEAD")) h->cond_ahead = atoi(e) != 0;
   if (const char* e = getenv("SCLDM_COND_ALL")) h->cond_all_on = atoi(e) != 0;
   if (const char* e = getenv("SCLDM_GROUPS")) h->groups = std::min(4, std::max(1, atoi(e)));
   if (const char* e = getenv("SCLDM_TAIL_SPLIT")) h->tail_split = atoi(e) != 0;
@@ -209,11 +210,8 @@ extern "C" void scldm_dit_destroy(scldm_dit* h) {
   }
   if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
   if (h->bwd_pack_ev) (void)hipEventDestroy(h->bwd_pack_ev);
-  if (h->cond_stream) (void)hipStreamDestroy(h->cond_stream);
   if (h->cond_all) (void)hipFree(h->cond_all);
   if (h->rk_host) (void)hipHostFree(h->rk_host);
-  for (hipEvent_t ev : {h->ev_cond[0], h->ev_cond[1], h->ev_free[0], h->ev_free[1], h->ev_ready})
-    if (ev) (void)hipEventDestroy(ev);
   delete h;
 }
 
@@ -446,8 +444,6 @@ struct Ws {
   float* mod;     // (n_rows, mod_w)
   float* silu;    // (n_rows, 256)
   void* asplit;   // (pad32(n_rows), 256) split-bf16 A fragments of the conditioning rows (adaln_x3_block_kernel)
-  float *mod2, *silu2;   // second conditioning buffer set (n_state > 0: the fused sampler prepares evaluation e + 1 beside evaluation e)
-  void* asplit2;
   float* temb;    // (256) timestep embedding shared by all rows of a scalar-t step
   int32_t* ridx;  // (n_fwd)
   float* dz;      // (n_state, e)
@@ -466,13 +462,6 @@ static Ws carve(const scldm_dit* h, void* base, int n_fwd, int n_rows, int n_sta
   w.mod = (float*)take((size_t)n_rows * h->mod_w * 4);
   w.silu = (float*)take((size_t)(n_rows + 1) * 256 * 4);  // +1 spare row (device scalar t)
   w.asplit = take((size_t)((n_rows + 31) / 32 * 32) * 256 * 4);
-  w.mod2 = w.silu2 = nullptr;
-  w.asplit2 = nullptr;
-  if (n_state > 0) {
-    w.mod2 = (float*)take((size_t)n_rows * h->mod_w * 4);
-    w.silu2 = (float*)take((size_t)(n_rows + 1) * 256 * 4);
-    w.asplit2 = take((size_t)((n_rows + 31) / 32 * 32) * 256 * 4);
-  }
   w.temb = (float*)take((size_t)kMaxTembEvals * 256 * 4);  // per-evaluation timestep embeddings of a whole solve
   w.ridx = (int32_t*)take((size_t)n_fwd * 4);
   w.dz = (float*)take((size_t)n_state * e * 4);
@@ -765,16 +754,7 @@ extern "C" int scldm_dit_forward(scldm_dit* h, const float* x, const float* t, c
   return trunk(h, x, n, 1, n, w.mod, w.ridx, w.h, out, precision, st);
 }
 
-// One CFG evaluation: dz (2B, e) = forward_with_cfg(z, t); t_dev/t_stride describe the device-side t.
-struct CfgPlan {
-  int B, P, U, uncond_rows, n_fwd, n_rows;
-  bool direct;   // SCLDM_OPT_CFG1_DIRECT applies: rows [B, 2B) run the conditional forward only (guided = conditional at scale 1)
-  const int64_t* const* ulabels;
-  const int32_t* cell_row;
-  uint32_t mask[SCLDM_MAX_CLASSES];
-  float scale[SCLDM_MAX_CLASSES];
-};
-
+// One CFG evaluation (CfgPlan, make_plan: cfg_plan.hpp).
 // plan (optional, device): plan[0] == 0 selects the dense plan (one row per sample-forward: uncond_rows = n_direct, U = B, no
 // cell_row) over the uniform one given by the arguments
 __global__ void fill_cfg_row_index_kernel(int32_t* __restrict__ ri, const int32_t* __restrict__ cell_row, int n_direct,
@@ -848,42 +828,25 @@ static int cfg_cond(scldm_dit* h, const CfgPlan& pl, const float* t_dev, int t_s
   return launch_adaln(h, w.silu, w.mod, t_stride == 2 ? rows_d : pl.n_rows, st, t_stride == 2 ? h->d_plan + 1 : nullptr, prec, w.asplit);
 }
 
-// The state-dependent part: the trunk over every sample-forward of the evaluation, then the CFG blend.
+// The state-dependent part of a CFG evaluation in two halves, so that a solve can put its own conditioning route between them:
+// the trunk over every sample-forward writes cfg_trunk_out(), cfg_finish() blends it into dz.
+// direct: the guided rows are the conditional forward itself - the trunk runs 2B sample-forwards and writes dz, no blend.
+static int cfg_trunk_rows(const CfgPlan& pl) { return pl.direct ? 2 * pl.B : pl.n_fwd; }
+static float* cfg_trunk_out(const CfgPlan& pl, const Ws& w, float* dz) { return pl.direct ? dz : w.v; }
 // euler_z / euler_h: the caller's Euler update z += h * dz is applied by the blend kernel itself (one launch less per evaluation)
-static int cfg_trunk(scldm_dit* h, const CfgPlan& pl, const float* z, const Ws& w, float* dz, int prec, hipStream_t st,
-                     float* euler_z = nullptr, float euler_h = 0.f) {
-  int rc;
-  if (pl.direct) {  // guided rows = the conditional forward itself: the trunk writes dz, no blend
-    if ((rc = trunk(h, z, 2 * pl.B, pl.B, 2 * pl.B, w.mod, w.ridx, w.h, dz, prec, st))) return rc;
-    if (euler_z) {
-      const size_t n = (size_t)2 * pl.B * 16 * h->cfg.n_embed_input;
-      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(euler_z, dz, euler_z, euler_h, n);
-      LAUNCH_CHECK();
-    }
-    return SCLDM_OK;
-  }
-  if ((rc = trunk(h, z, 2 * pl.B, pl.B, pl.n_fwd, w.mod, w.ridx, w.h, w.v, prec, st))) return rc;
-  CfgArgs ca;
-  ca.v = w.v;
-  ca.dz = dz;
-  ca.B = pl.B;
-  ca.e = 16 * h->cfg.n_embed_input;
-  ca.P = pl.P;
-  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) ca.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
-  ca.z = euler_z;
-  ca.hstep = euler_h;
-  const size_t n = (size_t)2 * pl.B * ca.e;
-  cfg_blend_kernel<<<cdiv(n, 256), 256, 0, st>>>(ca);
-  LAUNCH_CHECK();
-  return SCLDM_OK;
+static int cfg_finish(scldm_dit* h, const CfgPlan& pl, const Ws& w, float* dz, hipStream_t st, float* euler_z, float euler_h) {
+  const int e = 16 * h->cfg.n_embed_input;
+  if (!pl.direct) return scldm_cfg_blend(w.v, dz, pl.B, e, pl.P, pl.scale, euler_z, euler_h, st);
+  return euler_z ? scldm_ode_axpy(euler_z, dz, euler_z, euler_h, (size_t)2 * pl.B * e, st) : SCLDM_OK;
 }
 
 // One CFG evaluation: dz (2B, e) = forward_with_cfg(z, t); t_dev/t_stride describe the device-side t.
 static int cfg_eval(scldm_dit* h, const CfgPlan& pl, const float* z, const float* t_dev, int t_stride, const Ws& w,
-                    float* dz, int prec, hipStream_t st, const float* temb_pre = nullptr, float* euler_z = nullptr, float euler_h = 0.f) {
-  int rc = cfg_cond(h, pl, t_dev, t_stride, w, prec, st, temb_pre);
+                    float* dz, int prec, hipStream_t st) {
+  int rc = cfg_cond(h, pl, t_dev, t_stride, w, prec, st);
   if (rc) return rc;
-  return cfg_trunk(h, pl, z, w, dz, prec, st, euler_z, euler_h);
+  if ((rc = trunk(h, z, 2 * pl.B, pl.B, cfg_trunk_rows(pl), w.mod, w.ridx, w.h, cfg_trunk_out(pl, w, dz), prec, st))) return rc;
+  return cfg_finish(h, pl, w, dz, st, nullptr, 0.f);
 }
 
 // host launchers of the CFG / ODE kernels for the record-free inference path of wide shapes (train_api.hip; dit_handle.hpp)
@@ -899,7 +862,7 @@ int scldm_cfg_blend(const float* v, float* dz, int B, int e, int P, const float*
   ca.B = B;
   ca.e = e;
   ca.P = P;
-  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) ca.scale[p] = p < P ? scale[p] : 0.f;
+  fill_pass_scale(ca.scale, P, scale);
   ca.z = euler_z;
   ca.hstep = euler_h;
   cfg_blend_kernel<<<cdiv((size_t)2 * B * e, 256), 256, 0, st>>>(ca);
@@ -914,32 +877,6 @@ int scldm_ode_axpy(const float* z, const float* k, float* out, float hstep, size
 int scldm_ode_heun(float* z, const float* k1, const float* k2, float half_h, size_t n, hipStream_t st) {
   heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, k1, k2, half_h, n);
   LAUNCH_CHECK();
-  return SCLDM_OK;
-}
-
-static int make_plan(scldm_dit* h, CfgPlan& pl, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B,
-                     int n_pass, const uint32_t* pass_mask, const float* pass_scale, int t_stride) {
-  if (B <= 0) return fail(SCLDM_ERR_SHAPE, "B must be positive");
-  if (!h->cfg.has_null_row && h->cfg.n_classes > 0)
-    return fail(SCLDM_ERR_SHAPE, "classifier-free guidance needs the null rows of the class tables (model built with cfg_dropout_prob == 0)");
-  if (n_pass < 0 || n_pass > SCLDM_MAX_CLASSES) return fail(SCLDM_ERR_SHAPE, "n_pass out of range");
-  if (n_pass > 0 && (!ulabels || !pass_mask || !pass_scale || n_urows <= 0)) return fail(SCLDM_ERR_SHAPE, "conditional passes need labels/masks/scales");
-  if (n_pass > 0 && !cell_row && n_urows != B) return fail(SCLDM_ERR_SHAPE, "cell_row is NULL but n_urows (%d) != B (%d)", n_urows, B);
-  if (t_stride == 1 && n_pass > 0 && (cell_row || n_urows != B))
-    return fail(SCLDM_ERR_SHAPE, "per-sample t (t_stride=1) requires per-cell label rows (n_urows == B, cell_row NULL)");
-  pl.B = B;
-  pl.P = n_pass;
-  pl.U = n_pass > 0 ? n_urows : 0;
-  pl.uncond_rows = (t_stride == 0) ? 1 : 2 * B;
-  pl.n_fwd = 2 * B + n_pass * B;
-  pl.n_rows = (t_stride == 2) ? 2 * B + n_pass * B /* the larger, dense plan sizes the workspace */ : pl.uncond_rows + pl.P * pl.U;
-  pl.ulabels = ulabels;
-  pl.cell_row = cell_row;
-  pl.direct = h->cfg1_direct && t_stride == 0 && n_pass == 1 && pass_scale[0] == 1.0f;
-  for (int p = 0; p < n_pass; ++p) {
-    pl.mask[p] = pass_mask[p];
-    pl.scale[p] = pass_scale[p];
-  }
   return SCLDM_OK;
 }
 
@@ -964,45 +901,128 @@ extern "C" int scldm_dit_forward_cfg(scldm_dit* h, const float* x, const float* 
   return cfg_eval(h, pl, x, t, t_stride, w, out, precision, st);
 }
 
-// Whole-solve conditioning (see scldm_sample_ode): every evaluation's adaLN vectors in one row launch and one projection, into the handle's
-// buffer; *mod_all stays NULL when the per-evaluation launches are to be used (over budget, no room, or the buffer would have to grow
-// inside a stream capture).  temb: the (n_evals, 256) timestep embeddings of the solve.
-static int cond_all_prepare(scldm_dit* h, const CfgPlan& pl, const float* temb, int n_evals, int prec, hipStream_t st, float** mod_all_out) {
-  int rc;
-  float* mod_all = nullptr;
-  const size_t rows_all = (size_t)n_evals * pl.n_rows;
-  const size_t b_mod = align256(rows_all * h->mod_w * 4), b_silu = align256((rows_all + 1) * 256 * 4), b_split = align256((rows_all + 31) / 32 * 32 * 256 * 4);
-  if (b_mod <= ((size_t)1 << 30)) {
-    const size_t need = b_mod + b_silu + b_split;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap);
-    if (h->cond_all_bytes < need && cap == hipStreamCaptureStatusNone) {   // (no allocation inside a stream capture: the per-evaluation launches)
-      HIP_TRY(hipStreamSynchronize(st));     // (an earlier solve on this stream may still read the buffer that is replaced)
-      if (h->cond_all) (void)hipFree(h->cond_all);
-      h->cond_all = nullptr;
-      h->cond_all_bytes = 0;
-      if (hipMalloc(&h->cond_all, need) == hipSuccess) h->cond_all_bytes = need;
-      else (void)hipGetLastError();          // no room: the per-evaluation launches
-    }
-    if (h->cond_all_bytes >= need) {
-      mod_all = reinterpret_cast<float*>(h->cond_all);
-      float* silu_all = reinterpret_cast<float*>(reinterpret_cast<char*>(h->cond_all) + b_mod);
-      void* split_all = reinterpret_cast<char*>(h->cond_all) + b_mod + b_silu;
-      CondRowsArgs ca = cond_rows_args(h, pl, temb, silu_all, nullptr);
-      cond_rows_kernel<<<dim3(pl.n_rows, n_evals), 256, 0, st>>>(ca);
-      LAUNCH_CHECK();
-      if ((rc = launch_adaln(h, silu_all, mod_all, (int)rows_all, st, nullptr, prec, split_all))) return rc;
-    }
-  }
-  *mod_all_out = mod_all;
-  return SCLDM_OK;
+// The adaLN vectors of n_evals evaluations from their (n_evals, 256) timestep embeddings: ONE row launch over (rows, evaluations) and
+// ONE projection over n_evals x n_rows rows -> mod, evaluation j in rows [j n_rows, (j + 1) n_rows).  silu, asplit: scratch for as
+// many rows.  Same kernels and per-row arithmetic as the per-evaluation launches of cfg_cond: bit-identical (tested).
+static int cond_batch(scldm_dit* h, const CfgPlan& pl, const float* temb, int n_evals, float* silu, float* mod, void* asplit, int prec,
+                      hipStream_t st) {
+  CondRowsArgs ca = cond_rows_args(h, pl, temb, silu, nullptr);
+  cond_rows_kernel<<<dim3(pl.n_rows, n_evals), 256, 0, st>>>(ca);
+  LAUNCH_CHECK();
+  return launch_adaln(h, silu, mod, n_evals * pl.n_rows, st, nullptr, prec, asplit);
 }
 
-// torch.linspace(0, 1, steps) in fp32 (integrators.py:95): symmetric fill from both ends.
-static float linspace01(int idx, int steps) {
-  const float step = 1.0f / (float)(steps - 1);
-  return (idx < steps / 2) ? step * (float)idx : 1.0f - step * (float)(steps - idx - 1);
+// Whole-solve conditioning (see FusedSolve): cond_batch over every evaluation of the solve, into the handle's buffer; *mod_all stays NULL
+// when the per-evaluation launches are to be used (over budget, no room, or the buffer would have to grow inside a stream capture).
+// temb: the (n_evals, 256) timestep embeddings of the solve.
+static int cond_all_prepare(scldm_dit* h, const CfgPlan& pl, const float* temb, int n_evals, int prec, hipStream_t st, float** mod_all_out) {
+  *mod_all_out = nullptr;
+  const size_t rows_all = (size_t)n_evals * pl.n_rows;
+  const size_t b_mod = align256(rows_all * h->mod_w * 4), b_silu = align256((rows_all + 1) * 256 * 4), b_split = align256((rows_all + 31) / 32 * 32 * 256 * 4);
+  if (b_mod > ((size_t)1 << 30)) return SCLDM_OK;
+  const size_t need = b_mod + b_silu + b_split;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cap);
+  if (h->cond_all_bytes < need && cap == hipStreamCaptureStatusNone) {   // (no allocation inside a stream capture: the per-evaluation launches)
+    HIP_TRY(hipStreamSynchronize(st));     // (an earlier solve on this stream may still read the buffer that is replaced)
+    if (h->cond_all) (void)hipFree(h->cond_all);
+    h->cond_all = nullptr;
+    h->cond_all_bytes = 0;
+    if (hipMalloc(&h->cond_all, need) == hipSuccess) h->cond_all_bytes = need;
+    else (void)hipGetLastError();          // no room: the per-evaluation launches
+  }
+  if (h->cond_all_bytes < need) return SCLDM_OK;
+  char* base = reinterpret_cast<char*>(h->cond_all);
+  *mod_all_out = reinterpret_cast<float*>(base);
+  return cond_batch(h, pl, temb, n_evals, reinterpret_cast<float*>(base + b_mod), *mod_all_out, base + b_mod + b_silu, prec, st);
 }
+
+// One fixed-grid solve of the fused family (scldm_sample_ode, scldm_sample_sde, scldm_sample_ode_transport): set up once per call,
+// then asked one thing per evaluation - eval(e, zin, out): the conditioning of evaluation e, then the trunk of zin into out.  Which
+// conditioning route serves the solve is decided and kept in here:
+//   whole solve    the adaLN vectors depend on t and the labels only, so every evaluation's rows go through ONE timestep-embedding
+//                  launch, ONE row launch and ONE adaLN projection over n_evals x n_rows rows before the loop instead of two launches
+//                  per evaluation on the critical path (4.7 + 8.2 us of a 174 us evaluation at 128 cells:
+//                  profiles/r6_small_batch_trace.txt); an evaluation then reads its slice.  Budget 1 GB (15 rows x 100 evaluations =
+//                  83 MB for the dentate vocabulary, 51 rows x 200 Heun evaluations = 564 MB for hlca; a batch of 1 024 distinct joint
+//                  labels would need 5.7 GB and takes the next route).  SCLDM_COND_ALL=0 switches it off;
+//   pre-embedded   every timestep embedding in one launch before the loop; the row launch and the projection per evaluation;
+//   step by step   solves beyond kMaxTembEvals evaluations: a device scalar t, embedded per evaluation.
+struct FusedSolve {
+  scldm_dit* h;
+  CfgPlan pl;
+  Ws w;
+  int prec;
+  hipStream_t st;
+  size_t n;   // elements of the (2B, e) state
+
+  // the plan and the workspace: argument checks only, nothing is enqueued
+  int plan(scldm_dit* h_, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask,
+           const float* pass_scale, int precision, void* ws, void* stream) {
+    h = h_;
+    prec = precision;
+    st = (hipStream_t)stream;
+    int rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0);
+    if (rc) return rc;
+    w = carve(h, ws, pl.n_fwd, pl.n_rows, 2 * B);
+    n = (size_t)2 * B * 16 * h->cfg.n_embed_input;
+    return SCLDM_OK;
+  }
+  // The row index, the timestep embeddings and (whole-solve route) the conditioning of every evaluation.  times: the time of each
+  // evaluation (grid::eval_times).  grid_steps > 0: the solve runs over linspace(0, 1, grid_steps) and the embeddings come from the
+  // device's own grid (t_embed_all_kernel, `grid_heun` its layout) - it forms 1 - step x as one fma, which the host list is not
+  // guaranteed to reproduce, so scldm_sample_ode keeps it.
+  int prepare(const std::vector<float>& times, int grid_steps = 0, bool grid_heun = false) {
+    tl_ = times;
+    const int n_evals = (int)tl_.size();
+    fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, pl.cell_row, 2 * pl.B, 1, pl.B, pl.U, pl.P, nullptr, pl.direct);
+    LAUNCH_CHECK();
+    pre_ = n_evals <= kMaxTembEvals;
+    if (!pre_) return SCLDM_OK;
+    if (grid_steps > 0) {
+      t_embed_all_kernel<<<n_evals, 256, 0, st>>>(grid_steps, grid_heun, h->w0t, h->b0, h->w2t, h->b2, w.temb);
+    } else {
+      // the list of times sits at the head of the trunk's residual buffer: the embedding launch below has read it before the first trunk
+      // launch of this call overwrites it (stream order)
+      float* tlist = w.h;
+      for (int c0 = 0; c0 < n_evals; c0 += sde::kTChunk) {
+        sde::TChunk ch{};
+        const int m = std::min(sde::kTChunk, n_evals - c0);
+        for (int j = 0; j < m; ++j) ch.t[j] = tl_[c0 + j];
+        sde::set_tlist_kernel<<<1, sde::kTChunk, 0, st>>>(tlist + c0, ch, m);
+      }
+      sde::t_embed_list_kernel<<<n_evals, 256, 0, st>>>(tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
+    }
+    LAUNCH_CHECK();
+    if (h->cond_all_on && n_evals > 1) return cond_all_prepare(h, pl, w.temb, n_evals, prec, st, &mod_all_);
+    return SCLDM_OK;
+  }
+  // the conditioning of evaluation e, then the trunk of zin -> out: (cfg_trunk_rows(pl), e) rows, for the entry's blend kernel
+  int eval(int e, const float* zin, float* out) {
+    const float* mod = w.mod;
+    if (mod_all_) mod = mod_all_ + (size_t)e * pl.n_rows * h->mod_w;
+    else {
+      float* tscal = w.silu + (size_t)pl.n_rows * 256;   // device scalar t: the spare row carve() reserves after the silu rows
+      if (!pre_) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tl_[e]);
+      int rc = cfg_cond(h, pl, tscal, 0, w, prec, st, pre_ ? w.temb + (size_t)e * 256 : nullptr);
+      if (rc) return rc;
+    }
+    return trunk(h, zin, 2 * pl.B, pl.B, cfg_trunk_rows(pl), mod, w.ridx, w.h, out, prec, st);
+  }
+  // grid::euler_heun over linspace(a, b, n_steps + 1) on the state z with the workspace's slope buffers; step_eval as its `eval`
+  template <class Eval>
+  int step_loop(int n_steps, float a, float b, bool heun, float* z, Eval&& step_eval) {
+    return grid::euler_heun(
+        n_steps, a, b, heun, grid::Buffers{z, w.dz, w.k2, w.ztmp}, step_eval,
+        [&](const float* x, const float* k, float* out, float hs) { return scldm_ode_axpy(x, k, out, hs, n, st); },
+        [&](float* x, const float* k1, const float* k2, float half_hs) { return scldm_ode_heun(x, k1, k2, half_hs, n, st); });
+  }
+
+ private:
+  std::vector<float> tl_;
+  bool pre_ = false;
+  float* mod_all_ = nullptr;
+};
 
 extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row,
                                 int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method,
@@ -1012,96 +1032,16 @@ extern "C" int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ul
   if (!z || !ws_) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
   if (n_steps < 1) return fail(SCLDM_ERR_SHAPE, "n_steps must be >= 1");
   if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
-  CfgPlan pl;
-  if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
-  hipStream_t st = (hipStream_t)stream_;
-  Ws w = carve(h, ws_, pl.n_fwd, pl.n_rows, 2 * B);
-  fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, cell_row, 2 * B, 1, B, pl.U, pl.P, nullptr, pl.direct);
-  LAUNCH_CHECK();
-  const size_t n = (size_t)2 * B * 16 * h->cfg.n_embed_input;
-  const int steps = n_steps + 1;
-  float* tscal = w.silu + (size_t)pl.n_rows * 256;  // device scalar t: the spare row carve() reserves after the silu rows
-  const int n_evals = (method == SCLDM_METHOD_EULER) ? n_steps : 2 * n_steps;
-  const bool pre = n_evals <= kMaxTembEvals;
-  if (pre) {
-    t_embed_all_kernel<<<n_evals, 256, 0, st>>>(steps, method == SCLDM_METHOD_HEUN, h->w0t, h->b0, h->w2t, h->b2, w.temb);
-    LAUNCH_CHECK();
-  }
-  // Conditioning ahead (round 4, opt-in SCLDM_COND_AHEAD=1): the adaLN vectors of evaluation e + 1 depend on t and the labels only, so they are prepared on a
-  // second stream into the OTHER of two buffer sets while the trunk of evaluation e runs (its waves fill the CUs the trunk's last,
-  // partial round leaves idle: 36 us of adaLN projection per evaluation at 1 024 joint-conditioned cells).  Needs every evaluation's
-  // timestep embedding up front (`pre`).  ev_cond[b]: set b is ready; ev_free[b]: the trunk that read set b is done.  All work of the
-  // second stream is joined into `st` before the last trunk, i.e. before this call's last kernel.
-  const bool ahead = pre && h->cond_ahead && w.mod2 != nullptr && n_evals > 1;
-  Ws wb[2] = {w, w};
-  wb[1].mod = w.mod2;
-  wb[1].silu = w.silu2;
-  wb[1].asplit = w.asplit2;
-  if (ahead) {
-    if (!h->cond_stream) {
-      // LOWEST priority: the projection's workgroups are dispatched only when no workgroup of the trunk is pending, i.e. into the slots the
-      // trunk's last, partial round leaves idle - at normal priority they take slots from the trunk's FIRST round and cost more than they
-      // hide (same-box A/B: parse1m 1 024 cells -1.5 %, profiles/r4h_ab_cond_ahead.txt).  At lowest priority the trunk still runs 18 us
-      // longer beside it while 36 us are hidden: +0.5 % at 1 024 joint-conditioned cells, -0.8 % at 512 cells, -0.2 % at 4 096 - not the default.
-      int prio_least = 0, prio_greatest = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-      HIP_TRY(hipStreamCreateWithPriority(&h->cond_stream, hipStreamNonBlocking, prio_least));
-      for (hipEvent_t* ev : {&h->ev_cond[0], &h->ev_cond[1], &h->ev_free[0], &h->ev_free[1], &h->ev_ready})
-        HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventRecord(h->ev_ready, st));                       // timestep embeddings, row index, packed weights: all queued on st
-    HIP_TRY(hipStreamWaitEvent(h->cond_stream, h->ev_ready, 0));
-    if ((rc = cfg_cond(h, pl, tscal, 0, wb[0], precision, st, w.temb))) return rc;   // evaluation 0: in line
-  }
-  // Conditioning of the whole solve up front (round 6): the adaLN vectors depend on t and the labels only, so every evaluation's rows go
-  // through ONE timestep-embedding launch (above), ONE row launch and ONE adaLN projection over n_evals x n_rows rows instead of two
-  // launches per evaluation on the critical path (4.7 + 8.2 us of a 174 us evaluation at 128 cells: profiles/r6_small_batch_trace.txt).
-  // Same kernels, same per-row arithmetic: bit-identical (tested).  Budget 1 GB (15 rows x 100 evaluations = 83 MB for the dentate
-  // vocabulary, 51 rows x 200 Heun evaluations = 564 MB for hlca; a batch of 1 024 distinct joint labels would need 5.7 GB and keeps the
-  // per-evaluation launches).
-  float* mod_all = nullptr;
-  if (pre && !ahead && h->cond_all_on && n_evals > 1)
-    if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
-  int e_idx = 0;   // running evaluation index
-  // one evaluation: (ahead) queue the conditioning of the next one on the second stream, wait for this one's, run the trunk
-  auto eval = [&](const float* zin, float tval, float* dz, float* euler_z, float euler_h) -> int {
-    const int e = e_idx++;
-    if (mod_all) {
-      Ws we = w;
-      we.mod = mod_all + (size_t)e * pl.n_rows * h->mod_w;
-      return cfg_trunk(h, pl, zin, we, dz, precision, st, euler_z, euler_h);
-    }
-    if (!ahead) {
-      if (!pre) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tval);
-      return cfg_eval(h, pl, zin, tscal, 0, w, dz, precision, st, pre ? w.temb + (size_t)e * 256 : nullptr, euler_z, euler_h);
-    }
-    const int b = e & 1;
-    if (e + 1 < n_evals) {
-      if (e >= 1) HIP_TRY(hipStreamWaitEvent(h->cond_stream, h->ev_free[b ^ 1], 0));   // the trunk of evaluation e - 1 read set b ^ 1
-      int rc2 = cfg_cond(h, pl, tscal, 0, wb[b ^ 1], precision, h->cond_stream, w.temb + (size_t)(e + 1) * 256);
-      if (rc2) return rc2;
-      HIP_TRY(hipEventRecord(h->ev_cond[b ^ 1], h->cond_stream));
-    }
-    if (e >= 1) HIP_TRY(hipStreamWaitEvent(st, h->ev_cond[b], 0));
-    int rc2 = cfg_trunk(h, pl, zin, wb[b], dz, precision, st, euler_z, euler_h);
-    if (rc2) return rc2;
-    HIP_TRY(hipEventRecord(h->ev_free[b], st));
-    return SCLDM_OK;
+  FusedSolve s;
+  if ((rc = s.plan(h, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, precision, ws_, stream_))) return rc;
+  const bool heun = method == SCLDM_METHOD_HEUN;
+  if ((rc = s.prepare(grid::eval_times(n_steps, 0.f, 1.f, heun ? grid::kNext : grid::kNone), n_steps + 1, heun))) return rc;
+  // one evaluation: the trunk, then the CFG blend into dz (which also applies the Euler update when euler_z is given)
+  auto eval = [&](int e, const float* zin, float* dz, float* euler_z, float hs) -> int {
+    int rc2 = s.eval(e, zin, cfg_trunk_out(s.pl, s.w, dz));
+    return rc2 ? rc2 : cfg_finish(h, s.pl, s.w, dz, s.st, euler_z, hs);
   };
-  for (int i = 0; i < n_steps; ++i) {
-    const float t0 = linspace01(i, steps), t1 = linspace01(i + 1, steps);
-    const float hs = t1 - t0;
-    if (method == SCLDM_METHOD_EULER) {
-      if ((rc = eval(z, t0, w.dz, z, hs))) return rc;
-    } else {
-      if ((rc = eval(z, t0, w.dz, nullptr, 0.f))) return rc;
-      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.ztmp, hs, n);
-      if ((rc = eval(w.ztmp, t1, w.k2, nullptr, 0.f))) return rc;
-      heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.k2, 0.5f * hs, n);
-    }
-    LAUNCH_CHECK();
-  }
-  return SCLDM_OK;
+  return s.step_loop(n_steps, 0.f, 1.f, heun, z, eval);
 }
 
 // ---- adaptive Dormand-Prince 5(4) sampling (dopri5_ctl.hpp, dopri5_fused.hpp) ----
@@ -1118,11 +1058,6 @@ extern "C" double scldm_dopri5_initial_step(double h0, double d1, double d2) { r
 #include "dopri5_api.inc"
 
 // ---- SDE sampling (sde.hpp) -----------------------------------------------------------------------------------------------------------
-// torch.linspace(0, t1, steps) in fp32: linspace01's symmetric fill for any end point (step = (t1 - 0) / (steps - 1) in fp32)
-static float linspace0(int idx, int steps, float t1) {
-  const float step = t1 / (float)(steps - 1);
-  return (idx < steps / 2) ? step * (float)idx : t1 - step * (float)(steps - idx - 1);
-}
 // D(t) of path.py:52-77 for the Linear path (sigma_t = 1 - t), in double from the fp32 t the model sees
 static double sde_diffusion(int form, double norm, double t) {
   const double pi = 3.14159265358979323846;
@@ -1173,69 +1108,35 @@ extern "C" int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ul
     return fail(SCLDM_ERR_SHAPE, "last_step Mean / Tweedie with last_step_size 0 evaluates the score at t = 1; give a positive last_step_size or use last_step Euler / None");
   if (cell_offset < 0 || cells_total < cell_offset + B) return fail(SCLDM_ERR_SHAPE, "cells_total (%lld) < cell_offset (%lld) + B (%d)", cells_total, cell_offset, B);
   if (((uintptr_t)z & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)traj & 15)) return fail(SCLDM_ERR_SHAPE, "z, noise and traj must be 16-byte aligned");
-  CfgPlan pl;
-  if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
-  hipStream_t st = (hipStream_t)stream_;
-  Ws w = carve(h, ws_, pl.n_fwd, pl.n_rows, 2 * B);
+  FusedSolve s;
+  if ((rc = s.plan(h, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, precision, ws_, stream_))) return rc;
+  const CfgPlan& pl = s.pl;
+  const Ws& w = s.w;
+  hipStream_t st = s.st;
   const int e_row = 16 * h->cfg.n_embed_input;
-  const size_t n = (size_t)2 * B * e_row;
+  const size_t n = s.n;
   if (n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state too large (at most 2^33 elements)");
   const bool heun = method == SCLDM_METHOD_HEUN, has_last = last_step != SCLDM_SDE_LAST_NONE;
   const int n_steps = num_steps - 1;
-  const int n_evals = (heun ? 2 : 1) * n_steps + (has_last ? 1 : 0);
   // the fp32 grid of integrators.py:23-24 and every evaluation's time
   const float t1 = (float)(1.0 - (double)last_step_size);
-  const float dt = linspace0(1, num_steps, t1) - linspace0(0, num_steps, t1);
-  std::vector<float> tl;
-  tl.reserve(n_evals);
-  for (int i = 0; i < n_steps; ++i) {
-    const float t = linspace0(i, num_steps, t1);
-    tl.push_back(t);
-    if (heun) tl.push_back(t + dt);
-  }
-  if (has_last) tl.push_back(t1);
+  const float dt = grid::linspace(1, num_steps, 0.f, t1) - grid::linspace(0, num_steps, 0.f, t1);
+  const std::vector<float> tl = grid::eval_times(n_steps, 0.f, t1, heun ? grid::kPlusDt : grid::kNone, has_last ? &t1 : nullptr);
   for (int i = 0; i < (int)tl.size() - (has_last ? 1 : 0); ++i)
     if (!(tl[i] < 1.0f)) return fail(SCLDM_ERR_SHAPE, "evaluation %d of the solve sits at t = %g >= 1, where the score is singular", i, (double)tl[i]);
-  fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, cell_row, 2 * B, 1, B, pl.U, pl.P, nullptr, pl.direct);
-  LAUNCH_CHECK();
-  float* tscal = w.silu + (size_t)pl.n_rows * 256;   // device scalar t (solves beyond kMaxTembEvals): the spare row after the silu rows
-  const bool pre = n_evals <= kMaxTembEvals;
-  float* mod_all = nullptr;
-  if (pre) {
-    // the list of times sits at the head of the trunk's residual buffer: the embedding launch below has read it before the first trunk
-    // launch of this call overwrites it (stream order)
-    float* tlist = w.h;
-    for (int c0 = 0; c0 < n_evals; c0 += sde::kTChunk) {
-      sde::TChunk ch{};
-      const int m = std::min(sde::kTChunk, n_evals - c0);
-      for (int j = 0; j < m; ++j) ch.t[j] = tl[c0 + j];
-      sde::set_tlist_kernel<<<1, sde::kTChunk, 0, st>>>(tlist + c0, ch, m);
-    }
-    sde::t_embed_list_kernel<<<n_evals, 256, 0, st>>>(tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
-    LAUNCH_CHECK();
-    if (h->cond_all_on && n_evals > 1)
-      if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
-  }
+  if ((rc = s.prepare(tl))) return rc;
   sde::BlendArgs ba{};
   ba.v = w.v;
   ba.B = B;
   ba.e = e_row;
   ba.P = pl.P;
   ba.direct = pl.direct ? 1 : 0;
-  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) ba.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
+  fill_pass_scale(ba.scale, pl.P, pl.scale);
   ba.g = sde::NoiseGeom{seed, cell_offset, cells_total, 0u};
   int e_idx = 0;
   // one evaluation at zin, then out = a_x zin + a_v r (+ a_w w of step `step` when a_w != 0)
   auto eval = [&](const float* zin, float* out, float a_x, float a_v, float a_w, int step, float* traj_out) -> int {
-    const int e = e_idx++;
-    Ws we = w;
-    if (mod_all) we.mod = mod_all + (size_t)e * pl.n_rows * h->mod_w;
-    else {
-      if (!pre) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tl[e]);
-      int rc2 = cfg_cond(h, pl, tscal, 0, w, precision, st, pre ? w.temb + (size_t)e * 256 : nullptr);
-      if (rc2) return rc2;
-    }
-    int rc2 = trunk(h, zin, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, we.mod, w.ridx, w.h, w.v, precision, st);
+    int rc2 = s.eval(e_idx++, zin, w.v);
     if (rc2) return rc2;
     ba.x = zin;
     ba.out = out;
@@ -1257,7 +1158,7 @@ extern "C" int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ul
     *c_x = -D / om;
   };
   for (int i = 0; i < n_steps; ++i) {
-    const float t = linspace0(i, num_steps, t1);
+    const float t = grid::linspace(i, num_steps, 0.f, t1);
     const float a_w = (float)sqrt(2.0 * sde_diffusion(diffusion_form, diffusion_norm, t) * (double)dt);
     float* tr = traj ? traj + (size_t)i * n : nullptr;
     double c_v, c_x;
@@ -1328,11 +1229,6 @@ __global__ __launch_bounds__(256) void cfg_blend_drift_kernel(const DriftArgs a)
     zp[q] = zp[q] + f * a.h;
   }
 }
-// torch.linspace(t0, t1, steps) in fp32: linspace0's symmetric fill between any two end points
-float linspace_ab(int idx, int steps, float t0, float t1) {
-  const float step = (t1 - t0) / (float)(steps - 1);
-  return (idx < steps / 2) ? t0 + step * (float)idx : t1 - step * (float)(steps - idx - 1);
-}
 }  // namespace
 
 extern "C" int scldm_sample_ode_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B,
@@ -1350,88 +1246,40 @@ extern "C" int scldm_sample_ode_transport(scldm_dit* h, float* z, const int64_t*
   if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
   if (!(tr->sample_eps > 0.f))
     return fail(SCLDM_ERR_SHAPE, "a noise / score model needs sample_eps > 0: its drift is singular at t = 0 (alpha'/alpha) and at t = 1 (noise: 1 / sigma)");
-  CfgPlan pl;
-  if ((rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0))) return rc;
-  hipStream_t st = (hipStream_t)stream_;
-  Ws w = carve(h, ws_, pl.n_fwd, pl.n_rows, 2 * B);
+  FusedSolve s;
+  if ((rc = s.plan(h, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, precision, ws_, stream_))) return rc;
   const int e_row = 16 * h->cfg.n_embed_input;
-  const size_t n = (size_t)2 * B * e_row;
-  if (e_row % 4 || n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state rows must be a multiple of 4 elements, at most 2^33 elements in all");
+  if (e_row % 4 || s.n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state rows must be a multiple of 4 elements, at most 2^33 elements in all");
   const bool heun = method == SCLDM_METHOD_HEUN;
-  const int steps = n_steps + 1, n_evals = (heun ? 2 : 1) * n_steps;
   double td0, td1;
   tpath::transport_interval(tr, true, &td0, &td1);
   const float ta = (float)td0, tb = (float)td1;
-  std::vector<float> tl;
-  tl.reserve(n_evals);
-  for (int i = 0; i < n_steps; ++i) {
-    tl.push_back(linspace_ab(i, steps, ta, tb));
-    if (heun) tl.push_back(linspace_ab(i + 1, steps, ta, tb));
-  }
-  fill_cfg_row_index_kernel<<<cdiv(pl.n_fwd, 256), 256, 0, st>>>(w.ridx, cell_row, 2 * B, 1, B, pl.U, pl.P, nullptr, pl.direct);
-  LAUNCH_CHECK();
-  float* tscal = w.silu + (size_t)pl.n_rows * 256;   // device scalar t (solves beyond kMaxTembEvals): the spare row after the silu rows
-  const bool pre = n_evals <= kMaxTembEvals;
-  float* mod_all = nullptr;
-  if (pre) {
-    float* tlist = w.h;   // (read by the embedding launch before the first trunk launch overwrites it: stream order, as scldm_sample_sde)
-    for (int c0 = 0; c0 < n_evals; c0 += sde::kTChunk) {
-      sde::TChunk ch{};
-      const int m = std::min(sde::kTChunk, n_evals - c0);
-      for (int j = 0; j < m; ++j) ch.t[j] = tl[c0 + j];
-      sde::set_tlist_kernel<<<1, sde::kTChunk, 0, st>>>(tlist + c0, ch, m);
-    }
-    sde::t_embed_list_kernel<<<n_evals, 256, 0, st>>>(tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
-    LAUNCH_CHECK();
-    if (h->cond_all_on && n_evals > 1)
-      if ((rc = cond_all_prepare(h, pl, w.temb, n_evals, precision, st, &mod_all))) return rc;
-  }
+  const std::vector<float> tl = grid::eval_times(n_steps, ta, tb, heun ? grid::kNext : grid::kNone);
+  if ((rc = s.prepare(tl))) return rc;
   DriftArgs da{};
-  da.v = w.v;
+  da.v = s.w.v;
   da.B = B;
   da.e = e_row;
-  da.P = pl.P;
-  da.direct = pl.direct ? 1 : 0;
-  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) da.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
-  int e_idx = 0;
-  // one evaluation at zin: f_out = a zin + b m (when given), euler_z += hs f (when given)
-  auto eval = [&](const float* zin, float* f_out, float* euler_z, float hs) -> int {
-    const int e = e_idx++;
-    Ws we = w;
-    if (mod_all) we.mod = mod_all + (size_t)e * pl.n_rows * h->mod_w;
-    else {
-      if (!pre) set_scalar_kernel<<<1, 1, 0, st>>>(tscal, tl[e]);
-      int rc2 = cfg_cond(h, pl, tscal, 0, w, precision, st, pre ? w.temb + (size_t)e * 256 : nullptr);
-      if (rc2) return rc2;
-    }
-    int rc2 = trunk(h, zin, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, we.mod, w.ridx, w.h, w.v, precision, st);
+  da.P = s.pl.P;
+  da.direct = s.pl.direct ? 1 : 0;
+  fill_pass_scale(da.scale, s.pl.P, s.pl.scale);
+  // one evaluation at zin: the Euler step z += hs f (euler_z given), or f_out = a zin + b m
+  auto eval = [&](int e, const float* zin, float* f_out, float* euler_z, float hs) -> int {
+    int rc2 = s.eval(e, zin, s.w.v);
     if (rc2) return rc2;
     scldm_transport_coef k;
     tpath::transport_coef(tr->path, tr->model, tr->weight, (double)tl[e], &k);
     da.x = zin;
-    da.f = f_out;
+    da.f = euler_z ? nullptr : f_out;
     da.z = euler_z;
     da.a = (float)k.a;
     da.b = (float)k.b;
     da.h = hs;
-    cfg_blend_drift_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(da);
+    cfg_blend_drift_kernel<<<cdiv(s.n / 4, 256), 256, 0, s.st>>>(da);
     LAUNCH_CHECK();
     return SCLDM_OK;
   };
-  for (int i = 0; i < n_steps; ++i) {
-    const float t0 = linspace_ab(i, steps, ta, tb), t1 = linspace_ab(i + 1, steps, ta, tb);
-    const float hs = t1 - t0;
-    if (!heun) {
-      if ((rc = eval(z, nullptr, z, hs))) return rc;
-    } else {
-      if ((rc = eval(z, w.dz, nullptr, 0.f))) return rc;
-      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.ztmp, hs, n);
-      if ((rc = eval(w.ztmp, w.k2, nullptr, 0.f))) return rc;
-      heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.k2, 0.5f * hs, n);
-    }
-    LAUNCH_CHECK();
-  }
-  return SCLDM_OK;
+  return s.step_loop(n_steps, ta, tb, heun, z, eval);
 }
 
 extern "C" void scldm_dit_block_timing_enable(scldm_dit* h, int enable) {

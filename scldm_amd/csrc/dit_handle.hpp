@@ -56,17 +56,12 @@ struct scldm_dit {
   hipEvent_t fork_ev, join_ev[3];
   hipEvent_t wg_ev[2] = {nullptr, nullptr};   // fused training, small batches: layer l's weight-gradient launches (side stream) are done with operand-pair set l & 1
   hipEvent_t bwd_pack_ev = nullptr;   // the training step's backward weight stream is packed (second pack launch of fused::prepare)
-  // fused sampler: the conditioning of evaluation e + 1 (timestep rows + adaLN projection: independent of the state z) runs on its own
-  // stream beside the trunk of evaluation e, into the other of two buffer sets (scldm_sample_ode)
-  hipStream_t cond_stream = nullptr;
-  hipEvent_t ev_cond[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_ready = nullptr;
   // round 6: the adaLN vectors of EVERY evaluation of a fixed-grid solve in one batched pass ahead of the loop (they depend on t and the
   // labels only): SCLDM_COND_ALL=0 switches it off; cond_all = [mod | silu | split rows] for n_evals x n_rows rows, grown on demand
   bool cond_all_on = true;
   void* cond_all = nullptr;
   size_t cond_all_bytes = 0;
   double* rk_host = nullptr;   // pinned host slot the adaptive solve reads its error ratio through (allocated once, at create)
-  bool cond_ahead = false;  // SCLDM_COND_AHEAD=1: opt-in (measured +0.5 % at 1 024 joint-conditioned cells, -0.8 % at 512, -0.2 % at 4 096: off)
   int force_ft, force_x3_ft, force_x3_ntt;
   bool small_ntt = true;   // 32-token tiles for launches of at most 256 of them (SCLDM_SMALL_NTT=0: off)
   unsigned long long* dbg;  // device buffer for phase stamps (debug builds)

@@ -3,7 +3,7 @@
 // scldm_logp_ode_dopri5); this file is the problem that loop drives.  The state kernels are dopri5_fused.hpp.
 //
 // One attempted step = one batched conditioning pass over its six new evaluation times (time list -> t_embed_list_kernel ->
-// cond_rows_kernel over (rows, 6) -> one adaLN projection over 6 x rows rows: cond_all_prepare's scheme with n_evals = 6), the first
+// cond_rows_kernel over (rows, 6) -> one adaLN projection over 6 x rows rows: api.hip's cond_batch with n_evals = 6), the first
 // stage point (combine_kernel), six trunks each followed by ONE state kernel, error_final_kernel, and an 8-byte read of the error ratio.
 
 struct D5Ws {
@@ -94,7 +94,7 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
   geom.e = e_row;
   geom.P = pl.P;
   geom.direct = pl.direct ? 1 : 0;
-  for (int p = 0; p < SCLDM_MAX_CLASSES; ++p) geom.scale[p] = p < pl.P ? pl.scale[p] : 0.f;
+  fill_pass_scale(geom.scale, pl.P, pl.scale);
 
   float* K[7];
   for (int i = 0; i < 7; ++i) K[i] = w.k[i];
@@ -107,10 +107,7 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
     for (int j = 0; j < cnt; ++j) tt.t[j] = times[j];
     d5::set_times_kernel<<<1, 64, 0, st>>>(w.tlist, tt, cnt);
     sde::t_embed_list_kernel<<<cnt, 256, 0, st>>>(w.tlist, h->w0t, h->b0, h->w2t, h->b2, w.temb);
-    CondRowsArgs ca = cond_rows_args(h, pl, w.temb, w.silu, nullptr);
-    cond_rows_kernel<<<dim3(pl.n_rows, cnt), 256, 0, st>>>(ca);
-    LAUNCH_CHECK();
-    return launch_adaln(h, w.silu, w.mod, cnt * pl.n_rows, st, nullptr, precision, w.asplit);
+    return cond_batch(h, pl, w.temb, cnt, w.silu, w.mod, w.asplit, precision, st);
   };
   auto run_trunk = [&](const float* x, int slot) -> int {
     return trunk(h, x, 2 * B, B, pl.direct ? 2 * B : pl.n_fwd, w.mod + (size_t)slot * pl.n_rows * h->mod_w, w.ridx, w.h, w.v, precision, st);
@@ -173,7 +170,7 @@ static int d5_solve(scldm_dit* h, float* z, const int64_t* const* ulabels, int n
     if ((rc = norm(K[1], K[0], w.red))) return rc;
     return dopri5_read_back(h->rk_host, w.red + 1022, 1, ms, st);
   };
-  auto save_time = [&](int si) { return (double)(save_times ? save_times[si] : linspace01(si, num_save)); };
+  auto save_time = [&](int si) { return (double)(save_times ? save_times[si] : grid::linspace(si, num_save, 0.f, 1.f)); };
   auto attempt = [&](const d5::Step& step, double* ms) -> int {
     const scldm_dopri5_plan& plan = step.plan;
     int rc;

@@ -242,42 +242,10 @@ int infer_trunk(scldm_dit* h, const scldm_dit_weights* w, const float* x, int n_
   return linear_fwd(st, s.h, kD, w->fin_w, (int)T, din, kD, w->fin_b, out, din, k);
 }
 
-// ---- one CFG evaluation ---------------------------------------------------------------------------------------------------------------
-struct InferPlan {
-  int B, P, U, uncond_rows, n_fwd, n_rows;
-  const int64_t* const* ulabels;
-  const int32_t* cell_row;
-  uint32_t mask[SCLDM_MAX_CLASSES];
-  float scale[SCLDM_MAX_CLASSES];
-};
-int make_infer_plan(const scldm_dit* h, InferPlan& pl, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
-                    const uint32_t* pass_mask, const float* pass_scale, int t_stride) {
-  if (B <= 0) return fail(SCLDM_ERR_SHAPE, "B must be positive");
-  if (!h->cfg.has_null_row && h->cfg.n_classes > 0)
-    return fail(SCLDM_ERR_SHAPE, "classifier-free guidance needs the null rows of the class tables (model built with cfg_dropout_prob == 0)");
-  if (n_pass < 0 || n_pass > SCLDM_MAX_CLASSES) return fail(SCLDM_ERR_SHAPE, "n_pass out of range");
-  if (n_pass > 0 && (!ulabels || !pass_mask || !pass_scale || n_urows <= 0)) return fail(SCLDM_ERR_SHAPE, "conditional passes need labels/masks/scales");
-  if (n_pass > 0 && !cell_row && n_urows != B) return fail(SCLDM_ERR_SHAPE, "cell_row is NULL but n_urows (%d) != B (%d)", n_urows, B);
-  if (t_stride == 1 && n_pass > 0 && (cell_row || n_urows != B))
-    return fail(SCLDM_ERR_SHAPE, "per-sample t (t_stride=1) requires per-cell label rows (n_urows == B, cell_row NULL)");
-  pl.B = B;
-  pl.P = n_pass;
-  pl.U = n_pass > 0 ? n_urows : 0;
-  pl.uncond_rows = t_stride == 0 ? 1 : 2 * B;
-  pl.n_fwd = 2 * B + n_pass * B;
-  pl.n_rows = pl.uncond_rows + pl.P * pl.U;
-  pl.ulabels = ulabels;
-  pl.cell_row = cell_row;
-  for (int p = 0; p < n_pass; ++p) {
-    pl.mask[p] = pass_mask[p];
-    pl.scale[p] = pass_scale[p];
-  }
-  return SCLDM_OK;
-}
-
+// ---- one CFG evaluation (CfgPlan, make_plan: cfg_plan.hpp; this path always blends, whatever the plan's `direct` says) --------------------
 // the conditioning rows of one evaluation from its timestep embedding(s): row(s) of the unconditional pass (every class null), then
 // U rows per conditional pass.  temb_stride 0: one embedding for all rows; D: row i of the state's 2B (conditional rows: the second half)
-int infer_cfg_cond(scldm_dit* h, const scldm_dit_weights* w, const InferPlan& pl, const float* temb, long temb_stride, int precision,
+int infer_cfg_cond(scldm_dit* h, const scldm_dit_weights* w, const CfgPlan& pl, const float* temb, long temb_stride, int precision,
                    const InferWs& s, Scratch& k, hipStream_t st) {
   TRY(infer_cond_sum(h, w, temb, temb_stride, nullptr, 0u, 0, pl.uncond_rows, s, st));
   for (int p = 0; p < pl.P; ++p)
@@ -285,16 +253,10 @@ int infer_cfg_cond(scldm_dit* h, const scldm_dit_weights* w, const InferPlan& pl
   return infer_adaln(h, w, pl.n_rows, precision, s, s.mod, k, st);
 }
 // the state-dependent part: the trunk over every sample-forward, then the blend (with the caller's Euler step when euler_z is given)
-int infer_cfg_trunk(scldm_dit* h, const scldm_dit_weights* w, const InferPlan& pl, const float* z, float* dz, int precision, const InferWs& s,
+int infer_cfg_trunk(scldm_dit* h, const scldm_dit_weights* w, const CfgPlan& pl, const float* z, float* dz, int precision, const InferWs& s,
                     hipStream_t st, float* euler_z = nullptr, float euler_h = 0.f) {
   TRY(infer_trunk(h, w, z, 2 * pl.B, pl.B, pl.n_fwd, s.mod, s.ridx, s.v, precision, s, st));
   return scldm_cfg_blend(s.v, dz, pl.B, kS * h->cfg.n_embed_input, pl.P, pl.scale, euler_z, euler_h, st);
-}
-
-// torch.linspace(0, 1, steps) in fp32 (integrators.py:95): symmetric fill from both ends (grid_times_kernel of infer_wide.hip computes the same values)
-float infer_linspace01(int idx, int steps) {
-  const float step = 1.0f / (float)(steps - 1);
-  return (idx < steps / 2) ? step * (float)idx : 1.0f - step * (float)(steps - idx - 1);
 }
 
 }  // namespace
@@ -345,8 +307,8 @@ extern "C" int scldm_dit_infer_forward_cfg(scldm_dit* h, const scldm_dit_weights
   TRY(check_infer(h, w, B > 0 ? 2 * B + std::max(n_pass, 0) * B : 1, &precision, ws, "scldm_dit_forward_cfg"));
   if (!x || !t || !out) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
   if (t_stride != 0 && t_stride != 1) return fail(SCLDM_ERR_SHAPE, "t_stride must be 0 (one scalar t) or 1 (one t per sample)");
-  InferPlan pl;
-  TRY(make_infer_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, t_stride));
+  CfgPlan pl;
+  TRY(make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, t_stride));
   hipStream_t st = (hipStream_t)stream_;
   const InferWs s = carve_infer(h, ws, pl.n_fwd, pl.n_rows, 0);
   Scratch k = split_k_scratch(s);
@@ -364,8 +326,8 @@ extern "C" int scldm_dit_infer_sample_ode(scldm_dit* h, const scldm_dit_weights*
   if (!z) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
   if (n_steps < 1) return fail(SCLDM_ERR_SHAPE, "n_steps must be >= 1");
   if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
-  InferPlan pl;
-  TRY(make_infer_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0));
+  CfgPlan pl;
+  TRY(make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0));
   hipStream_t st = (hipStream_t)stream_;
   const InferWs s = carve_infer(h, ws, pl.n_fwd, pl.n_rows, 2 * B);
   Scratch k = split_k_scratch(s);
@@ -376,10 +338,10 @@ extern "C" int scldm_dit_infer_sample_ode(scldm_dit* h, const scldm_dit_weights*
   const int steps = n_steps + 1, kD = h->cfg.n_embed;
   const bool heun = method == SCLDM_METHOD_HEUN;
   const int n_evals = heun ? 2 * n_steps : n_steps;
-  int e_idx = 0;
   // one evaluation; the timestep embeddings of kInferEvalChunk evaluations at a time come from one pass of the timestep MLP
-  auto eval = [&](const float* zin, float* dz, float* euler_z, float euler_h) -> int {
-    const int e = e_idx++, j = e % kInferEvalChunk;
+  // (grid_times_kernel of infer_wide.hip computes grid::linspace's values)
+  auto eval = [&](int e, const float* zin, float* dz, float* euler_z, float euler_h) -> int {
+    const int j = e % kInferEvalChunk;
     if (j == 0) {
       const int m = std::min(kInferEvalChunk, n_evals - e);
       TRY(scldm_infer_grid_times(st, s.tgrid, steps, heun ? 1 : 0, e, m));
@@ -388,17 +350,8 @@ extern "C" int scldm_dit_infer_sample_ode(scldm_dit* h, const scldm_dit_weights*
     TRY(infer_cfg_cond(h, w, pl, s.temb + (size_t)j * kD, 0, precision, s, k, st));
     return infer_cfg_trunk(h, w, pl, zin, dz, precision, s, st, euler_z, euler_h);
   };
-  for (int i = 0; i < n_steps; ++i) {
-    const float t0 = infer_linspace01(i, steps), t1 = infer_linspace01(i + 1, steps);
-    const float hs = t1 - t0;
-    if (!heun) {
-      TRY(eval(z, s.dz, z, hs));
-    } else {
-      TRY(eval(z, s.dz, nullptr, 0.f));
-      TRY(scldm_ode_axpy(z, s.dz, s.ztmp, hs, n, st));
-      TRY(eval(s.ztmp, s.k2, nullptr, 0.f));
-      TRY(scldm_ode_heun(z, s.dz, s.k2, 0.5f * hs, n, st));
-    }
-  }
-  return SCLDM_OK;
+  return grid::euler_heun(
+      n_steps, 0.f, 1.f, heun, grid::Buffers{z, s.dz, s.k2, s.ztmp}, eval,
+      [&](const float* x, const float* kk, float* out, float hs) { return scldm_ode_axpy(x, kk, out, hs, n, st); },
+      [&](float* x, const float* k1, const float* k2, float half_hs) { return scldm_ode_heun(x, k1, k2, half_hs, n, st); });
 }

@@ -6,7 +6,9 @@
 #include <cstdint>
 
 #include "api_common.hpp"
+#include "cfg_plan.hpp"
 #include "dit_handle.hpp"
+#include "fixed_grid.hpp"
 #include "logp.hpp"
 
 using namespace scldm;
@@ -43,12 +45,6 @@ LogpWs carve_logp(const scldm_dit* h, int B, int n_pass, int precision, void* ba
   return w;
 }
 
-// torch.linspace(0, 1, steps) in fp32: symmetric fill from both ends (the grid of scldm_sample_ode)
-float linspace01(int idx, int steps) {
-  const float step = 1.0f / (float)(steps - 1);
-  return (idx < steps / 2) ? step * (float)idx : 1.0f - step * (float)(steps - idx - 1);
-}
-
 }  // namespace
 
 extern "C" size_t scldm_logp_workspace_bytes(const scldm_dit* h, int B, int n_pass, int precision) {
@@ -78,14 +74,11 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
   if (!h || !w || !z || !logp_out || !saved || !ws_) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode: null pointer argument");
   if (n_steps < 1) return fail(SCLDM_ERR_SHAPE, "n_steps must be >= 1");
   if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
-  if (B < 1) return fail(SCLDM_ERR_SHAPE, "B must be positive");
   if (cell_offset < 0 || cells_total < cell_offset + B) return fail(SCLDM_ERR_SHAPE, "cells_total (%lld) < cell_offset (%lld) + B (%d)", cells_total, cell_offset, B);
-  if (n_pass < 0 || n_pass > SCLDM_MAX_CLASSES) return fail(SCLDM_ERR_SHAPE, "n_pass out of range");
-  if (n_pass > 0 && (!ulabels || !pass_mask || !pass_scale || n_urows <= 0)) return fail(SCLDM_ERR_SHAPE, "conditional passes need labels/masks/scales");
-  if (n_pass > 0 && !cell_row && n_urows != B) return fail(SCLDM_ERR_SHAPE, "cell_row is NULL but n_urows (%d) != B (%d)", n_urows, B);
+  CfgPlan pl;   // (the argument checks of every CFG entry; the solve blends in its own kernels and never takes the direct route)
+  int rc = make_plan(h, pl, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, 0);
+  if (rc) return rc;
   const scldm_dit_config& c = h->cfg;
-  if (!c.has_null_row && c.n_classes > 0)
-    return fail(SCLDM_ERR_SHAPE, "classifier-free guidance needs the null rows of the class tables (model built with cfg_dropout_prob == 0)");
   if (((uintptr_t)z & 15) || ((uintptr_t)probe & 15)) return fail(SCLDM_ERR_SHAPE, "z and probe must be 16-byte aligned");
   const int e = 16 * c.n_embed_input;
   const long long N = (long long)(2 + n_pass) * B;
@@ -151,9 +144,8 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
   };
   const int steps = n_steps + 1;
   for (int i = 0; i < n_steps; ++i) {
-    const float s0 = linspace01(i, steps), s1 = linspace01(i + 1, steps);
+    const float s0 = grid::linspace(i, steps, 0.f, 1.f), s1 = grid::linspace(i + 1, steps, 0.f, 1.f);
     const float hs = s1 - s0;
-    int rc;
     if (method == SCLDM_METHOD_EULER) {
       if ((rc = eval(z, s0, logp::kEuler, hs))) return rc;
     } else {

@@ -6,7 +6,9 @@
 #include <atomic>
 
 #include "api_common.hpp"
+#include "cfg_plan.hpp"
 #include "dit_handle.hpp"
+#include "fixed_grid.hpp"
 #include "train.hpp"
 #include "bgemm.hpp"
 #include "bgemm8.hpp"

@@ -545,6 +545,23 @@ def test_fused_sampler_vs_oracle(name, method, steps, precision, tol):
         assert max_abs_rel(traj[-1].cpu(), out.cpu()) < 1e-5
 
 
+def test_fused_sampler_beyond_the_pre_embedded_limit_vs_float64_oracle():
+    """The step-by-step conditioning route of the fused fixed-grid solves (a device scalar t, embedded per evaluation), taken by solves
+    with more than 4 096 evaluations: one cell, one conditional pass at guidance 1.5, Euler over 4 098 grid points = 4 097 evaluations,
+    fp32, against the float64 end state of the oracle chain (sample_ode_fixed over dit_forward_with_cfg).  That chain takes about a
+    minute on the CPU, so its inputs and end state are a fixture (tests/golden/make_golden_long_euler.py; the fp32 oracle chain ends
+    7e-6 from the float64 one, 14 times inside the gate).  scldm_sample_ode, scldm_sample_sde and scldm_sample_ode_transport share the
+    route (api.hip: FusedSolve)."""
+    g, m, cfg, sd = build("dit_base", "fp32")
+    long = load_golden("long_euler_4097")
+    name, steps = str(long["label_name"]), int(long["grid_points"])
+    assert steps - 1 == 4097 and long["end64"].dtype == np.float64
+    z2 = cu(np.concatenate([long["z0"], long["z0"]]))
+    cond2 = {name: cu(np.concatenate([long["label"], long["label"]]))}
+    out = m.sample_ode_cfg(z2, cond2, {name: float(long["scale"])}, steps, "euler")
+    check_err(out.cpu(), torch.from_numpy(long["end64"]), TOL_FP32, "fused sampler dit_base euler x4097 [fp32] vs float64 oracle", FLOOR_TOL["fp32"])
+
+
 def test_bitwise_repeatability_and_batch_permutation_at_full_size():
     """Size-independent properties at the benchmark batch (3 x 4096 sample-forwards): identical bytes on repeat,
     and permuting the cells permutes the outputs exactly (cells are independent; cross-sample MFMA blocks are masked)."""
