@@ -15,7 +15,10 @@ namespace scldm {
 //   units 48-63: c_proj rows w*64 + ft*32 + r                                      attn.c_proj.weight (256,256)
 //   chunk c, units 0-15: tile rows 0-15 = w1[hid], rows 16-31 = w2[hid], hid = c*128 + w*32 + ft*16 + (r&15)
 //   chunk c, units 16-23: mlp.c_proj rows w*64 + ft*32 + r, k = hidden index c*128 + ks*16 + ...
-// Hidden indices >= H are zero (exact padding of 684 -> 768).
+// Hidden indices >= H are zero: exact padding of H to the stream's chunk layout (scldm_dit_create) - whole 128-unit chunks for FT=1,
+// ceil(H / 64) * 64 as whole chunks plus at most one trailing 64-unit half chunk for FT=2 (684 -> 768 / 704; 768 -> 768 both, no padded
+// unit; 720 -> 768: the padded units sit in a WHOLE chunk of the FT=2 stream too).  Any H >= 1 is packed; the kernels walk n_chunks
+// chunks and the half chunk.
 // m16 (FT=2, 16-bit policies; dit_forward.hpp: gemm_pass_tile16): the W12 units of a chunk (and of the trailing half chunk) are
 // 16-row x 32-k fragments instead - unit vv = k-step (vv & 7) of 32 of tile vv >> 3, fragment 0 = w1[hid], fragment 1 = w2[hid],
 // hid = c*128 + (w*2 + tile)*16 + (l&15), k = 32*(vv & 7) + (l>>4)*8 + j.  Same units, same bytes.

@@ -572,6 +572,19 @@ class DiT(nn.Module):
         training kernels, also used for their inference."""
         return self.n_embed == 256 and self.n_head == 8 and self.seq_len == 16 and self.n_embed_input <= 32
 
+    @property
+    def hidden_dim(self) -> int:
+        """SwiGLU hidden width (684 for multiple_of=4 at n_embed 256)."""
+        return swiglu_hidden(self.n_embed, self.multiple_of)
+
+    @property
+    def fused_train_shape(self) -> bool:
+        """True when training steps in bf16 / fp16 run on the fused training route (train_fused.hip): a fused shape whose hidden width
+        is at most 768 (the route's operand arrays are padded to three 256-unit chunks) and a multiple of 4 (every training route needs
+        that).  The fused INFERENCE kernels take any hidden width; a fused shape with a wider MLP trains, and computes input_vjp and the
+        likelihood's VJP, on the generic GEMM-based route (fp16 on its exact-fp32 GEMMs)."""
+        return self.fused_shape and self.hidden_dim <= 768 and self.hidden_dim % 4 == 0
+
     def _generic_forward(self, x: torch.Tensor, t: torch.Tensor, labels) -> torch.Tensor:
         """DiT.forward through scldm_dit_train_forward without keeping the activation record (inference on non-fused shapes)."""
         L, h = self._native_handle()

@@ -348,7 +348,8 @@ class FusedTrainStep:
     replayed - per replay the host stages 16 bytes (learning rate, weight decay, EMA action) and copies the batch.  Gradients live in
     one flat fp32 buffer (`.grad` of every parameter is a view), so a data-parallel group reduces it in place between backward and
     optimizer (`group=`; that variant is not graphed).  `grad_clip_norm=` = the trainer's `gradient_clip_val` (global-norm clipping inside
-    the optimizer's launch; `optimizer.last_grad_norm` is the step's norm).  Requires the fused training route (base DiT shape, precision bf16 | fp16)
+    the optimizer's launch; `optimizer.last_grad_norm` is the step's norm).  Requires the fused training route (base DiT shape with a SwiGLU hidden width <= 768
+    that is a multiple of 4 - `DiT.fused_train_shape` -, precision bf16 | fp16; anything else is refused at construction)
     and `scldm_amd.optim.AdamW`.  `transport`: the Linear path with velocity prediction (ldm_base.yaml:30-35) runs `scldm_dit_train_step`; the
     GVP path, noise / score prediction and the loss weights run `scldm_dit_train_step_transport` (same forward / backward / optimizer calls,
     the batch preparation and the loss kernel take the path), graphed alike.
@@ -389,6 +390,9 @@ class FusedTrainStep:
         prec = dit._prec()
         if prec not in (_lib.PRECISIONS["bf16"], _lib.PRECISIONS["fp16"]) or not dit.fused_shape:
             raise NotImplementedError("FusedTrainStep serves the fused training route: the reference's DiT shape at precision 'bf16' or 'fp16'")
+        if not dit.fused_train_shape:
+            raise NotImplementedError(f"FusedTrainStep serves the fused training route: it needs a SwiGLU hidden width <= 768 that is a multiple "
+                                      f"of 4, got hidden width {dit.hidden_dim} (multiple_of={dit.multiple_of}); train this model with train_step")
         self.prec = prec
         n, e = self.n, dit.seq_len * dit.n_embed_input
         f32 = dict(dtype=torch.float32, device=dev)

@@ -45,6 +45,39 @@ def test_forward_with_cfg_matches_reference(name, tag):
     assert max_abs_rel(y, g[f"cfg_out_{tag}"]) < TOL
 
 
+# SwiGLU hidden widths other than the 684 of multiple_of=4 (tests/golden/make_golden_hidden.py): name -> (multiple_of, hidden width)
+HIDDEN_CASES = {"dit_h768": (256, 768), "dit_h704": (64, 704), "dit_h700": (100, 700), "dit_h832": (832, 832), "dit_h682": (2, 682)}
+
+
+@pytest.mark.parametrize("name", sorted(HIDDEN_CASES))
+def test_other_hidden_widths_match_reference(name):
+    """Forward, the SwiGLU output of block 0 and the CFG forward at the reference's own hidden width for this multiple_of: pins
+    oracle.dit.mlp_hidden_dim (and, below, scldm_amd's swiglu_hidden) to the reference module's w1 row count."""
+    from scldm_amd.layers import swiglu_hidden
+    g, cfg, sd = setup(name)
+    multiple_of, hidden = HIDDEN_CASES[name]
+    assert cfg.multiple_of == multiple_of and int(g["hidden"]) == hidden
+    assert golden_json(g, "shapes_json")["blocks.0.mlp.w1.weight"] == [hidden, 256]           # the reference module's own shape
+    assert mlp_hidden_dim(256, multiple_of) == hidden == swiglu_hidden(256, multiple_of)
+    assert tuple(sd["blocks.1.mlp.c_proj.weight"].shape) == (256, hidden)
+    cond = {"clusters": torch.from_numpy(g["fwd_label_clusters"])}
+    taps = {}
+    y = dit_forward(sd, cfg, torch.from_numpy(g["fwd_x"]), torch.from_numpy(g["fwd_t"]), cond, taps=taps)
+    assert max_abs_rel(y, g["fwd_out"]) < TOL
+    assert max_abs_rel(taps["block0.mlp_out"], g["tap_block0.mlp_out"]) < TOL
+    cond2 = {"clusters": torch.from_numpy(g["cfg_label_clusters"])}
+    y2 = dit_forward_with_cfg(sd, cfg, torch.from_numpy(g["cfg_x"]), torch.from_numpy(g["cfg_t"]), cond2, golden_json(g, "cfg_scales_s2"))
+    assert max_abs_rel(y2, g["cfg_out_s2"]) < TOL
+
+
+def test_oracle_and_package_agree_on_the_hidden_width():
+    from scldm_amd.layers import swiglu_hidden
+    for n_embed in (256, 512, 1024):
+        for multiple_of in (1, 2, 4, 5, 7, 64, 100, 256, 683, 832, 1024):
+            h = mlp_hidden_dim(n_embed, multiple_of)
+            assert h == swiglu_hidden(n_embed, multiple_of) and h % multiple_of == 0 and 0 <= h - int(8 * n_embed / 3) < multiple_of
+
+
 def test_fp64_oracle_is_closer_than_tolerance():
     g, cfg, sd = setup("dit_base", torch.float64)
     cond = {k: torch.from_numpy(g[f"fwd_label_{k}"]) for k in golden_json(g, "fwd_classes")}
