@@ -980,6 +980,61 @@ int scldm_gaussian_recon_loss(const float* counts, const float* mu, int B, int G
 int scldm_gaussian_recon_loss_bwd(const float* counts, const float* mu, const float* gout_rows, int B, int G, float target_sum,
                                   float* dmu, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ScviVAE: the scVI-style baseline of the reference (src/scldm/vae.py:90-128; EncoderScvi / DecoderScvi nnets.py:19-73,
+ * GaussianLinearLayer / NegativeBinomialLinearLayer stochastic_layers.py:38-70,123-158).  Inference (eval mode), exact fp32:
+ *   h = x = log1p(counts);  per layer  x = SiLU(BatchNorm1d_eval(Linear(x)))
+ *   loc = Linear_loc(h),  scale = exp(hardtanh(Linear_scale(h), -7, 5)),  z = loc + eps scale
+ *   g = decoder MLP(z);  mu = library_size softmax_G(Linear_mu(g));  theta = softplus(theta_param) (shared, (G)) or
+ *   softplus(Linear_theta(g)) (per cell, (B, G); torch's threshold-20 softplus).
+ * All weights are read where they live, in torch's Linear layout (out, in).  Only the BatchNorm affine and the Linear bias of every
+ * MLP layer are packed, into y = s x + c per column (s = gamma / sqrt(running_var + eps), c = beta + (b - running_mean) s), by ONE
+ * single-workgroup launch that first fingerprints those five vectors of every layer and re-packs only if they moved: scldm_scvi_pack
+ * runs it unconditionally, every encode / decode / forward runs it first, so an in-place update of a parameter or a running statistic
+ * is picked up in stream order without a host read.
+ * Every product accumulates each output element in one fixed k order (a first layer with K > 1024 is split over K in chunks of 1024 -
+ * a function of K alone - and a second launch sums the chunks in order); the softmax over genes merges per-tile (max, sum exp) pairs
+ * in tile order.  No float atomics: results are bit-equal run to run, and a row's results do not depend on the other rows of the batch.
+ * scldm_scvi_create allocates nothing on the device and needs none; the first scldm_scvi_pack of a handle allocates the packed
+ * vectors.  After it, pack / encode / decode / forward make kernel launches only and can be captured into a graph.
+ * SCLDM_ERR_SHAPE with a message and nothing launched: a NULL or misaligned pointer (floats 4 bytes, ws 256 bytes), a layer count
+ * below 1 (or above 8), a non-positive dimension or B, n_library != B.  SCLDM_ERR_STATE: encode / decode / forward before pack.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct scldm_scvi scldm_scvi;
+typedef struct {
+  const float* w;        /* Linear weight (n_hidden, in) */
+  const float* b;        /* Linear bias (n_hidden) */
+  const float* bn_w;     /* BatchNorm1d weight, bias, running_mean, running_var (n_hidden each) */
+  const float* bn_b;
+  const float* bn_mean;
+  const float* bn_var;
+} scldm_scvi_layer;
+typedef struct {
+  const scldm_scvi_layer* enc;   /* n_enc_layers entries; layer 0 has in = n_genes */
+  const scldm_scvi_layer* dec;   /* n_dec_layers entries; layer 0 has in = n_latent */
+  const float* loc_w;   const float* loc_b;     /* (n_latent, n_hidden), (n_latent) */
+  const float* scale_w; const float* scale_b;
+  const float* mu_w;    const float* mu_b;      /* (n_genes, n_hidden), (n_genes) */
+  const float* theta_w;                         /* shared theta: the parameter (n_genes); else Linear weight (n_genes, n_hidden) */
+  const float* theta_b;                         /* shared theta: ignored (may be NULL); else (n_genes) */
+} scldm_scvi_params;
+
+int scldm_scvi_create(int n_enc_layers, int n_dec_layers, int n_genes, int n_hidden, int n_latent, int shared_theta, float bn_eps,
+                      scldm_scvi** out);
+void scldm_scvi_destroy(scldm_scvi* h);
+int scldm_scvi_pack(scldm_scvi* h, const scldm_scvi_params* p, void* stream);
+size_t scldm_scvi_workspace_bytes(const scldm_scvi* h, int B);
+/* counts (B, n_genes) -> h (B, n_hidden), loc, scale (B, n_latent); with eps (B, n_latent) also z = loc + eps scale (z may be NULL
+ * when eps is). */
+int scldm_scvi_encode(scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z,
+                      void* ws, void* stream);
+/* z (B, n_latent), library_size (n_library = B) -> mu (B, n_genes), theta ((n_genes) shared | (B, n_genes)). */
+int scldm_scvi_decode(scldm_scvi* h, const float* z, const float* library_size, int n_library, int B, float* mu, float* theta, void* ws,
+                      void* stream);
+/* encode (eps required) followed by decode of its z, one fingerprint / pack launch in front. */
+int scldm_scvi_forward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps, float* hout,
+                       float* loc, float* scale, float* z, float* mu, float* theta, void* ws, void* stream);
+
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the
  * production library returns SCLDM_ERR_STATE. */

@@ -103,6 +103,17 @@ class TransportCoef(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("alpha", "d_alpha", "sigma", "d_sigma", "ratio", "dv", "a", "b", "c", "w")]
 
 
+class ScviLayer(C.Structure):
+    """scldm_scvi_layer (include/scldm_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w", "b", "bn_w", "bn_b", "bn_mean", "bn_var")]
+
+
+class ScviParams(C.Structure):
+    """scldm_scvi_params (include/scldm_hip.h)."""
+    _fields_ = [("enc", C.POINTER(ScviLayer)), ("dec", C.POINTER(ScviLayer))] + \
+               [(n, C.c_void_p) for n in ("loc_w", "loc_b", "scale_w", "scale_b", "mu_w", "mu_b", "theta_w", "theta_b")]
+
+
 ERR_SOLVER = -4   # SCLDM_ERR_SOLVER
 
 
@@ -313,6 +324,15 @@ def lib() -> C.CDLL:
     L.scldm_vae_train_gaussian_backward.argtypes = [C.c_void_p, C.POINTER(VaeWeights), C.POINTER(VaeWeights), C.c_void_p, C.c_void_p, C.c_int,
                                                     C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_scvi_create.argtypes = [C.c_int] * 6 + [C.c_float, C.POINTER(C.c_void_p)]
+    L.scldm_scvi_destroy.argtypes = [C.c_void_p]
+    L.scldm_scvi_destroy.restype = None
+    L.scldm_scvi_pack.argtypes = [C.c_void_p, C.POINTER(ScviParams), C.c_void_p]
+    L.scldm_scvi_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    L.scldm_scvi_workspace_bytes.restype = C.c_size_t
+    L.scldm_scvi_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.scldm_scvi_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.scldm_scvi_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
     _lib = L
     return L
 
@@ -335,7 +355,9 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dopri5_initial_h0", "scldm_dopri5_initial_step",
            "scldm_logp_ode_dopri5_workspace_bytes", "scldm_logp_ode_dopri5",
            "scldm_transport_coef_at", "scldm_sample_ode_transport", "scldm_fm_plan", "scldm_fm_wloss", "scldm_fm_wloss_bwd", "scldm_fm_prepare_transport", "scldm_fm_wloss_grad",
-           "scldm_dit_train_step_transport"]
+           "scldm_dit_train_step_transport",
+           "scldm_scvi_create", "scldm_scvi_destroy", "scldm_scvi_pack", "scldm_scvi_workspace_bytes", "scldm_scvi_encode", "scldm_scvi_decode",
+           "scldm_scvi_forward"]
 
 
 def check(rc: int, what: str) -> None:

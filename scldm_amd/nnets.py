@@ -92,6 +92,44 @@ class Decoder(nn.Module):
         raise RuntimeError("Decoder is fused into scldm_amd.vae.TransformerVAE.decode; call TransformerVAE.decode")
 
 
+def _scvi_mlp(n_in: int, n_hidden: int, n_layers: int, dropout: float) -> nn.Sequential:
+    """[Linear, BatchNorm1d, SiLU, Dropout] x n_layers: the module indices (4 i, 4 i + 1) are the reference's state_dict keys."""
+    if n_layers < 1:
+        raise ValueError(f"n_layers must be >= 1 (got {n_layers})")
+    layers = []
+    for i in range(n_layers):
+        layers.extend([nn.Linear(n_in if i == 0 else n_hidden, n_hidden), nn.BatchNorm1d(n_hidden), nn.SiLU(), nn.Dropout(dropout)])
+    return nn.Sequential(*layers)
+
+
+class EncoderScvi(nn.Module):
+    """scVI-style encoder MLP - parameter and buffer tree of scldm.nnets.EncoderScvi (nnets.py:19-45): log1p, then per layer
+    SiLU(BatchNorm1d(Linear(x))).  Its arithmetic runs inside scldm_amd.vae.ScviVAE (scldm_scvi_encode), in eval mode only."""
+
+    def __init__(self, n_genes: int, n_hidden: int, n_layers: int, dropout: float):
+        super().__init__()
+        self.n_genes, self.n_hidden, self.n_layers, self.dropout = n_genes, n_hidden, n_layers, dropout
+        self.encoder_mlp = _scvi_mlp(n_genes, n_hidden, n_layers, dropout)
+        self.latent_embedding = 0
+
+    def forward(self, x, genes=None):  # pragma: no cover - guard only
+        raise RuntimeError("EncoderScvi is fused into scldm_amd.vae.ScviVAE.encode; call ScviVAE.encode")
+
+
+class DecoderScvi(nn.Module):
+    """scVI-style decoder MLP - parameter and buffer tree of scldm.nnets.DecoderScvi (nnets.py:48-73); runs inside
+    scldm_amd.vae.ScviVAE.decode (scldm_scvi_decode)."""
+
+    def __init__(self, n_latent: int, n_hidden: int, n_layers: int, dropout: float):
+        super().__init__()
+        self.n_latent, self.n_hidden, self.n_layers, self.dropout = n_latent, n_hidden, n_layers, dropout
+        self.decoder_mlp = _scvi_mlp(n_latent, n_hidden, n_layers, dropout)
+        self.last_embedding = None
+
+    def forward(self, x, condition=None):  # pragma: no cover - guard only
+        raise RuntimeError("DecoderScvi is fused into scldm_amd.vae.ScviVAE.decode; call ScviVAE.decode")
+
+
 class _DiTTrainFn(torch.autograd.Function):
     """DiT.forward with a HIP backward: scldm_dit_train_forward / scldm_dit_train_backward (include/scldm_hip.h).
     Replaces torch autograd over scldm.nnets.DiT.forward (nnets.py:273-297) inside Transport.training_losses.

@@ -53,6 +53,41 @@ class NegativeBinomialTransformerLayer(nn.Module):
         raise RuntimeError("NegativeBinomialTransformerLayer is fused into scldm_amd.vae.TransformerVAE.decode")
 
 
+class GaussianLinearLayer(nn.Module):
+    """Posterior head of the scVI-style baseline (stochastic_layers.py:38-70): `loc` and `scale` Linear(n_hidden, n_latent);
+    Normal(loc(h), exp(hardtanh(scale(h), -7, 5))).  Both products, the clamp, the exp and z = loc + eps scale are one kernel inside
+    scldm_amd.vae.ScviVAE (scldm_scvi_encode)."""
+
+    def __init__(self, n_hidden: int, n_latent: int):
+        super().__init__()
+        self.n_hidden, self.n_latent = n_hidden, n_latent
+        self.loc = nn.Linear(n_hidden, n_latent, bias=True)
+        self.scale = nn.Linear(n_hidden, n_latent, bias=True)
+
+    def forward(self, *a, **k):  # pragma: no cover - guard only
+        raise RuntimeError("GaussianLinearLayer is fused into scldm_amd.vae.ScviVAE.encode")
+
+
+class NegativeBinomialLinearLayer(nn.Module):
+    """Likelihood head of the scVI-style baseline (stochastic_layers.py:123-158): `mu` Linear(n_hidden, n_genes); `theta` a
+    Parameter (n_genes) initialised to ones (shared_theta=True) or a Linear(n_hidden, n_genes).  mu = library_size softmax_G(mu(g)),
+    theta = softplus(theta) or softplus(theta(g)); computed inside scldm_amd.vae.ScviVAE.decode (scldm_scvi_decode)."""
+
+    def __init__(self, *, n_genes: int, n_hidden: int, shared_theta: bool = False):
+        super().__init__()
+        self.shared_theta = shared_theta
+        self.n_genes, self.n_hidden = n_genes, n_hidden
+        self.mu = nn.Linear(n_hidden, n_genes, bias=True)
+        if shared_theta:
+            self.theta = nn.Parameter(torch.ones(n_genes), requires_grad=True)
+        else:
+            self.theta = nn.Linear(n_hidden, n_genes, bias=True)
+        self.softplus = nn.Softplus()
+
+    def forward(self, *a, **k):  # pragma: no cover - guard only
+        raise RuntimeError("NegativeBinomialLinearLayer is fused into scldm_amd.vae.ScviVAE.decode")
+
+
 class NegativeBinomial(torch.distributions.Distribution):
     """Minimal stand-in for scvi.distributions.NegativeBinomial(mu=, theta=) as used by the reference
     (vae.py:87; models.py:819 calls .sample()): holds mu / theta, samples with the Gamma-Poisson mixture."""

@@ -10,8 +10,9 @@ from torch._utils import _unflatten_dense_tensors
 
 from . import _lib
 from .layers import InputTransformerVAE, swiglu_hidden
-from .nnets import Decoder, Encoder, _require_cuda_f32, _stream_ptr
-from .stochastic_layers import GaussianTransformerLayer, NegativeBinomial, NegativeBinomialTransformerLayer, Normal
+from .nnets import Decoder, DecoderScvi, Encoder, EncoderScvi, _require_cuda_f32, _stream_ptr
+from .stochastic_layers import (GaussianLinearLayer, GaussianTransformerLayer, NegativeBinomial, NegativeBinomialLinearLayer,
+                                NegativeBinomialTransformerLayer, Normal)
 
 
 def table_order(genes: torch.Tensor, genes_subset: torch.Tensor, counts_subset: torch.Tensor, n_rows: int):
@@ -511,3 +512,229 @@ class TransformerVAE(nn.Module):
             if self.gaussian_head:
                 return {"mu": nb.mu}, z        # vae.py:47-49
             return {"mu": nb.mu, "theta": nb.theta}, z
+
+
+class ScviVAE(nn.Module):
+    """The scVI-style baseline with the reference's API (src/scldm/vae.py:90-128): `EncoderScvi` -> `GaussianLinearLayer` ->
+    `DecoderScvi` -> `NegativeBinomialLinearLayer`, plus the prior the training loss uses.  Inference only: eval mode, exact fp32, on
+    the kernels of csrc/scvi.hpp (scldm_scvi_*).  The weights are read where they live; the BatchNorm affine and running statistics
+    and the Linear bias of every MLP layer are folded into one scale / shift pair per column by a fingerprint-guarded packing launch
+    in front of every call, so `load_state_dict`, an optimiser step or an in-place `.data` / buffer update is picked up by the next
+    call."""
+
+    def __init__(self, encoder: EncoderScvi, encoder_head: GaussianLinearLayer, decoder: DecoderScvi,
+                 decoder_head: NegativeBinomialLinearLayer, prior: nn.Module):
+        super().__init__()
+        self.encoder = encoder
+        self.encoder_head = encoder_head
+        self.decoder = decoder
+        self.decoder_head = decoder_head
+        self.prior = prior
+        self._precision = "fp32"
+        self._handle = None
+        self._weights_key = None
+        self._ws = None
+        self._keep = None
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str) -> None:
+        if value != "fp32":
+            raise NotImplementedError(f"ScviVAE runs in exact fp32 only (precision={value!r}); fp16 / bf16 operands are not built for it")
+        self._precision = value
+
+    # ------------------------------------------------------------------ native handle
+    def _layers(self, mlp):
+        return [(mlp[4 * i], mlp[4 * i + 1]) for i in range(len(mlp) // 4)]
+
+    def _tensors(self):
+        """Every parameter and buffer the kernels read."""
+        out = []
+        for mlp in (self.encoder.encoder_mlp, self.decoder.decoder_mlp):
+            for lin, bn in self._layers(mlp):
+                out += [lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        eh, dh = self.encoder_head, self.decoder_head
+        out += [eh.loc.weight, eh.loc.bias, eh.scale.weight, eh.scale.bias, dh.mu.weight, dh.mu.bias]
+        out += [dh.theta] if dh.shared_theta else [dh.theta.weight, dh.theta.bias]
+        return out
+
+    def _check_mode(self, *inputs) -> None:
+        if self.training:
+            drop = max(float(self.encoder.dropout), float(self.decoder.dropout))
+            extra = f" (dropout={drop:g} would also need a mask kernel)" if drop > 0 else ""
+            raise NotImplementedError("ScviVAE has no training path: BatchNorm1d batch statistics and the backward are not built; call "
+                                      f".eval() first{extra}")
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs):
+            raise NotImplementedError("ScviVAE is inference only: an input requires grad under enabled autograd, and there is no HIP "
+                                      "backward for this model; detach the input or call it under torch.no_grad()")
+
+    def _native(self):
+        L = _lib.lib()
+        w0 = self.decoder_head.mu.weight
+        if w0.device.type != "cuda":
+            raise RuntimeError("ScviVAE parameters must live on a CUDA (ROCm) device; there is no CPU path")
+        enc_layers, dec_layers = self._layers(self.encoder.encoder_mlp), self._layers(self.decoder.decoder_mlp)
+        if self._handle is None:
+            eps = {float(bn.eps) for _, bn in enc_layers + dec_layers}
+            if len(eps) != 1:
+                raise NotImplementedError(f"the packed BatchNorm fold takes one eps for every layer (got {sorted(eps)})")
+            G, H = w0.shape
+            h = C.c_void_p()
+            _lib.check(L.scldm_scvi_create(len(enc_layers), len(dec_layers), G, H, self.encoder_head.loc.weight.shape[0],
+                                           int(self.decoder_head.shared_theta), eps.pop(), C.byref(h)), "scldm_scvi_create")
+            self._handle = h
+        tensors = self._tensors()
+        key = tuple(t.data_ptr() for t in tensors)
+        if key != self._weights_key:
+            for t in tensors:
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != w0.device:
+                    raise RuntimeError("ScviVAE parameters and buffers must be contiguous fp32 on one device")
+
+            def layer(lin, bn):
+                return _lib.ScviLayer(w=lin.weight.data_ptr(), b=lin.bias.data_ptr(), bn_w=bn.weight.data_ptr(), bn_b=bn.bias.data_ptr(),
+                                      bn_mean=bn.running_mean.data_ptr(), bn_var=bn.running_var.data_ptr())
+            ea = (_lib.ScviLayer * len(enc_layers))(*[layer(*l) for l in enc_layers])
+            da = (_lib.ScviLayer * len(dec_layers))(*[layer(*l) for l in dec_layers])
+            eh, dh = self.encoder_head, self.decoder_head
+            shared = dh.shared_theta
+            p = _lib.ScviParams(enc=ea, dec=da, loc_w=eh.loc.weight.data_ptr(), loc_b=eh.loc.bias.data_ptr(),
+                                scale_w=eh.scale.weight.data_ptr(), scale_b=eh.scale.bias.data_ptr(), mu_w=dh.mu.weight.data_ptr(),
+                                mu_b=dh.mu.bias.data_ptr(), theta_w=dh.theta.data_ptr() if shared else dh.theta.weight.data_ptr(),
+                                theta_b=None if shared else dh.theta.bias.data_ptr())
+            with torch.cuda.device(w0.device):
+                _lib.check(L.scldm_scvi_pack(self._handle, C.byref(p), _stream_ptr()), "scldm_scvi_pack")
+            self._weights_key = key
+        return L, self._handle
+
+    def _workspace(self, L, B: int) -> int:
+        need = L.scldm_scvi_workspace_bytes(self._handle, B)
+        dev = self.decoder_head.mu.weight.device
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._ws.data_ptr()
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.update(_handle=None, _weights_key=None, _ws=None, _keep=None)
+        return state
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                _lib.lib().scldm_scvi_destroy(self._handle)
+        except Exception:
+            pass
+
+    @property
+    def _dims(self):
+        G, H = self.decoder_head.mu.weight.shape
+        return G, H, self.encoder_head.loc.weight.shape[0]
+
+    def _counts(self, counts: torch.Tensor) -> torch.Tensor:
+        c = _require_cuda_f32("counts", counts)
+        G = self._dims[0]
+        if c.dim() != 2 or c.shape[1] != G:
+            raise ValueError(f"counts must be (B, {G}); got {tuple(c.shape)}")
+        return c
+
+    def _library(self, library_size: torch.Tensor, B: int) -> torch.Tensor:
+        lib = _require_cuda_f32("library_size", library_size).reshape(-1)
+        if lib.shape[0] != B:
+            raise ValueError(f"library_size must hold one value per cell, (B,) or (B, 1) with B = {B}; got {tuple(library_size.shape)}")
+        return lib
+
+    def _encode(self, counts: torch.Tensor, eps: torch.Tensor | None):
+        L, h = self._native()
+        c = self._counts(counts)
+        B = c.shape[0]
+        G, H, nl = self._dims
+        new = lambda *s: torch.empty(*s, device=c.device, dtype=torch.float32)   # noqa: E731
+        hz, loc, scale = new(B, H), new(B, nl), new(B, nl)
+        z = None
+        if eps is not None:
+            eps = _require_cuda_f32("eps", eps)
+            if eps.shape != (B, nl):
+                raise ValueError(f"eps must be (B, n_latent) = ({B}, {nl}); got {tuple(eps.shape)}")
+            z = new(B, nl)
+        ws = self._workspace(L, B)
+        with torch.cuda.device(c.device):
+            _lib.check(L.scldm_scvi_encode(h, c.data_ptr(), B, eps.data_ptr() if eps is not None else None, hz.data_ptr(), loc.data_ptr(),
+                                           scale.data_ptr(), z.data_ptr() if z is not None else None, ws, _stream_ptr()), "scldm_scvi_encode")
+        return hz, loc, scale, z
+
+    # ------------------------------------------------------------------ reference API (vae.py:90-128)
+    @torch.no_grad()
+    def _encode_checked(self, counts, eps=None):
+        return self._encode(counts, eps)
+
+    def encode(self, counts: torch.Tensor) -> torch.distributions.Normal:
+        """The variational posterior Normal(loc, scale) of `counts` (B, n_genes) (encoder, then encoder_head)."""
+        self._check_mode(counts)
+        _, loc, scale, _ = self._encode_checked(counts)
+        return Normal(loc, scale)
+
+    def encode_hidden(self, counts: torch.Tensor, eps: torch.Tensor | None = None):
+        """(h, loc, scale, z): the encoder MLP's output next to the posterior's parameters; z = loc + eps scale when eps is given."""
+        self._check_mode(counts)
+        return self._encode_checked(counts, eps)
+
+    def decode(self, z: torch.Tensor, genes: torch.Tensor | None, library_size: torch.Tensor,
+               condition: dict[str, torch.Tensor] | None = None) -> NegativeBinomial:
+        """NegativeBinomial(mu, theta) of latents z (B, n_latent): decoder, then decoder_head (what VAEScvi.sample calls,
+        models.py; `genes` and `condition` are accepted and unused, as the reference's head ignores them)."""
+        self._check_mode(z, library_size)
+        with torch.no_grad():
+            L, h = self._native()
+            z = _require_cuda_f32("z", z)
+            G, H, nl = self._dims
+            if z.dim() != 2 or z.shape[1] != nl:
+                raise ValueError(f"z must be (B, {nl}); got {tuple(z.shape)}")
+            B = z.shape[0]
+            lib = self._library(library_size, B)
+            mu = torch.empty(B, G, device=z.device, dtype=torch.float32)
+            theta = torch.empty((G,) if self.decoder_head.shared_theta else (B, G), device=z.device, dtype=torch.float32)
+            ws = self._workspace(L, B)
+            with torch.cuda.device(z.device):
+                _lib.check(L.scldm_scvi_decode(h, z.data_ptr(), lib.data_ptr(), lib.shape[0], B, mu.data_ptr(), theta.data_ptr(), ws,
+                                               _stream_ptr()), "scldm_scvi_decode")
+        return NegativeBinomial(mu=mu, theta=theta)
+
+    def forward_outputs(self, counts: torch.Tensor, library_size: torch.Tensor, eps: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+        """Every array one scldm_scvi_forward call writes, by name: the encoder MLP's output `h` (B, n_hidden), `loc`, `scale`, `z`
+        (B, n_latent), `mu` (B, n_genes) and `theta` ((n_genes,) shared, else (B, n_genes)).  `forward` wraps this and drops `h`, which
+        the reference's forward does not return."""
+        self._check_mode(counts, library_size)
+        with torch.no_grad():
+            L, h = self._native()
+            c = self._counts(counts)
+            B = c.shape[0]
+            G, H, nl = self._dims
+            lib = self._library(library_size, B)
+            if eps is None:
+                eps = torch.randn(B, nl, device=c.device, dtype=torch.float32)
+            eps = _require_cuda_f32("eps", eps)
+            if eps.shape != (B, nl):
+                raise ValueError(f"eps must be (B, n_latent) = ({B}, {nl}); got {tuple(eps.shape)}")
+            new = lambda *s: torch.empty(*s, device=c.device, dtype=torch.float32)   # noqa: E731
+            hz, loc, scale, z, mu = new(B, H), new(B, nl), new(B, nl), new(B, nl), new(B, G)
+            theta = new(G) if self.decoder_head.shared_theta else new(B, G)
+            ws = self._workspace(L, B)
+            with torch.cuda.device(c.device):
+                _lib.check(L.scldm_scvi_forward(h, c.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), hz.data_ptr(),
+                                                loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(), ws,
+                                                _stream_ptr()), "scldm_scvi_forward")
+        return {"h": hz, "loc": loc, "scale": scale, "z": z, "mu": mu, "theta": theta}
+
+    def forward(self, counts: torch.Tensor, genes: torch.Tensor | None, library_size: torch.Tensor,
+                condition: dict[str, torch.Tensor] | None = None, counts_subset: torch.Tensor | None = None,
+                genes_subset: torch.Tensor | None = None, masking_prop: float = 0.0, mask_token_idx: int = 0, *,
+                eps: torch.Tensor | None = None):
+        """(NegativeBinomial(mu, theta), Normal(loc, scale), z) as the reference's eval-mode forward returns them (vae.py:106-128);
+        `eps` (B, n_latent) is the reparameterisation noise (default: torch.randn on the device).  genes, condition, counts_subset,
+        genes_subset, masking_prop and mask_token_idx are accepted and ignored, as in the reference.  The encoder's hidden `h`, which
+        the same call computes, is dropped here: `forward_outputs` returns it."""
+        o = self.forward_outputs(counts, library_size, eps)
+        return NegativeBinomial(mu=o["mu"], theta=o["theta"]), Normal(o["loc"], o["scale"]), o["z"]
