@@ -1035,6 +1035,44 @@ int scldm_scvi_decode(scldm_scvi* h, const float* z, const float* library_size, 
 int scldm_scvi_forward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps, float* hout,
                        float* loc, float* scale, float* z, float* mu, float* theta, void* ws, void* stream);
 
+/* Training of the same model (the reference: VAEScvi.training_step / loss, models.py:942-1113), exact fp32, forward and backward.
+ *   forward   per MLP layer: a = x W^T + b; BatchNorm1d in TRAINING mode (batch mean and biased variance per column, the running
+ *             statistics updated in place with `momentum`, running_var from the unbiased variance); SiLU; dropout keep / (1 - p).
+ *             Then the posterior head (loc, scale, z = loc + eps scale) and the likelihood head as in scldm_scvi_forward.
+ *   backward  from the upstream gradients of mu, theta, loc, scale and z (each may be NULL = zero) to every parameter's gradient.
+ *             The gradient of a Linear bias in front of a training-mode BatchNorm is mathematically zero and written as exact zeros.
+ * `masks`: n_enc_layers + n_dec_layers pointers (encoder first) to (B, n_hidden) keep bytes; an MLP whose rate is 0 ignores its
+ * entries (masks may be NULL when both rates are 0).  masks_given = 0: the forward draws each keep byte from Philox4x32-10 keyed by
+ * (seed; MLP, layer, row, column) and records it there; masks_given = 1: it reads them.  The backward reads them.
+ * `record` (scldm_scvi_train_record_bytes, 256-byte aligned) carries the normalised activations from forward to backward; `ws`
+ * (scldm_scvi_train_workspace_bytes) is scratch of one call.  Backward also takes the forward's eps, scale, z, mu and theta back.
+ * Every reduction (BatchNorm column sums over the batch, bias gradients, the softmax backward's row sum, the split products) has one
+ * fixed order and there are no float atomics: the same inputs, seed and build give the same bits.  A row's results depend on the
+ * other rows of the batch (BatchNorm).  The forward ends with the fingerprint / pack launch of scldm_scvi_pack, so an eval call after
+ * a step sees the new running statistics.  SCLDM_ERR_SHAPE with nothing launched: the checks of scldm_scvi_forward, B < 2 (torch's
+ * BatchNorm refuses one row in training mode), a rate outside [0, 1), momentum outside [0, 1], a missing mask or gradient pointer. */
+typedef struct { float* dw; float* db; float* dgamma; float* dbeta; } scldm_scvi_layer_grads;
+typedef struct {
+  const scldm_scvi_layer_grads* enc;   /* n_enc_layers entries */
+  const scldm_scvi_layer_grads* dec;   /* n_dec_layers entries */
+  float* loc_w;   float* loc_b;
+  float* scale_w; float* scale_b;
+  float* mu_w;    float* mu_b;
+  float* theta_w;                      /* shared theta: (n_genes); else (n_genes, n_hidden) */
+  float* theta_b;                      /* shared theta: ignored (may be NULL) */
+} scldm_scvi_grads;
+size_t scldm_scvi_train_record_bytes(const scldm_scvi* h, int B);
+size_t scldm_scvi_train_workspace_bytes(const scldm_scvi* h, int B);
+int scldm_scvi_train_forward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                             float p_enc, float p_dec, unsigned long long seed, unsigned char* const* masks, int masks_given,
+                             float momentum, void* record, float* loc, float* scale, float* z, float* mu, float* theta, void* ws,
+                             void* stream);
+int scldm_scvi_train_backward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                              float p_enc, float p_dec, unsigned char* const* masks, const void* record, const float* scale,
+                              const float* z, const float* mu, const float* theta, const float* dmu, const float* dtheta,
+                              const float* dloc, const float* dscale, const float* dz, const scldm_scvi_grads* grads, void* ws,
+                              void* stream);
+
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the
  * production library returns SCLDM_ERR_STATE. */

@@ -108,6 +108,17 @@ class ScviLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w", "b", "bn_w", "bn_b", "bn_mean", "bn_var")]
 
 
+class ScviLayerGrads(C.Structure):
+    """scldm_scvi_layer_grads (include/scldm_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dw", "db", "dgamma", "dbeta")]
+
+
+class ScviGrads(C.Structure):
+    """scldm_scvi_grads (include/scldm_hip.h)."""
+    _fields_ = [("enc", C.POINTER(ScviLayerGrads)), ("dec", C.POINTER(ScviLayerGrads))] + \
+               [(n, C.c_void_p) for n in ("loc_w", "loc_b", "scale_w", "scale_b", "mu_w", "mu_b", "theta_w", "theta_b")]
+
+
 class ScviParams(C.Structure):
     """scldm_scvi_params (include/scldm_hip.h)."""
     _fields_ = [("enc", C.POINTER(ScviLayer)), ("dec", C.POINTER(ScviLayer))] + \
@@ -333,6 +344,13 @@ def lib() -> C.CDLL:
     L.scldm_scvi_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     L.scldm_scvi_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     L.scldm_scvi_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
+    for f in (L.scldm_scvi_train_record_bytes, L.scldm_scvi_train_workspace_bytes):
+        f.argtypes = [C.c_void_p, C.c_int]
+        f.restype = C.c_size_t
+    L.scldm_scvi_train_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float,
+                                           C.c_uint64, C.POINTER(C.c_void_p), C.c_int, C.c_float] + [C.c_void_p] * 8
+    L.scldm_scvi_train_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float,
+                                            C.POINTER(C.c_void_p)] + [C.c_void_p] * 10 + [C.POINTER(ScviGrads), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -357,7 +375,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_transport_coef_at", "scldm_sample_ode_transport", "scldm_fm_plan", "scldm_fm_wloss", "scldm_fm_wloss_bwd", "scldm_fm_prepare_transport", "scldm_fm_wloss_grad",
            "scldm_dit_train_step_transport",
            "scldm_scvi_create", "scldm_scvi_destroy", "scldm_scvi_pack", "scldm_scvi_workspace_bytes", "scldm_scvi_encode", "scldm_scvi_decode",
-           "scldm_scvi_forward"]
+           "scldm_scvi_forward",
+           "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward"]
 
 
 def check(rc: int, what: str) -> None:

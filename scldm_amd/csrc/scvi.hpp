@@ -58,6 +58,8 @@ struct Traits {
   static constexpr int kCols = kDual ? 32 : 64;                            // columns of the N0 axis one tile covers
 };
 
+// scvi_train::prod_kernel (scvi_train.hpp) is a second copy of this kernel's stage loop and MFMA loop with the TN / NN loaders of the
+// backward: a change to the tile, the LDS stride or the fragment layout here has to be made there as well.
 template <int MODE, bool LOG1P>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs a) {
   using T = Traits<MODE>;

@@ -1,29 +1,18 @@
 // C ABI of the scVI-style baseline VAE (include/scldm_hip.h): scldm_scvi_create / _destroy / _pack / _workspace_bytes / _encode /
-// _decode / _forward.  Every entry checks its arguments before the first HIP call and makes launches only (no host read, no copy).
+// _decode / _forward, the training entries are in scvi_train_api.hip.  Every entry checks its arguments before the first HIP call and makes launches only (no host read, no copy).
 #include <hip/hip_runtime.h>
 
 #include <new>
 
-#include "api_common.hpp"
 #include "scvi.hpp"
+#include "scvi_handle.hpp"
 
 using namespace scldm;
 using namespace scldm::scvi;
-
-struct scldm_scvi {
-  int n_enc, n_dec, G, H, L, shared_theta;
-  float bn_eps;
-  bool packed;
-  scldm_scvi_layer enc[kMaxLayers], dec[kMaxLayers];
-  scldm_scvi_params p;            // p.enc / p.dec point at the two arrays above
-  float *d_s, *d_c;               // (n_enc + n_dec, H) folded BatchNorm scale / shift
-  unsigned long long* d_fp;       // pack_kernel's fingerprint state
-};
+using namespace scldm::scvi_host;
+static_assert(scvi_host::kScviMaxLayers == scvi::kMaxLayers && scvi_host::kScviSplit == kScviSplitK, "scvi_handle.hpp restates scvi.hpp");
 
 namespace {
-bool misaligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) != 0; }
-int splits_of(int K) { return cdiv(K, kScviSplitK); }
-int lik_tiles(const scldm_scvi* h) { return cdiv(h->G, h->shared_theta ? 64 : 32); }
 
 struct Layout { size_t act0, act1, part, pairs, total; };
 Layout layout_of(const scldm_scvi* h, int B) {
@@ -41,40 +30,12 @@ Layout layout_of(const scldm_scvi* h, int B) {
   return l;
 }
 
-int check_ptr(const char* entry, const char* name, const void* p, bool required) {
-  if (!p) return required ? fail(SCLDM_ERR_SHAPE, "%s: %s is NULL", entry, name) : SCLDM_OK;
-  if (misaligned(p, 4)) return fail(SCLDM_ERR_SHAPE, "%s: %s is not 4-byte aligned", entry, name);
-  return SCLDM_OK;
-}
-#define CHECK_PTR(entry, p, required)                                \
-  do {                                                               \
-    const int rc_ = check_ptr(entry, #p, p, required);               \
-    if (rc_ != SCLDM_OK) return rc_;                                 \
-  } while (0)
-
 int check_call(const char* entry, const scldm_scvi* h, int B, const void* ws) {
   if (!h) return fail(SCLDM_ERR_SHAPE, "%s: NULL handle", entry);
   if (B < 1) return fail(SCLDM_ERR_SHAPE, "%s: need B >= 1 (got %d)", entry, B);
   if (!ws) return fail(SCLDM_ERR_SHAPE, "%s: ws is NULL", entry);
   if (misaligned(ws, 256)) return fail(SCLDM_ERR_SHAPE, "%s: ws is not 256-byte aligned", entry);
   return SCLDM_OK;
-}
-
-void launch_pack(const scldm_scvi* h, int force, hipStream_t st) {
-  PackArgs a;
-  const int n = h->n_enc + h->n_dec;
-  for (int i = 0; i < n; ++i) {
-    const scldm_scvi_layer& l = i < h->n_enc ? h->enc[i] : h->dec[i - h->n_enc];
-    a.layer[i] = PackLayer{l.b, l.bn_w, l.bn_b, l.bn_mean, l.bn_var};
-  }
-  a.n_layers = n;
-  a.H = h->H;
-  a.force = force;
-  a.bn_eps = h->bn_eps;
-  a.s = h->d_s;
-  a.c = h->d_c;
-  a.fp_state = h->d_fp;
-  hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, st, a);
 }
 
 // Y (B, H) = SiLU(s (act(X) W^T) + c), K split by kScviSplitK
@@ -139,13 +100,78 @@ int decode_impl(const scldm_scvi* h, const float* z, const float* library, int B
   const Layout l = layout_of(h, B);
   float* act[2] = {(float*)(ws + l.act0), (float*)(ws + l.act1)};
   float* part = (float*)(ws + l.part);
-  float* pairs = (float*)(ws + l.pairs);
   const float* x = z;
   for (int i = 0; i < h->n_dec; ++i) {
     launch_layer(h, x, i == 0 ? h->L : h->H, false, h->dec[i].w, h->n_enc + i, act[i & 1], B, part, st);
     x = act[i & 1];
   }
   LAUNCH_CHECK();
+  return lik_head_impl(h, x, library, B, mu, theta, (float*)(ws + l.pairs), st);
+}
+
+int check_encode(const char* entry, const scldm_scvi* h, const float* counts, int B, const float* eps, const float* hout, const float* loc,
+                 const float* scale, const float* z, const void* ws) {
+  int rc = check_call(entry, h, B, ws);
+  if (rc != SCLDM_OK) return rc;
+  CHECK_PTR(entry, counts, true);
+  CHECK_PTR(entry, hout, true);
+  CHECK_PTR(entry, loc, true);
+  CHECK_PTR(entry, scale, true);
+  CHECK_PTR(entry, eps, false);
+  CHECK_PTR(entry, z, eps != nullptr);
+  return SCLDM_OK;
+}
+int check_decode(const char* entry, const scldm_scvi* h, const float* z, const float* library, int n_library, int B, const float* mu,
+                 const float* theta, const void* ws) {
+  int rc = check_call(entry, h, B, ws);
+  if (rc != SCLDM_OK) return rc;
+  if (n_library != B) return fail(SCLDM_ERR_SHAPE, "%s: library_size has %d entries for %d cells", entry, n_library, B);
+  CHECK_PTR(entry, z, true);
+  CHECK_PTR(entry, library, true);
+  CHECK_PTR(entry, mu, true);
+  CHECK_PTR(entry, theta, true);
+  return SCLDM_OK;
+}
+}  // namespace
+
+// ---- the launches scvi_train_api.hip shares (scvi_handle.hpp)
+namespace scldm {
+namespace scvi_host {
+void launch_pack(const scldm_scvi* h, int force, hipStream_t st) {
+  PackArgs a;
+  const int n = h->n_enc + h->n_dec;
+  for (int i = 0; i < n; ++i) {
+    const scldm_scvi_layer& l = i < h->n_enc ? h->enc[i] : h->dec[i - h->n_enc];
+    a.layer[i] = PackLayer{l.b, l.bn_w, l.bn_b, l.bn_mean, l.bn_var};
+  }
+  a.n_layers = n;
+  a.H = h->H;
+  a.force = force;
+  a.bn_eps = h->bn_eps;
+  a.s = h->d_s;
+  a.c = h->d_c;
+  a.fp_state = h->d_fp;
+  hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, st, a);
+}
+
+int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, float* part, hipStream_t st) {
+  GemmArgs a = {};
+  a.X = X;
+  a.W0 = W;
+  a.M = B;
+  a.N0 = N;
+  a.K = K;
+  const int sp = splits_of(K);
+  a.k_per_split = sp > 1 ? kScviSplitK : cdiv(K, kBK) * kBK;
+  a.out0 = part;
+  const dim3 grid(cdiv(N, kBN), cdiv(B, kBM), sp);
+  if (log1p) hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, false>), grid, dim3(256), 0, st, a);
+  return sp;
+}
+
+// mu = library softmax_G(x W_mu^T + b), theta (shared: softplus of the parameter; else softplus(x W_theta^T + b)) of x (B, H)
+int lik_head_impl(const scldm_scvi* h, const float* x, const float* library, int B, float* mu, float* theta, float* pairs, hipStream_t st) {
   GemmArgs a = {};
   a.X = x;
   a.W0 = h->p.mu_w;
@@ -172,35 +198,8 @@ int decode_impl(const scldm_scvi* h, const float* z, const float* library, int B
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
-
-int check_encode(const char* entry, const scldm_scvi* h, const float* counts, int B, const float* eps, const float* hout, const float* loc,
-                 const float* scale, const float* z, const void* ws) {
-  int rc = check_call(entry, h, B, ws);
-  if (rc != SCLDM_OK) return rc;
-  CHECK_PTR(entry, counts, true);
-  CHECK_PTR(entry, hout, true);
-  CHECK_PTR(entry, loc, true);
-  CHECK_PTR(entry, scale, true);
-  CHECK_PTR(entry, eps, false);
-  CHECK_PTR(entry, z, eps != nullptr);
-  return SCLDM_OK;
-}
-int check_decode(const char* entry, const scldm_scvi* h, const float* z, const float* library, int n_library, int B, const float* mu,
-                 const float* theta, const void* ws) {
-  int rc = check_call(entry, h, B, ws);
-  if (rc != SCLDM_OK) return rc;
-  if (n_library != B) return fail(SCLDM_ERR_SHAPE, "%s: library_size has %d entries for %d cells", entry, n_library, B);
-  CHECK_PTR(entry, z, true);
-  CHECK_PTR(entry, library, true);
-  CHECK_PTR(entry, mu, true);
-  CHECK_PTR(entry, theta, true);
-  return SCLDM_OK;
-}
-int check_packed(const char* entry, const scldm_scvi* h) {   // after every argument check
-  if (!h->packed) return fail(SCLDM_ERR_STATE, "%s: scldm_scvi_pack has not been called", entry);
-  return SCLDM_OK;
-}
-}  // namespace
+}  // namespace scvi_host
+}  // namespace scldm
 
 extern "C" int scldm_scvi_create(int n_enc_layers, int n_dec_layers, int n_genes, int n_hidden, int n_latent, int shared_theta,
                                  float bn_eps, scldm_scvi** out) {

@@ -104,7 +104,7 @@ def _scvi_mlp(n_in: int, n_hidden: int, n_layers: int, dropout: float) -> nn.Seq
 
 class EncoderScvi(nn.Module):
     """scVI-style encoder MLP - parameter and buffer tree of scldm.nnets.EncoderScvi (nnets.py:19-45): log1p, then per layer
-    SiLU(BatchNorm1d(Linear(x))).  Its arithmetic runs inside scldm_amd.vae.ScviVAE (scldm_scvi_encode), in eval mode only."""
+    SiLU(BatchNorm1d(Linear(x))).  Its arithmetic runs inside scldm_amd.vae.ScviVAE (scldm_scvi_encode; training: scldm_scvi_train_*)."""
 
     def __init__(self, n_genes: int, n_hidden: int, n_layers: int, dropout: float):
         super().__init__()

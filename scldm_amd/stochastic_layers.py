@@ -102,6 +102,15 @@ class NegativeBinomial(torch.distributions.Distribution):
     def mean(self):
         return self.mu
 
+    def log_prob(self, value: torch.Tensor) -> torch.Tensor:
+        """Elementwise log-likelihood of `value` (B, G): scldm_amd.distributions.log_nb_positive(value, mu, theta) (the reference's
+        own formula, eps 1e-8, one fused HIP kernel forward and one backward), a (G,) theta broadcast over the cells; differentiable
+        with respect to mu and theta.  With it VAEScvi.loss runs as written (models.py:1041).  Device tensors only."""
+        from .distributions import log_nb_positive
+        if not (self.mu.is_cuda and value.is_cuda):
+            raise RuntimeError("NegativeBinomial.log_prob runs on the MI355X (log_nb_positive); value, mu and theta must be CUDA (ROCm) tensors")
+        return log_nb_positive(value, self.mu, self.theta)
+
     @torch.no_grad()
     def sample(self, sample_shape=torch.Size(), seed: int | None = None):
         """counts ~ Poisson(Gamma(concentration=theta, rate=theta/mu)) (the parameterisation scvi-tools uses), drawn by the HIP

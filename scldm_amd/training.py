@@ -656,3 +656,17 @@ class FusedTrainStep:
         self.steps += 1
         self.optimizer._opt_called = True      # (torch's LR schedulers warn when scheduler.step() is not preceded by an optimizer.step(): the fused call is that step)
         return self.loss
+
+
+def scvi_loss(vae, counts: torch.Tensor, conditional_likelihood, variational_posterior, z_sample: torch.Tensor,
+              kl_weight: float = 1.0) -> dict[str, torch.Tensor]:
+    """The reference's VAEScvi.loss (models.py:1031-1053) for `scldm_amd.vae.ScviVAE`: {"llh": the negative log-likelihood of
+    `counts` under the decoder's NegativeBinomial, summed over genes and averaged over cells, "kl": kl_weight (log q(z | x) -
+    log p(z)) summed over the latent and averaged over cells}.  The step's loss is the sum of the two."""
+    recon = -conditional_likelihood.log_prob(counts)
+    kl = kl_weight * (variational_posterior.log_prob(z_sample) - vae.prior.log_prob(z_sample))
+    out = {"llh": recon.sum(dim=1).mean(), "kl": kl.sum(dim=1).mean()}
+    for k, v in out.items():
+        if torch.isnan(v).any():
+            raise ValueError(f"NaN values detected in {k}")
+    return out

@@ -516,11 +516,17 @@ class TransformerVAE(nn.Module):
 
 class ScviVAE(nn.Module):
     """The scVI-style baseline with the reference's API (src/scldm/vae.py:90-128): `EncoderScvi` -> `GaussianLinearLayer` ->
-    `DecoderScvi` -> `NegativeBinomialLinearLayer`, plus the prior the training loss uses.  Inference only: eval mode, exact fp32, on
+    `DecoderScvi` -> `NegativeBinomialLinearLayer`, plus the prior the training loss uses.  Inference: eval mode, exact fp32, on
     the kernels of csrc/scvi.hpp (scldm_scvi_*).  The weights are read where they live; the BatchNorm affine and running statistics
     and the Linear bias of every MLP layer are folded into one scale / shift pair per column by a fingerprint-guarded packing launch
     in front of every call, so `load_state_dict`, an optimiser step or an in-place `.data` / buffer update is picked up by the next
-    call."""
+    call.
+
+    Training is opt-in: with `train_enabled = True` a module in training mode runs `forward` through one autograd function on the
+    kernels of csrc/scvi_train.hpp (scldm_scvi_train_forward / _backward: BatchNorm batch statistics, dropout, the whole backward).
+    With the default, training mode is refused as before."""
+
+    train_enabled = False
 
     def __init__(self, encoder: EncoderScvi, encoder_head: GaussianLinearLayer, decoder: DecoderScvi,
                  decoder_head: NegativeBinomialLinearLayer, prior: nn.Module):
@@ -535,6 +541,8 @@ class ScviVAE(nn.Module):
         self._weights_key = None
         self._ws = None
         self._keep = None
+        self._train_ws = None
+        self.last_dropout_masks = None
 
     @property
     def precision(self) -> str:
@@ -618,7 +626,7 @@ class ScviVAE(nn.Module):
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        state.update(_handle=None, _weights_key=None, _ws=None, _keep=None)
+        state.update(_handle=None, _weights_key=None, _ws=None, _keep=None, _train_ws=None, last_dropout_masks=None)
         return state
 
     def __del__(self):
@@ -728,13 +736,150 @@ class ScviVAE(nn.Module):
                                                 _stream_ptr()), "scldm_scvi_forward")
         return {"h": hz, "loc": loc, "scale": scale, "z": z, "mu": mu, "theta": theta}
 
+    # ------------------------------------------------------------------ training (opt-in)
+    def _train_params(self):
+        """The trainable parameters in the order _ScviTrainFn returns their gradients."""
+        out = []
+        eh, dh = self.encoder_head, self.decoder_head
+        for lin, bn in self._layers(self.encoder.encoder_mlp):
+            out += [lin.weight, lin.bias, bn.weight, bn.bias]
+        out += [eh.loc.weight, eh.loc.bias, eh.scale.weight, eh.scale.bias]
+        for lin, bn in self._layers(self.decoder.decoder_mlp):
+            out += [lin.weight, lin.bias, bn.weight, bn.bias]
+        out += [dh.mu.weight, dh.mu.bias]
+        out += [dh.theta] if dh.shared_theta else [dh.theta.weight, dh.theta.bias]
+        return out
+
+    def _train_workspace(self, L, B: int) -> int:
+        need = L.scldm_scvi_train_workspace_bytes(self._handle, B)
+        dev = self.decoder_head.mu.weight.device
+        if self._train_ws is None or self._train_ws.numel() < need or self._train_ws.device != dev:
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._train_ws.data_ptr()
+
+    def _train_forward(self, counts, library_size, eps, seed, dropout_masks):
+        if self._precision != "fp32":
+            raise NotImplementedError(f"ScviVAE trains in exact fp32 only (precision={self._precision!r})")
+        for name, t in (("counts", counts), ("library_size", library_size), ("eps", eps)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise NotImplementedError(f"ScviVAE training forms no gradient with respect to its inputs ({name} requires grad); detach it")
+        bns = [bn for mlp in (self.encoder.encoder_mlp, self.decoder.decoder_mlp) for _, bn in self._layers(mlp)]
+        if any(bn.momentum is None for bn in bns):
+            raise NotImplementedError("ScviVAE training takes a numeric BatchNorm momentum (momentum=None, the cumulative average, is not built)")
+        if len({float(bn.momentum) for bn in bns}) != 1:
+            raise NotImplementedError(f"ScviVAE training takes one BatchNorm momentum for every layer (got {sorted({float(bn.momentum) for bn in bns})})")
+        if len({float(bn.eps) for bn in bns}) != 1:
+            raise NotImplementedError(f"the packed BatchNorm fold takes one eps for every layer (got {sorted({float(bn.eps) for bn in bns})})")
+        if counts.dim() == 2 and counts.shape[0] < 2:
+            raise ValueError(f"BatchNorm1d in training mode needs at least two cells per batch (got B = {counts.shape[0]})")
+        c = self._counts(counts)
+        B = c.shape[0]
+        G, H, nl = self._dims
+        lib = self._library(library_size, B)
+        if eps is None:
+            eps = torch.randn(B, nl, device=c.device, dtype=torch.float32)
+        eps = _require_cuda_f32("eps", eps)
+        if eps.shape != (B, nl):
+            raise ValueError(f"eps must be (B, n_latent) = ({B}, {nl}); got {tuple(eps.shape)}")
+        n_enc, n_dec = len(self.encoder.encoder_mlp) // 4, len(self.decoder.decoder_mlp) // 4
+        rates = [float(self.encoder.dropout)] * n_enc + [float(self.decoder.dropout)] * n_dec
+        if dropout_masks is not None:
+            dropout_masks = list(dropout_masks)
+            if len(dropout_masks) != n_enc + n_dec:
+                raise ValueError(f"dropout_masks must hold one (B, {H}) uint8 mask per MLP layer, encoder first ({n_enc + n_dec}); got {len(dropout_masks)}")
+            masks = []
+            for p, m in zip(rates, dropout_masks):
+                if p > 0:
+                    if not isinstance(m, torch.Tensor) or not m.is_cuda or m.shape != (B, H):
+                        raise ValueError(f"every dropout mask of an MLP with dropout > 0 must be a CUDA (ROCm) tensor of shape ({B}, {H})")
+                    m = m.to(torch.uint8).contiguous()
+                masks.append(m if p > 0 else None)
+        else:
+            masks = [torch.empty(B, H, dtype=torch.uint8, device=c.device) if p > 0 else None for p in rates]
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item()) if any(p > 0 for p in rates) else 0
+        mu, theta, loc, scale, z = _ScviTrainFn.apply(self, c, lib, eps, int(seed or 0), masks, dropout_masks is not None,
+                                                      *self._train_params())
+        for bn in bns:
+            bn.num_batches_tracked += 1
+        self.last_dropout_masks = masks
+        return NegativeBinomial(mu=mu, theta=theta), Normal(loc, scale), z
+
     def forward(self, counts: torch.Tensor, genes: torch.Tensor | None, library_size: torch.Tensor,
                 condition: dict[str, torch.Tensor] | None = None, counts_subset: torch.Tensor | None = None,
                 genes_subset: torch.Tensor | None = None, masking_prop: float = 0.0, mask_token_idx: int = 0, *,
-                eps: torch.Tensor | None = None):
-        """(NegativeBinomial(mu, theta), Normal(loc, scale), z) as the reference's eval-mode forward returns them (vae.py:106-128);
+                eps: torch.Tensor | None = None, seed: int | None = None, dropout_masks=None):
+        """(NegativeBinomial(mu, theta), Normal(loc, scale), z) as the reference's forward returns them (vae.py:106-128);
         `eps` (B, n_latent) is the reparameterisation noise (default: torch.randn on the device).  genes, condition, counts_subset,
         genes_subset, masking_prop and mask_token_idx are accepted and ignored, as in the reference.  The encoder's hidden `h`, which
-        the same call computes, is dropped here: `forward_outputs` returns it."""
+        the same call computes, is dropped here: `forward_outputs` returns it.
+
+        In training mode with `train_enabled` the five tensors are differentiable with respect to the parameters (one HIP forward, one
+        HIP backward), the BatchNorm running statistics and `num_batches_tracked` advance, and dropout keeps an element with the
+        module's rates: the keep masks are drawn on the device from `seed` (default: a draw from torch's global generator) or given as
+        `dropout_masks`, one (B, n_hidden) uint8 tensor per MLP layer, encoder first; the masks used are left in
+        `last_dropout_masks`.  `seed` and `dropout_masks` mean nothing in eval mode."""
+        if self.training and self.train_enabled:
+            return self._train_forward(counts, library_size, eps, seed, dropout_masks)
         o = self.forward_outputs(counts, library_size, eps)
         return NegativeBinomial(mu=o["mu"], theta=o["theta"]), Normal(o["loc"], o["scale"]), o["z"]
+
+
+class _ScviTrainFn(torch.autograd.Function):
+    """ScviVAE's training forward and backward: scldm_scvi_train_forward / scldm_scvi_train_backward (include/scldm_hip.h)."""
+
+    @staticmethod
+    def forward(ctx, module, counts, lib, eps, seed, masks, masks_given, *params):
+        L, h = module._native()
+        B = counts.shape[0]
+        G, H, nl = module._dims
+        dev = counts.device
+        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)   # noqa: E731
+        loc, scale, z, mu = new(B, nl), new(B, nl), new(B, nl), new(B, G)
+        theta = new(G) if module.decoder_head.shared_theta else new(B, G)
+        record = torch.empty(L.scldm_scvi_train_record_bytes(h, B), dtype=torch.uint8, device=dev)
+        mask_ptrs = (C.c_void_p * len(masks))(*[m.data_ptr() if m is not None else None for m in masks])
+        p_enc, p_dec = float(module.encoder.dropout), float(module.decoder.dropout)
+        momentum = float(module.encoder.encoder_mlp[1].momentum)
+        ws = module._train_workspace(L, B)
+        with torch.cuda.device(dev):
+            _lib.check(L.scldm_scvi_train_forward(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), p_enc, p_dec,
+                                                  C.c_uint64(seed), mask_ptrs, int(masks_given), momentum, record.data_ptr(),
+                                                  loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(), ws,
+                                                  _stream_ptr()), "scldm_scvi_train_forward")
+        ctx.module, ctx.masks, ctx.rates = module, masks, (p_enc, p_dec)
+        # the parameters too: the backward reads the weights through the handle's pointers, so an in-place update between forward
+        # and backward (an optimizer step before a second backward with retain_graph) must raise autograd's version error
+        ctx.save_for_backward(counts, lib, eps, record, scale, z, mu, theta, *params)
+        ctx.set_materialize_grads(False)
+        return mu, theta, loc, scale, z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmu, dtheta, dloc, dscale, dz):
+        module = ctx.module
+        counts, lib, eps, record, scale, z, mu, theta, *params = ctx.saved_tensors
+        L, h = module._native()
+        B = counts.shape[0]
+        ups = [None if g is None else g.contiguous().float() for g in (dmu, dtheta, dloc, dscale, dz)]
+        grads = [torch.empty_like(p) for p in params]
+        it = iter(grads)
+        n_enc, n_dec = len(module.encoder.encoder_mlp) // 4, len(module.decoder.decoder_mlp) // 4
+
+        def layers(n):
+            return (_lib.ScviLayerGrads * n)(*[_lib.ScviLayerGrads(*[next(it).data_ptr() for _ in range(4)]) for _ in range(n)])
+        ea = layers(n_enc)
+        head = [next(it).data_ptr() for _ in range(4)]
+        da = layers(n_dec)
+        shared = module.decoder_head.shared_theta
+        lik = [next(it).data_ptr() for _ in range(3 if shared else 4)] + ([None] if shared else [])
+        g = _lib.ScviGrads(ea, da, *head, *lik)
+        mask_ptrs = (C.c_void_p * len(ctx.masks))(*[m.data_ptr() if m is not None else None for m in ctx.masks])
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        ws = module._train_workspace(L, B)
+        with torch.cuda.device(counts.device):
+            _lib.check(L.scldm_scvi_train_backward(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), ctx.rates[0],
+                                                   ctx.rates[1], mask_ptrs, record.data_ptr(), scale.data_ptr(), z.data_ptr(),
+                                                   mu.data_ptr(), theta.data_ptr(), *[ptr(t) for t in ups], C.byref(g), ws,
+                                                   _stream_ptr()), "scldm_scvi_train_backward")
+        return (None,) * 7 + tuple(g_ if p.requires_grad else None for g_, p in zip(grads, params))
