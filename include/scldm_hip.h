@@ -1034,6 +1034,25 @@ int scldm_scvi_decode(scldm_scvi* h, const float* z, const float* library_size, 
 /* encode (eps required) followed by decode of its z, one fingerprint / pack launch in front. */
 int scldm_scvi_forward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps, float* hout,
                        float* loc, float* scale, float* z, float* mu, float* theta, void* ws, void* stream);
+/* The same three entries with the precision of the products as an argument (in front of ws).  Arguments, checks, workspace
+ * (scldm_scvi_workspace_bytes serves both precisions: the activations between launches stay fp32), the fingerprint / pack launch in
+ * front and the launch-only / graph-capture property are those of the entry without the suffix.
+ *   SCLDM_PREC_FP32  exactly the launches of the plain entry; the results are bit-equal to it.
+ *   SCLDM_PREC_FP16  every product on v_mfma_f32_32x32x16_f16 (the reference's TF32 class: 10 explicit mantissa bits, fp32
+ *                    accumulate).  Both operands are read as fp32 where they live and rounded to fp16, round-to-nearest-even,
+ *                    while they are staged (log1p of the counts is taken in fp32 first); a value beyond +-65 504 saturates to
+ *                    +-65 504 as in the MCAB fp16 weight policy above; NaN operands are outside the contract.  There is no packed
+ *                    fp16 copy of the weights.  The folded BatchNorm affine, SiLU, loc / scale / z, the logits, the softmax merge
+ *                    and softplus stay fp32.  The determinism of the fp32 path holds word for word: one accumulator per output
+ *                    element in ascending k order, K > 1024 split in chunks that depend on K alone and summed in split order, no
+ *                    float atomics, bit-equal run to run, a row's bits independent of the other rows of the batch.
+ *   any other value  SCLDM_ERR_SHAPE with a message, nothing launched (checked after the arguments, before the packed state). */
+int scldm_scvi_encode_ex(scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z,
+                         int precision, void* ws, void* stream);
+int scldm_scvi_decode_ex(scldm_scvi* h, const float* z, const float* library_size, int n_library, int B, float* mu, float* theta,
+                         int precision, void* ws, void* stream);
+int scldm_scvi_forward_ex(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                          float* hout, float* loc, float* scale, float* z, float* mu, float* theta, int precision, void* ws, void* stream);
 
 /* Training of the same model (the reference: VAEScvi.training_step / loss, models.py:942-1113), exact fp32, forward and backward.
  *   forward   per MLP layer: a = x W^T + b; BatchNorm1d in TRAINING mode (batch mean and biased variance per column, the running

@@ -344,6 +344,9 @@ def lib() -> C.CDLL:
     L.scldm_scvi_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     L.scldm_scvi_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     L.scldm_scvi_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
+    L.scldm_scvi_encode_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_scvi_decode_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_scvi_forward_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]
     for f in (L.scldm_scvi_train_record_bytes, L.scldm_scvi_train_workspace_bytes):
         f.argtypes = [C.c_void_p, C.c_int]
         f.restype = C.c_size_t
@@ -376,7 +379,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_dit_train_step_transport",
            "scldm_scvi_create", "scldm_scvi_destroy", "scldm_scvi_pack", "scldm_scvi_workspace_bytes", "scldm_scvi_encode", "scldm_scvi_decode",
            "scldm_scvi_forward",
-           "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward"]
+           "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward",
+           "scldm_scvi_encode_ex", "scldm_scvi_decode_ex", "scldm_scvi_forward_ex"]
 
 
 def check(rc: int, what: str) -> None:

@@ -1,5 +1,5 @@
 // C ABI of the scVI-style baseline VAE (include/scldm_hip.h): scldm_scvi_create / _destroy / _pack / _workspace_bytes / _encode /
-// _decode / _forward, the training entries are in scvi_train_api.hip.  Every entry checks its arguments before the first HIP call and makes launches only (no host read, no copy).
+// _decode / _forward, the training entries are in scvi_train_api.hip, the _ex entries (precision argument) in scvi_fp16_api.hip.  Every entry checks its arguments before the first HIP call and makes launches only (no host read, no copy).
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -319,3 +319,48 @@ extern "C" int scldm_scvi_forward(scldm_scvi* h, const float* counts, const floa
   if (rc != SCLDM_OK) return rc;
   return decode_impl(h, z, library_size, B, mu, theta, (char*)ws, (hipStream_t)stream_);
 }
+
+// ---- what scvi_fp16_api.hip shares (scvi_handle.hpp): host code only, after every use above, so that the kernels of this device
+// module are instantiated in the order they always were
+namespace scldm {
+namespace scvi_host {
+int eval_check_encode(const char* entry, const scldm_scvi* h, const float* counts, int B, const float* eps, const float* hout,
+                      const float* loc, const float* scale, const float* z, const void* ws) {
+  return check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
+}
+int eval_check_decode(const char* entry, const scldm_scvi* h, const float* z, const float* library, int n_library, int B, const float* mu,
+                      const float* theta, const void* ws) {
+  return check_decode(entry, h, z, library, n_library, B, mu, theta, ws);
+}
+int eval_check_forward(const char* entry, const scldm_scvi* h, const float* counts, const float* library, int n_library, int B,
+                       const float* eps, const float* hout, const float* loc, const float* scale, const float* z, const float* mu,
+                       const float* theta, const void* ws) {
+  int rc = check_call(entry, h, B, ws);
+  if (rc != SCLDM_OK) return rc;
+  if (!eps) return fail(SCLDM_ERR_SHAPE, "%s: eps is NULL (the caller draws it)", entry);
+  rc = check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
+  if (rc != SCLDM_OK) return rc;
+  return check_decode(entry, h, z, library, n_library, B, mu, theta, ws);
+}
+EvalWorkspace eval_workspace(const scldm_scvi* h, int B, char* ws) {
+  const Layout l = layout_of(h, B);
+  return EvalWorkspace{{(float*)(ws + l.act0), (float*)(ws + l.act1)}, (float*)(ws + l.part), (float*)(ws + l.pairs)};
+}
+int encode_fp32(const scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z, char* ws,
+                hipStream_t st) {
+  return encode_impl(h, counts, B, eps, hout, loc, scale, z, ws, st);
+}
+int decode_fp32(const scldm_scvi* h, const float* z, const float* library, int B, float* mu, float* theta, char* ws, hipStream_t st) {
+  return decode_impl(h, z, library, B, mu, theta, ws, st);
+}
+void launch_merge(const float* part, int splits, size_t plane, int N, const float* s, const float* c, float* Y, hipStream_t st) {
+  hipLaunchKernelGGL(merge_kernel, dim3(cdiv((long long)plane, 256)), dim3(256), 0, st, part, splits, plane, N, s, c, Y);
+}
+int launch_softmax_finalize(const scldm_scvi* h, const float* library, int B, float* mu, float* theta, const float* pairs, hipStream_t st) {
+  hipLaunchKernelGGL(softmax_finalize_kernel, dim3(B), dim3(256), 0, st, mu, pairs, lik_tiles(h), h->G, library,
+                     h->shared_theta ? h->p.theta_w : nullptr, theta);
+  LAUNCH_CHECK();
+  return SCLDM_OK;
+}
+}  // namespace scvi_host
+}  // namespace scldm

@@ -524,9 +524,14 @@ class ScviVAE(nn.Module):
 
     Training is opt-in: with `train_enabled = True` a module in training mode runs `forward` through one autograd function on the
     kernels of csrc/scvi_train.hpp (scldm_scvi_train_forward / _backward: BatchNorm batch statistics, dropout, the whole backward).
-    With the default, training mode is refused as before."""
+    With the default, training mode is refused as before.
+
+    fp16 operands are opt-in as well: with `fp16_enabled = True`, `precision = "fp16"` runs every product of the eval-mode calls on
+    the kernel of csrc/scvi_fp16.hpp (operands rounded to fp16, fp32 accumulate and epilogues: the reference's TF32 class).  With the
+    default the setter refuses everything but "fp32" as before; training is fp32 whatever the switch says."""
 
     train_enabled = False
+    fp16_enabled = False
 
     def __init__(self, encoder: EncoderScvi, encoder_head: GaussianLinearLayer, decoder: DecoderScvi,
                  decoder_head: NegativeBinomialLinearLayer, prior: nn.Module):
@@ -550,8 +555,11 @@ class ScviVAE(nn.Module):
 
     @precision.setter
     def precision(self, value: str) -> None:
-        if value != "fp32":
+        if value != "fp32" and not self.fp16_enabled:
             raise NotImplementedError(f"ScviVAE runs in exact fp32 only (precision={value!r}); fp16 / bf16 operands are not built for it")
+        if value not in ("fp32", "fp16"):
+            raise NotImplementedError(f"ScviVAE runs in fp32 or, with fp16_enabled, on fp16 operands (precision={value!r}); "
+                                      "bf16 operands are not built for it")
         self._precision = value
 
     # ------------------------------------------------------------------ native handle
@@ -669,8 +677,9 @@ class ScviVAE(nn.Module):
             z = new(B, nl)
         ws = self._workspace(L, B)
         with torch.cuda.device(c.device):
-            _lib.check(L.scldm_scvi_encode(h, c.data_ptr(), B, eps.data_ptr() if eps is not None else None, hz.data_ptr(), loc.data_ptr(),
-                                           scale.data_ptr(), z.data_ptr() if z is not None else None, ws, _stream_ptr()), "scldm_scvi_encode")
+            _lib.check(L.scldm_scvi_encode_ex(h, c.data_ptr(), B, eps.data_ptr() if eps is not None else None, hz.data_ptr(), loc.data_ptr(),
+                                              scale.data_ptr(), z.data_ptr() if z is not None else None, _lib.PRECISIONS[self._precision],
+                                              ws, _stream_ptr()), "scldm_scvi_encode_ex")
         return hz, loc, scale, z
 
     # ------------------------------------------------------------------ reference API (vae.py:90-128)
@@ -706,8 +715,8 @@ class ScviVAE(nn.Module):
             theta = torch.empty((G,) if self.decoder_head.shared_theta else (B, G), device=z.device, dtype=torch.float32)
             ws = self._workspace(L, B)
             with torch.cuda.device(z.device):
-                _lib.check(L.scldm_scvi_decode(h, z.data_ptr(), lib.data_ptr(), lib.shape[0], B, mu.data_ptr(), theta.data_ptr(), ws,
-                                               _stream_ptr()), "scldm_scvi_decode")
+                _lib.check(L.scldm_scvi_decode_ex(h, z.data_ptr(), lib.data_ptr(), lib.shape[0], B, mu.data_ptr(), theta.data_ptr(),
+                                                  _lib.PRECISIONS[self._precision], ws, _stream_ptr()), "scldm_scvi_decode_ex")
         return NegativeBinomial(mu=mu, theta=theta)
 
     def forward_outputs(self, counts: torch.Tensor, library_size: torch.Tensor, eps: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
@@ -731,9 +740,9 @@ class ScviVAE(nn.Module):
             theta = new(G) if self.decoder_head.shared_theta else new(B, G)
             ws = self._workspace(L, B)
             with torch.cuda.device(c.device):
-                _lib.check(L.scldm_scvi_forward(h, c.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), hz.data_ptr(),
-                                                loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(), ws,
-                                                _stream_ptr()), "scldm_scvi_forward")
+                _lib.check(L.scldm_scvi_forward_ex(h, c.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), hz.data_ptr(),
+                                                   loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(),
+                                                   _lib.PRECISIONS[self._precision], ws, _stream_ptr()), "scldm_scvi_forward_ex")
         return {"h": hz, "loc": loc, "scale": scale, "z": z, "mu": mu, "theta": theta}
 
     # ------------------------------------------------------------------ training (opt-in)
