@@ -1,5 +1,6 @@
 // C ABI of the scVI-style baseline VAE (include/scldm_hip.h): scldm_scvi_create / _destroy / _pack / _workspace_bytes / _encode /
-// _decode / _forward, the training entries are in scvi_train_api.hip, the _ex entries (precision argument) in scvi_fp16_api.hip.  Every entry checks its arguments before the first HIP call and makes launches only (no host read, no copy).
+// _decode / _forward and their _ex forms with a precision argument; the training entries are in scvi_train_api.hip.  Every entry
+// checks its arguments before the first HIP call and makes launches only (no host read, no copy).
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -10,7 +11,6 @@
 using namespace scldm;
 using namespace scldm::scvi;
 using namespace scldm::scvi_host;
-static_assert(scvi_host::kScviMaxLayers == scvi::kMaxLayers && scvi_host::kScviSplit == kScviSplitK, "scvi_handle.hpp restates scvi.hpp");
 
 namespace {
 
@@ -38,9 +38,21 @@ int check_call(const char* entry, const scldm_scvi* h, int B, const void* ws) {
   return SCLDM_OK;
 }
 
-// Y (B, H) = SiLU(s (act(X) W^T) + c), K split by kScviSplitK
-void launch_layer(const scldm_scvi* h, const float* X, int K, bool log1p, const float* W, int layer, float* Y, int B, float* part,
-                  hipStream_t st) {
+// gemm_kernel<., MODE, LOG1P> on the operands of `precision` over the whole of a.out0's (M, N0); only PARTIAL splits K
+template <int MODE, bool LOG1P = false>
+void launch_gemm(int precision, GemmArgs a, hipStream_t st) {
+  const bool f16 = precision == SCLDM_PREC_FP16;
+  const int bk = f16 ? F16Operands::kBK : F32Operands::kBK;
+  const int sp = MODE == MODE_PARTIAL ? splits_of(a.K) : 1;
+  a.k_per_split = sp > 1 ? kScviSplit : cdiv(a.K, bk) * bk;
+  const dim3 grid(cdiv(a.N0, Traits<MODE>::kCols), cdiv(a.M, kBM), sp);
+  if (f16) hipLaunchKernelGGL((gemm_kernel<F16Operands, MODE, LOG1P>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gemm_kernel<F32Operands, MODE, LOG1P>), grid, dim3(256), 0, st, a);
+}
+
+// Y (B, H) = SiLU(s (act(X) W^T) + c), K split by kScviSplit
+void launch_layer(const scldm_scvi* h, int precision, const float* X, int K, bool log1p, const float* W, int layer, float* Y, int B,
+                  float* part, hipStream_t st) {
   GemmArgs a = {};
   a.X = X;
   a.W0 = W;
@@ -50,30 +62,28 @@ void launch_layer(const scldm_scvi* h, const float* X, int K, bool log1p, const 
   a.N0 = h->H;
   a.K = K;
   const int sp = splits_of(K);
-  a.k_per_split = sp > 1 ? kScviSplitK : cdiv(K, kBK) * kBK;
-  const dim3 grid(cdiv(h->H, kBN), cdiv(B, kBM), sp);
   if (sp == 1) {
     a.out0 = Y;
-    if (log1p) hipLaunchKernelGGL((gemm_kernel<MODE_LAYER, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_kernel<MODE_LAYER, false>), grid, dim3(256), 0, st, a);
+    if (log1p) launch_gemm<MODE_LAYER, true>(precision, a, st);
+    else launch_gemm<MODE_LAYER>(precision, a, st);
   } else {
     a.out0 = part;
-    if (log1p) hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, false>), grid, dim3(256), 0, st, a);
+    if (log1p) launch_gemm<MODE_PARTIAL, true>(precision, a, st);
+    else launch_gemm<MODE_PARTIAL>(precision, a, st);
     const size_t plane = (size_t)B * h->H;
     hipLaunchKernelGGL(merge_kernel, dim3(cdiv((long long)plane, 256)), dim3(256), 0, st, part, sp, plane, h->H, a.b0, a.b1, Y);
   }
 }
 
-int encode_impl(const scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z,
-                char* ws, hipStream_t st) {
+int encode_impl(const scldm_scvi* h, int precision, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale,
+                float* z, char* ws, hipStream_t st) {
   const Layout l = layout_of(h, B);
   float* act[2] = {(float*)(ws + l.act0), (float*)(ws + l.act1)};
   float* part = (float*)(ws + l.part);
   const float* x = counts;
   for (int i = 0; i < h->n_enc; ++i) {
     float* y = i == h->n_enc - 1 ? hout : act[i & 1];
-    launch_layer(h, x, i == 0 ? h->G : h->H, i == 0, h->enc[i].w, i, y, B, part, st);
+    launch_layer(h, precision, x, i == 0 ? h->G : h->H, i == 0, h->enc[i].w, i, y, B, part, st);
     x = y;
   }
   LAUNCH_CHECK();
@@ -86,27 +96,27 @@ int encode_impl(const scldm_scvi* h, const float* counts, int B, const float* ep
   a.M = B;
   a.N0 = h->L;
   a.K = h->H;
-  a.k_per_split = cdiv(h->H, kBK) * kBK;
   a.out0 = loc;
   a.out1 = scale;
   a.out2 = eps ? z : nullptr;
   a.eps = eps;
-  hipLaunchKernelGGL((gemm_kernel<MODE_POST, false>), dim3(cdiv(h->L, 32), cdiv(B, kBM), 1), dim3(256), 0, st, a);
+  launch_gemm<MODE_POST>(precision, a, st);
   LAUNCH_CHECK();
   return SCLDM_OK;
 }
 
-int decode_impl(const scldm_scvi* h, const float* z, const float* library, int B, float* mu, float* theta, char* ws, hipStream_t st) {
+int decode_impl(const scldm_scvi* h, int precision, const float* z, const float* library, int B, float* mu, float* theta, char* ws,
+                hipStream_t st) {
   const Layout l = layout_of(h, B);
   float* act[2] = {(float*)(ws + l.act0), (float*)(ws + l.act1)};
   float* part = (float*)(ws + l.part);
   const float* x = z;
   for (int i = 0; i < h->n_dec; ++i) {
-    launch_layer(h, x, i == 0 ? h->L : h->H, false, h->dec[i].w, h->n_enc + i, act[i & 1], B, part, st);
+    launch_layer(h, precision, x, i == 0 ? h->L : h->H, false, h->dec[i].w, h->n_enc + i, act[i & 1], B, part, st);
     x = act[i & 1];
   }
   LAUNCH_CHECK();
-  return lik_head_impl(h, x, library, B, mu, theta, (float*)(ws + l.pairs), st);
+  return lik_head_impl(h, x, library, B, mu, theta, (float*)(ws + l.pairs), precision, st);
 }
 
 int check_encode(const char* entry, const scldm_scvi* h, const float* counts, int B, const float* eps, const float* hout, const float* loc,
@@ -131,6 +141,47 @@ int check_decode(const char* entry, const scldm_scvi* h, const float* z, const f
   CHECK_PTR(entry, mu, true);
   CHECK_PTR(entry, theta, true);
   return SCLDM_OK;
+}
+// the last two checks of every eval entry, after those of its arguments
+int check_precision_packed(const char* entry, const scldm_scvi* h, int precision) {
+  if (precision != SCLDM_PREC_FP32 && precision != SCLDM_PREC_FP16)
+    return fail(SCLDM_ERR_SHAPE, "%s: precision %d is not built for the scVI baseline (SCLDM_PREC_FP32 or SCLDM_PREC_FP16)", entry, precision);
+  return check_packed(entry, h);
+}
+
+// ---- the eval entries under the name of the C entry that forwards to them
+int encode_entry(const char* entry, scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale,
+                 float* z, int precision, void* ws, void* stream_) {
+  int rc = check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
+  if (rc == SCLDM_OK) rc = check_precision_packed(entry, h, precision);
+  if (rc != SCLDM_OK) return rc;
+  launch_pack(h, 0, (hipStream_t)stream_);
+  return encode_impl(h, precision, counts, B, eps, hout, loc, scale, z, (char*)ws, (hipStream_t)stream_);
+}
+
+int decode_entry(const char* entry, scldm_scvi* h, const float* z, const float* library_size, int n_library, int B, float* mu, float* theta,
+                 int precision, void* ws, void* stream_) {
+  int rc = check_decode(entry, h, z, library_size, n_library, B, mu, theta, ws);
+  if (rc == SCLDM_OK) rc = check_precision_packed(entry, h, precision);
+  if (rc != SCLDM_OK) return rc;
+  launch_pack(h, 0, (hipStream_t)stream_);
+  return decode_impl(h, precision, z, library_size, B, mu, theta, (char*)ws, (hipStream_t)stream_);
+}
+
+int forward_entry(const char* entry, scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                  float* hout, float* loc, float* scale, float* z, float* mu, float* theta, int precision, void* ws, void* stream_) {
+  int rc = check_call(entry, h, B, ws);
+  if (rc != SCLDM_OK) return rc;
+  if (!eps) return fail(SCLDM_ERR_SHAPE, "%s: eps is NULL (the caller draws it)", entry);
+  rc = check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
+  if (rc != SCLDM_OK) return rc;
+  rc = check_decode(entry, h, z, library_size, n_library, B, mu, theta, ws);
+  if (rc == SCLDM_OK) rc = check_precision_packed(entry, h, precision);
+  if (rc != SCLDM_OK) return rc;
+  launch_pack(h, 0, (hipStream_t)stream_);
+  rc = encode_impl(h, precision, counts, B, eps, hout, loc, scale, z, (char*)ws, (hipStream_t)stream_);
+  if (rc != SCLDM_OK) return rc;
+  return decode_impl(h, precision, z, library_size, B, mu, theta, (char*)ws, (hipStream_t)stream_);
 }
 }  // namespace
 
@@ -161,17 +212,14 @@ int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, 
   a.M = B;
   a.N0 = N;
   a.K = K;
-  const int sp = splits_of(K);
-  a.k_per_split = sp > 1 ? kScviSplitK : cdiv(K, kBK) * kBK;
   a.out0 = part;
-  const dim3 grid(cdiv(N, kBN), cdiv(B, kBM), sp);
-  if (log1p) hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemm_kernel<MODE_PARTIAL, false>), grid, dim3(256), 0, st, a);
-  return sp;
+  if (log1p) launch_gemm<MODE_PARTIAL, true>(SCLDM_PREC_FP32, a, st);
+  else launch_gemm<MODE_PARTIAL>(SCLDM_PREC_FP32, a, st);
+  return splits_of(K);
 }
 
-// mu = library softmax_G(x W_mu^T + b), theta (shared: softplus of the parameter; else softplus(x W_theta^T + b)) of x (B, H)
-int lik_head_impl(const scldm_scvi* h, const float* x, const float* library, int B, float* mu, float* theta, float* pairs, hipStream_t st) {
+int lik_head_impl(const scldm_scvi* h, const float* x, const float* library, int B, float* mu, float* theta, float* pairs, int precision,
+                  hipStream_t st) {
   GemmArgs a = {};
   a.X = x;
   a.W0 = h->p.mu_w;
@@ -179,21 +227,18 @@ int lik_head_impl(const scldm_scvi* h, const float* x, const float* library, int
   a.M = B;
   a.N0 = h->G;
   a.K = h->H;
-  a.k_per_split = cdiv(h->H, kBK) * kBK;
   a.out0 = mu;
   a.pairs = pairs;
-  const int tiles = lik_tiles(h);
-  const dim3 grid(tiles, cdiv(B, kBM), 1);
   if (h->shared_theta) {
-    hipLaunchKernelGGL((gemm_kernel<MODE_LIK, false>), grid, dim3(256), 0, st, a);
+    launch_gemm<MODE_LIK>(precision, a, st);
   } else {
     a.W1 = h->p.theta_w;
     a.b1 = h->p.theta_b;
     a.out1 = theta;
-    hipLaunchKernelGGL((gemm_kernel<MODE_LIK2, false>), grid, dim3(256), 0, st, a);
+    launch_gemm<MODE_LIK2>(precision, a, st);
   }
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(softmax_finalize_kernel, dim3(B), dim3(256), 0, st, mu, pairs, tiles, h->G, library,
+  hipLaunchKernelGGL(softmax_finalize_kernel, dim3(B), dim3(256), 0, st, mu, pairs, lik_tiles(h), h->G, library,
                      h->shared_theta ? h->p.theta_w : nullptr, theta);
   LAUNCH_CHECK();
   return SCLDM_OK;
@@ -207,8 +252,8 @@ extern "C" int scldm_scvi_create(int n_enc_layers, int n_dec_layers, int n_genes
   *out = nullptr;
   if (n_enc_layers < 1 || n_dec_layers < 1)
     return fail(SCLDM_ERR_SHAPE, "scldm_scvi_create: n_layers must be >= 1 (got encoder %d, decoder %d)", n_enc_layers, n_dec_layers);
-  if (n_enc_layers > kMaxLayers || n_dec_layers > kMaxLayers)
-    return fail(SCLDM_ERR_SHAPE, "scldm_scvi_create: at most %d layers per MLP (got encoder %d, decoder %d)", kMaxLayers, n_enc_layers, n_dec_layers);
+  if (n_enc_layers > kScviMaxLayers || n_dec_layers > kScviMaxLayers)
+    return fail(SCLDM_ERR_SHAPE, "scldm_scvi_create: at most %d layers per MLP (got encoder %d, decoder %d)", kScviMaxLayers, n_enc_layers, n_dec_layers);
   if (n_genes < 1 || n_hidden < 1 || n_latent < 1)
     return fail(SCLDM_ERR_SHAPE, "scldm_scvi_create: n_genes, n_hidden and n_latent must be positive (got %d, %d, %d)", n_genes, n_hidden, n_latent);
   if (!(bn_eps >= 0.f)) return fail(SCLDM_ERR_SHAPE, "scldm_scvi_create: the BatchNorm eps must be >= 0 (got %g)", (double)bn_eps);
@@ -287,80 +332,30 @@ extern "C" size_t scldm_scvi_workspace_bytes(const scldm_scvi* h, int B) {
 
 extern "C" int scldm_scvi_encode(scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z,
                                  void* ws, void* stream_) {
-  int rc = check_encode("scldm_scvi_encode", h, counts, B, eps, hout, loc, scale, z, ws);
-  if (rc == SCLDM_OK) rc = check_packed("scldm_scvi_encode", h);
-  if (rc != SCLDM_OK) return rc;
-  launch_pack(h, 0, (hipStream_t)stream_);
-  return encode_impl(h, counts, B, eps, hout, loc, scale, z, (char*)ws, (hipStream_t)stream_);
+  return encode_entry("scldm_scvi_encode", h, counts, B, eps, hout, loc, scale, z, SCLDM_PREC_FP32, ws, stream_);
+}
+extern "C" int scldm_scvi_encode_ex(scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale,
+                                    float* z, int precision, void* ws, void* stream_) {
+  return encode_entry("scldm_scvi_encode_ex", h, counts, B, eps, hout, loc, scale, z, precision, ws, stream_);
 }
 
 extern "C" int scldm_scvi_decode(scldm_scvi* h, const float* z, const float* library_size, int n_library, int B, float* mu, float* theta,
                                  void* ws, void* stream_) {
-  int rc = check_decode("scldm_scvi_decode", h, z, library_size, n_library, B, mu, theta, ws);
-  if (rc == SCLDM_OK) rc = check_packed("scldm_scvi_decode", h);
-  if (rc != SCLDM_OK) return rc;
-  launch_pack(h, 0, (hipStream_t)stream_);
-  return decode_impl(h, z, library_size, B, mu, theta, (char*)ws, (hipStream_t)stream_);
+  return decode_entry("scldm_scvi_decode", h, z, library_size, n_library, B, mu, theta, SCLDM_PREC_FP32, ws, stream_);
+}
+extern "C" int scldm_scvi_decode_ex(scldm_scvi* h, const float* z, const float* library_size, int n_library, int B, float* mu, float* theta,
+                                    int precision, void* ws, void* stream_) {
+  return decode_entry("scldm_scvi_decode_ex", h, z, library_size, n_library, B, mu, theta, precision, ws, stream_);
 }
 
 extern "C" int scldm_scvi_forward(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
                                   float* hout, float* loc, float* scale, float* z, float* mu, float* theta, void* ws, void* stream_) {
-  const char* entry = "scldm_scvi_forward";
-  int rc = check_call(entry, h, B, ws);
-  if (rc != SCLDM_OK) return rc;
-  if (!eps) return fail(SCLDM_ERR_SHAPE, "%s: eps is NULL (the caller draws it)", entry);
-  rc = check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
-  if (rc != SCLDM_OK) return rc;
-  rc = check_decode(entry, h, z, library_size, n_library, B, mu, theta, ws);
-  if (rc == SCLDM_OK) rc = check_packed(entry, h);
-  if (rc != SCLDM_OK) return rc;
-  launch_pack(h, 0, (hipStream_t)stream_);
-  rc = encode_impl(h, counts, B, eps, hout, loc, scale, z, (char*)ws, (hipStream_t)stream_);
-  if (rc != SCLDM_OK) return rc;
-  return decode_impl(h, z, library_size, B, mu, theta, (char*)ws, (hipStream_t)stream_);
+  return forward_entry("scldm_scvi_forward", h, counts, library_size, n_library, B, eps, hout, loc, scale, z, mu, theta, SCLDM_PREC_FP32, ws,
+                       stream_);
 }
-
-// ---- what scvi_fp16_api.hip shares (scvi_handle.hpp): host code only, after every use above, so that the kernels of this device
-// module are instantiated in the order they always were
-namespace scldm {
-namespace scvi_host {
-int eval_check_encode(const char* entry, const scldm_scvi* h, const float* counts, int B, const float* eps, const float* hout,
-                      const float* loc, const float* scale, const float* z, const void* ws) {
-  return check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
+extern "C" int scldm_scvi_forward_ex(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                                     float* hout, float* loc, float* scale, float* z, float* mu, float* theta, int precision, void* ws,
+                                     void* stream_) {
+  return forward_entry("scldm_scvi_forward_ex", h, counts, library_size, n_library, B, eps, hout, loc, scale, z, mu, theta, precision, ws,
+                       stream_);
 }
-int eval_check_decode(const char* entry, const scldm_scvi* h, const float* z, const float* library, int n_library, int B, const float* mu,
-                      const float* theta, const void* ws) {
-  return check_decode(entry, h, z, library, n_library, B, mu, theta, ws);
-}
-int eval_check_forward(const char* entry, const scldm_scvi* h, const float* counts, const float* library, int n_library, int B,
-                       const float* eps, const float* hout, const float* loc, const float* scale, const float* z, const float* mu,
-                       const float* theta, const void* ws) {
-  int rc = check_call(entry, h, B, ws);
-  if (rc != SCLDM_OK) return rc;
-  if (!eps) return fail(SCLDM_ERR_SHAPE, "%s: eps is NULL (the caller draws it)", entry);
-  rc = check_encode(entry, h, counts, B, eps, hout, loc, scale, z, ws);
-  if (rc != SCLDM_OK) return rc;
-  return check_decode(entry, h, z, library, n_library, B, mu, theta, ws);
-}
-EvalWorkspace eval_workspace(const scldm_scvi* h, int B, char* ws) {
-  const Layout l = layout_of(h, B);
-  return EvalWorkspace{{(float*)(ws + l.act0), (float*)(ws + l.act1)}, (float*)(ws + l.part), (float*)(ws + l.pairs)};
-}
-int encode_fp32(const scldm_scvi* h, const float* counts, int B, const float* eps, float* hout, float* loc, float* scale, float* z, char* ws,
-                hipStream_t st) {
-  return encode_impl(h, counts, B, eps, hout, loc, scale, z, ws, st);
-}
-int decode_fp32(const scldm_scvi* h, const float* z, const float* library, int B, float* mu, float* theta, char* ws, hipStream_t st) {
-  return decode_impl(h, z, library, B, mu, theta, ws, st);
-}
-void launch_merge(const float* part, int splits, size_t plane, int N, const float* s, const float* c, float* Y, hipStream_t st) {
-  hipLaunchKernelGGL(merge_kernel, dim3(cdiv((long long)plane, 256)), dim3(256), 0, st, part, splits, plane, N, s, c, Y);
-}
-int launch_softmax_finalize(const scldm_scvi* h, const float* library, int B, float* mu, float* theta, const float* pairs, hipStream_t st) {
-  hipLaunchKernelGGL(softmax_finalize_kernel, dim3(B), dim3(256), 0, st, mu, pairs, lik_tiles(h), h->G, library,
-                     h->shared_theta ? h->p.theta_w : nullptr, theta);
-  LAUNCH_CHECK();
-  return SCLDM_OK;
-}
-}  // namespace scvi_host
-}  // namespace scldm

@@ -1,28 +1,23 @@
 // Training kernels of the scVI-style baseline VAE (ScviVAE; the reference trains it with VAEScvi.training_step, models.py:942-1113):
 // BatchNorm1d in training mode forward and backward, the dropout mask, the two heads' backward and the products a backward needs.
-// Exact fp32 (OpF32) like scvi.hpp, whose forward tile kernel (NT: X[M, K] W[N, K]^T) the training forward reuses as it is
-// (MODE_PARTIAL: the raw products, launched by scvi_api.hip).  These kernels live in a translation unit of their own
-// (scvi_train_api.hip): the eval kernels' device module is what it was.  Philox4x32-10 is the project's, from fm_step_common.hpp.
+// Exact fp32 (scvi::F32Operands).  The training forward takes its raw products from scvi::gemm_kernel (MODE_PARTIAL, launched by
+// scvi_api.hip).  Philox4x32-10 is the project's, from fm_step_common.hpp.
 //
-// prod_kernel is scvi::gemm_kernel's tile (64 x 64 per workgroup of four waves, K in stages of 32 through LDS, one accumulator per
-// element walked in ascending k, the next stage's loads in flight during the MFMAs) with the two loaders a backward needs:
-//   TN  C[M, N] = A[K, M]^T B[K, N]   weight gradients, K = batch: both operands k-STRIDED, so a thread walks the row axis (64
-//                                     consecutive rows per 256-byte request) and four k-values per stage pass
-//   NN  C[M, N] = A[M, K] B[K, N]     data gradients dY W with W as torch stores it: A k-contiguous (gemm_kernel's loader), B k-strided
-// Loads are masked scalar dwords (17 002-float rows are 8-byte aligned), log1p is applied to the B operand while staging (dW_0 =
-// da_0^T log1p(X)).  K above scvi_host::kScviSplit is cut into blockIdx.z splits of that many k-values - a function of K alone - written as slots of a
-// partial buffer which sum_slots_kernel adds in slot order.  No float atomics anywhere: every sum below has one fixed order.
+// prod_kernel is the tile product of scvi_tile.hpp with the loaders a backward needs:
+//   TN  C[M, N] = A[K, M]^T B[K, N]   weight gradients, K = batch: both operands k-strided
+//   NN  C[M, N] = A[M, K] B[K, N]     data gradients dY W with W as torch stores it: A k-contiguous, B k-strided
+// log1p is applied to the B operand while staging (dW_0 = da_0^T log1p(X)).  K above kScviSplit is cut into blockIdx.z splits of that
+// many k-values - a function of K alone - written as slots of a partial buffer which sum_slots_kernel adds in slot order.  No float
+// atomics anywhere: every sum below has one fixed order.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include <type_traits>
 
-#include "common.hpp"
 #include "fm_step_common.hpp"
+#include "scvi_tile.hpp"
 
 namespace scldm {
 namespace scvi_train {
 
-constexpr int kBM = 64, kBN = 64, kBK = 32, kLd = kBK + 4;   // scvi::gemm_kernel's tile
 constexpr uint32_t kTagDrop = 0x64726f70u;   // "drop": keeps the mask draws apart from the project's other Philox streams
 
 struct ProdArgs {
@@ -37,65 +32,19 @@ struct ProdArgs {
 
 template <bool AT, bool LOG1P_B>
 __global__ __launch_bounds__(256) void prod_kernel(const ProdArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * kBM * kLd];
-  float* As = smem;
-  float* Bs = smem + kBM * kLd;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * kBM, n0 = blockIdx.x * kBN;
+  using P = scvi::F32Operands;
+  using LA = std::conditional_t<AT, scvi::StridedLoader<P, false>, scvi::RowLoader<P, false>>;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[scvi::kStageBytes<P>];
+  LA la(a.A, blockIdx.y * scvi::kBM, a.M, a.lda);
+  scvi::StridedLoader<P, LOG1P_B> lb(a.Bm, blockIdx.x * scvi::kBN, a.N, a.ldb);
   const int k_lo = blockIdx.z * a.k_per_split;
   const int k_hi = min(a.K, k_lo + a.k_per_split);
-  // k-contiguous loader: thread -> k offset tid & 31 of rows (tid >> 5) + 8 j;  k-strided loader: row tid & 63 at k offsets (tid >> 6) + 4 j
-  const int lk = tid & 31, lr = tid >> 5, tr = tid & 63, tk = tid >> 6;
-  float xa[8], wb[8];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (AT) {
-        const int k = k0 + tk + 4 * j, m = m0 + tr;
-        xa[j] = (k < k_hi && m < a.M) ? a.A[(size_t)k * a.lda + m] : 0.f;
-      } else {
-        const int k = k0 + lk, m = m0 + lr + 8 * j;
-        xa[j] = (k < k_hi && m < a.M) ? a.A[(size_t)m * a.lda + k] : 0.f;
-      }
-      const int k = k0 + tk + 4 * j, n = n0 + tr;
-      wb[j] = (k < k_hi && n < a.N) ? a.Bm[(size_t)k * a.ldb + n] : 0.f;
-    }
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  if (k_lo < k_hi) fetch(k_lo);
-  const int hh = lane >> 5, l31 = lane & 31;
-  for (int k0 = k_lo; k0 < k_hi; k0 += kBK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (AT) As[tr * kLd + tk + 4 * j] = xa[j];
-      else As[(lr + 8 * j) * kLd + lk] = xa[j];
-      Bs[tr * kLd + tk + 4 * j] = LOG1P_B ? log1pf(wb[j]) : wb[j];
-    }
-    __syncthreads();
-    if (k0 + kBK < k_hi) fetch(k0 + kBK);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float* ap = As + (wm * 32 + l31) * kLd + u * 16 + 8 * hh;
-      const float* bp = Bs + (wn * 32 + l31) * kLd + u * 16 + 8 * hh;
-      const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap), a1 = *reinterpret_cast<const f32x4*>(ap + 4);
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
-      const f32x8 af = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-      const f32x8 bf = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-      acc = OpF32::mma(af, bf, acc);
-    }
-    __syncthreads();
-  }
-  // lane holds column wn * 32 + l31 of the tile, register r row wm * 32 + acc_row(r, hh)
-  const int n = n0 + wn * 32 + l31;
-  if (n >= a.N) return;
-  float* out = a.out + (size_t)(a.slot0 + blockIdx.z) * a.M * a.N;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wm * 32 + acc_row(r, hh);
-    if (m < a.M) out[(size_t)m * a.N + n] = acc[r];
-  }
+  const f32x16 acc = scvi::tile_product<P>(la, lb, smem, k_lo, k_hi);
+  scvi::GemmArgs g = {};
+  g.M = a.M;
+  g.N0 = a.N;
+  g.out0 = a.out;
+  scvi::tile_epilogue<scvi::MODE_PARTIAL>(g, acc, nullptr, a.slot0 + blockIdx.z);
 }
 
 // out = slot 0 + slot 1 + ... in slot order

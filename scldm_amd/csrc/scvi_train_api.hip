@@ -73,10 +73,10 @@ int launch_prod(const float* A, long long lda, bool at, const float* Bm, long lo
   a.N = N;
   a.K = K;
   const int sp = splits_of(K);
-  a.k_per_split = sp > 1 ? kScviSplit : cdiv(K, kBK) * kBK;
+  a.k_per_split = sp > 1 ? kScviSplit : cdiv(K, scvi::F32Operands::kBK) * scvi::F32Operands::kBK;
   a.out = dst;
   a.slot0 = slot0;
-  const dim3 grid(cdiv(N, kBN), cdiv(M, kBM), sp);
+  const dim3 grid(cdiv(N, scvi::kBN), cdiv(M, scvi::kBM), sp);
   if (!at) hipLaunchKernelGGL((prod_kernel<false, false>), grid, dim3(256), 0, st, a);
   else if (log1p_b) hipLaunchKernelGGL((prod_kernel<true, true>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((prod_kernel<true, false>), grid, dim3(256), 0, st, a);
@@ -187,7 +187,7 @@ extern "C" int scldm_scvi_train_forward(scldm_scvi* h, const float* counts, cons
     LAUNCH_CHECK();
     x = a.h;
   }
-  rc = lik_head_impl(h, x, library, B, mu, theta, (float*)((char*)ws + l.pairs), st);
+  rc = lik_head_impl(h, x, library, B, mu, theta, (float*)((char*)ws + l.pairs), SCLDM_PREC_FP32, st);
   if (rc != SCLDM_OK) return rc;
   launch_pack(h, 0, st);      // the fingerprint sees the new running statistics: eval calls after this step use them
   LAUNCH_CHECK();

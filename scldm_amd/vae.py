@@ -527,7 +527,7 @@ class ScviVAE(nn.Module):
     With the default, training mode is refused as before.
 
     fp16 operands are opt-in as well: with `fp16_enabled = True`, `precision = "fp16"` runs every product of the eval-mode calls on
-    the kernel of csrc/scvi_fp16.hpp (operands rounded to fp16, fp32 accumulate and epilogues: the reference's TF32 class).  With the
+    the same kernel on csrc/scvi_tile.hpp's F16Operands (operands rounded to fp16, fp32 accumulate and epilogues: the reference's TF32 class).  With the
     default the setter refuses everything but "fp32" as before; training is fp32 whatever the switch says."""
 
     train_enabled = False

@@ -1,4 +1,4 @@
-"""ScviVAE's fp16-operand inference path (csrc/scvi_fp16.hpp, scldm_scvi_*_ex) on the MI355X, held to the arithmetic class of the
+"""ScviVAE's fp16-operand inference path (F16Operands of csrc/scvi_tile.hpp, scldm_scvi_*_ex) on the MI355X, held to the arithmetic class of the
 reference: per tensor, rel-L2(kernel, exact) <= 1.5 x rel-L2(10-bit-operand helper, exact), exact being the helper
 (tests/scvi_class_ref.py) with no rounding - precision_class.class_gate, whose CLASS_FACTOR is not a tuning knob.  Also: the fp32
 route behind the new entries is bit-equal to the old one, run-to-run and batch-composition bit-equality, graph capture, the

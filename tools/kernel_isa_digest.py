@@ -2,7 +2,7 @@
 """One line per device symbol of a translation unit: instruction count, digest of the instruction text, digest of the kernel
 descriptor (device-only compile with build.sh's code-generation flags, no GPU needed).  Addresses and raw bytes are stripped, so two
 trees whose outputs `diff` equal compile to the same instructions.
-usage: tools/kernel_isa_digest.py [file.hip ...]    (default: the seven translation units of build.sh)"""
+usage: tools/kernel_isa_digest.py [file.hip ...]    (default: the translation units of build.sh's TUS line)"""
 import hashlib
 import os
 import re
@@ -11,7 +11,7 @@ import sys
 import tempfile
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-tus = sys.argv[1:] or [f"scldm_amd/csrc/{t}.hip" for t in "api vae_api vae_train_api train_api train_fused optim train_step".split()]
+tus = sys.argv[1:] or [f"scldm_amd/csrc/{t}.hip" for t in re.search(r'^TUS="([^"]*)"', open(os.path.join(root, "build.sh")).read(), re.M)[1].split()]
 flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-I", "include", *os.environ.get("SCLDM_HIPCC_FLAGS", "").split()]
 digest = lambda b: hashlib.sha256(b).hexdigest()[:16]
 
