@@ -1091,6 +1091,35 @@ int scldm_scvi_train_backward(scldm_scvi* h, const float* counts, const float* l
                               const float* z, const float* mu, const float* theta, const float* dmu, const float* dtheta,
                               const float* dloc, const float* dscale, const float* dz, const scldm_scvi_grads* grads, void* ws,
                               void* stream);
+/* The same step with the precision of its products as an argument (in front of ws); forward and backward of one step take the same
+ * value.  Arguments, checks, record and workspace (the two size functions serve both precisions) are those of the plain entries.
+ *   SCLDM_PREC_FP32  exactly the launches of the plain entries, which are calls of these; bit-equal results.
+ *   SCLDM_PREC_FP16  the reference's TF32 class (it trains under torch.set_float32_matmul_precision("high")): every product of the
+ *                    forward and of the backward on v_mfma_f32_32x32x16_f16 with the operand policy of scldm_scvi_forward_ex (fp32
+ *                    where the operands live, rounded to fp16 while staged, log1p in fp32 first, saturation at +-65 504, fp32
+ *                    accumulate).  BatchNorm forward and backward, SiLU and its derivative, dropout, the posterior head, the softmax
+ *                    and its backward, the bias column sums and the split sums stay fp32.  Every gradient tensor that is an operand
+ *                    (dlogit, the theta logits' gradient, each layer's da, dloc_t, dlog_scale) is staged as 2^e d with one e per
+ *                    tensor, e = 10 - floor(log2(max |d|)) (max |2^e d| in [1024, 2048); 0 for a zero or non-finite tensor; |e| <=
+ *                    126), and the product is multiplied by 2^-e, both exact: callers pass unscaled gradients, there is no loss
+ *                    scale.  max |d| is an unsigned maximum of magnitude bits formed on the device by the kernel that writes the
+ *                    tensor; the host never reads it.  The determinism statement above holds word for word.
+ *   any other value  SCLDM_ERR_SHAPE with a message, nothing launched, nothing written (checked after the arguments, before the
+ *                    packed state).
+ * scldm_scvi_train_set_found_inf registers a caller-owned device float (NULL: none) with the contract of
+ * scldm_vae_train_set_found_inf: every SCLDM_PREC_FP16 backward resets it to 0.0 at its start and sets it to 1.0 when an upstream
+ * gradient or one of the gradient tensors above is non-finite, or when a parameter gradient it produced is; an optimizer that takes
+ * GradScaler's `found_inf` (scldm_adamw_step) then skips the step on device.  The fp32 backward never touches it. */
+int scldm_scvi_train_forward_ex(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                                float p_enc, float p_dec, unsigned long long seed, unsigned char* const* masks, int masks_given,
+                                float momentum, void* record, float* loc, float* scale, float* z, float* mu, float* theta,
+                                int precision, void* ws, void* stream);
+int scldm_scvi_train_backward_ex(scldm_scvi* h, const float* counts, const float* library_size, int n_library, int B, const float* eps,
+                                 float p_enc, float p_dec, unsigned char* const* masks, const void* record, const float* scale,
+                                 const float* z, const float* mu, const float* theta, const float* dmu, const float* dtheta,
+                                 const float* dloc, const float* dscale, const float* dz, const scldm_scvi_grads* grads, int precision,
+                                 void* ws, void* stream);
+int scldm_scvi_train_set_found_inf(scldm_scvi* h, float* found_inf /* device, caller-owned, may be NULL */);
 
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the

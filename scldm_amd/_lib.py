@@ -354,6 +354,9 @@ def lib() -> C.CDLL:
                                            C.c_uint64, C.POINTER(C.c_void_p), C.c_int, C.c_float] + [C.c_void_p] * 8
     L.scldm_scvi_train_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float,
                                             C.POINTER(C.c_void_p)] + [C.c_void_p] * 10 + [C.POINTER(ScviGrads), C.c_void_p, C.c_void_p]
+    L.scldm_scvi_train_forward_ex.argtypes = L.scldm_scvi_train_forward.argtypes[:-2] + [C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_scvi_train_backward_ex.argtypes = L.scldm_scvi_train_backward.argtypes[:-2] + [C.c_int, C.c_void_p, C.c_void_p]
+    L.scldm_scvi_train_set_found_inf.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -380,7 +383,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_scvi_create", "scldm_scvi_destroy", "scldm_scvi_pack", "scldm_scvi_workspace_bytes", "scldm_scvi_encode", "scldm_scvi_decode",
            "scldm_scvi_forward",
            "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward",
-           "scldm_scvi_encode_ex", "scldm_scvi_decode_ex", "scldm_scvi_forward_ex"]
+           "scldm_scvi_encode_ex", "scldm_scvi_decode_ex", "scldm_scvi_forward_ex",
+           "scldm_scvi_train_forward_ex", "scldm_scvi_train_backward_ex", "scldm_scvi_train_set_found_inf"]
 
 
 def check(rc: int, what: str) -> None:

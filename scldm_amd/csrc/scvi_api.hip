@@ -205,7 +205,7 @@ void launch_pack(const scldm_scvi* h, int force, hipStream_t st) {
   hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, st, a);
 }
 
-int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, float* part, hipStream_t st) {
+int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, float* part, int precision, hipStream_t st) {
   GemmArgs a = {};
   a.X = X;
   a.W0 = W;
@@ -213,8 +213,8 @@ int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, 
   a.N0 = N;
   a.K = K;
   a.out0 = part;
-  if (log1p) launch_gemm<MODE_PARTIAL, true>(SCLDM_PREC_FP32, a, st);
-  else launch_gemm<MODE_PARTIAL>(SCLDM_PREC_FP32, a, st);
+  if (log1p) launch_gemm<MODE_PARTIAL, true>(precision, a, st);
+  else launch_gemm<MODE_PARTIAL>(precision, a, st);
   return splits_of(K);
 }
 

@@ -15,6 +15,7 @@ struct scldm_scvi {
   scldm_scvi_params p;            // p.enc / p.dec point at the two arrays above
   float *d_s, *d_c;               // (n_enc + n_dec, H) folded BatchNorm scale / shift
   unsigned long long* d_fp;       // pack_kernel's fingerprint state
+  float* found_inf;               // fp16 training backward: caller-owned device float (scldm_scvi_train_set_found_inf), may be NULL
 };
 
 namespace scldm {
@@ -47,8 +48,9 @@ static inline int check_packed(const char* entry, const scldm_scvi* h) {   // af
 
 // defined in scvi_api.hip, on the kernels of scvi.hpp
 void launch_pack(const scldm_scvi* h, int force, hipStream_t st);
-// raw fp32 products X (B, K) W (N, K)^T into slots [0, splits) of `part` (splits, B, N), log1p applied to X while staging; returns the splits
-int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, float* part, hipStream_t st);
+// raw products X (B, K) W (N, K)^T on the operands of `precision` into slots [0, splits) of `part` (splits, B, N), log1p applied to X
+// while staging; returns the splits
+int launch_raw(const float* X, int K, bool log1p, const float* W, int N, int B, float* part, int precision, hipStream_t st);
 // mu = library softmax_G(x W_mu^T + b), theta (shared: softplus of the parameter; else softplus(x W_theta^T + b)) of x (B, H), the
 // products on the operands of `precision` (SCLDM_PREC_FP32 or SCLDM_PREC_FP16)
 int lik_head_impl(const scldm_scvi* h, const float* x, const float* library, int B, float* mu, float* theta, float* pairs, int precision,

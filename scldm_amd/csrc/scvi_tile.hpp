@@ -24,7 +24,9 @@
 //   RowLoader      k contiguous (torch's Linear layout, used as it is): thread -> k offsets P::kPer (tid & 31) + i of rows
 //                  (tid >> 5) + 8 j; the rows may come from two matrices (a tile whose columns [32, 64) belong to a second weight)
 //   StridedLoader  k strided, the tile's row axis contiguous: thread -> row tid & 63 at k offsets (tid >> 6) + 4 j, so a wave reads
-//                  64 consecutive rows per 256-byte request
+//                  64 consecutive rows per 256-byte request (one k-value per thread and pass: F32Operands)
+//   StridedPairLoader  the same for a policy with two k-values per dword (F16Operands): thread -> one row, one k-pair per pass
+//   ScaledRowLoader / StridedPairLoader<., ., true>  multiply by the operand's power of two first (fp16 training: a gradient operand)
 // Epilogues (MODE), all in fp32:
 //   LAYER    y = SiLU(s[n] acc + c[n])                        BatchNorm1d(eval) and the Linear bias folded into (s, c)
 //   PARTIAL  partial[slot][m, n] = acc                        the raw product of one k-split; the caller sums the slots in order
@@ -168,6 +170,73 @@ struct StridedLoader {
   __device__ __forceinline__ void store(typename P::E* S, int j) const {
     const float x = LOG1P ? log1pf(v[j]) : v[j];
     P::store(&S[tr() * P::kLd + tk() + 4 * j], &x);
+  }
+};
+
+// ---- the power-of-two scale of a gradient operand (fp16 training: fp16 has TF32's mantissa but five exponent bits).  `m` is the
+// largest magnitude of the tensor as fp32 bits (sign cleared; an unsigned maximum, exact in any order).  e = 10 - floor(log2(max)),
+// so max |2^e d| lies in [1024, 2048); zero and non-finite maxima take e = 0; |e| <= 126 keeps 2^e and 2^-e normal fp32.
+__device__ __forceinline__ bool scale_max_finite(uint32_t m) { return m < 0x7f800000u; }
+__device__ __forceinline__ int scale_exponent(uint32_t m) {
+  if (m == 0u || !scale_max_finite(m)) return 0;
+  const int e = 10 - ((int)(m >> 23) - 127);
+  return min(max(e, -126), 126);
+}
+__device__ __forceinline__ float pow2_f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+__device__ __forceinline__ uint32_t magnitude_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+
+// RowLoader whose values are multiplied by `mul` (a power of two: exact in fp32) before the policy's clamp and cast
+template <class P>
+struct ScaledRowLoader : RowLoader<P, false> {
+  using Base = RowLoader<P, false>;
+  float mul;
+  __device__ __forceinline__ ScaledRowLoader(const float* base_, int r0_, int n_, size_t ld_, float mul_) : Base(base_, r0_, n_, ld_), mul(mul_) {}
+  __device__ __forceinline__ void store(typename P::E* S, int j) const {
+    float x[P::kPer];
+#pragma unroll
+    for (int i = 0; i < P::kPer; ++i) x[i] = this->v[j][i] * mul;
+    P::store(&S[(Base::lr() + 8 * j) * P::kLd + Base::lk()], x);
+  }
+};
+
+// StridedLoader for a policy that packs two consecutive k-values per dword (F16Operands).  A wave covers 32 consecutive rows of
+// two neighbouring k-pairs: lanes [0, 16) and [32, 48) rows 0-15 / 16-31 of the wave's 32 at k-pair p, lanes [16, 32) and [48, 64)
+// the same rows at k-pair p + 1, so each global load instruction reads two runs of 32 consecutive floats (128 bytes) per k-value.
+// The packed ds_write_b32 of a 32-lane group (the unit that conflicts, bank = dword mod 32) goes to dwords 36 r + p: 16 rows
+// give 4 r mod 32 = eight multiples of 4, each twice, and p, p + 1 land on neighbouring banks - 16 banks, two addresses each: a
+// two-way conflict, which costs ds_write_b32 no extra cycle.  (One row per lane, the fp32 StridedLoader's shape, would be
+// four-way: twice the cycles.)  A pair that straddles k_hi (an odd K) keeps its first half and zeroes the second.
+template <class P, bool LOG1P, bool SCALED>
+struct StridedPairLoader {
+  static_assert(P::kPer == 2 && P::kBK == 64, "two k-values per thread and pass, 32 pairs per stage");
+  const float* base;     // (K, n) with row stride ld
+  size_t ld;
+  int r0, n;
+  float mul;             // SCALED: the operand's power of two
+  float v[8][2];
+  struct Stage { int k0, k_hi; };
+  static __device__ __forceinline__ int tr() {
+    const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
+    return 32 * (w & 1) + 16 * (lane >> 5) + (lane & 15);
+  }
+  static __device__ __forceinline__ int tp() { return 2 * ((int)threadIdx.x >> 7) + (((int)threadIdx.x >> 4) & 1); }   // pass j: k-pair tp() + 4 j
+  __device__ __forceinline__ StridedPairLoader(const float* base_, int r0_, int n_, size_t ld_, float mul_ = 1.f)
+      : base(base_), ld(ld_), r0(r0_), n(n_), mul(mul_) {}
+  __device__ __forceinline__ void prepare(int) {}
+  __device__ __forceinline__ Stage stage(int k0, int k_hi) const { return Stage{k0, k_hi}; }
+  __device__ __forceinline__ void fetch(int j, const Stage& st) {
+    const int k = st.k0 + 2 * (tp() + 4 * j), r = r0 + tr();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) v[j][i] = (k + i < st.k_hi && r < n) ? base[(size_t)(k + i) * ld + r] : 0.f;
+  }
+  __device__ __forceinline__ void store(typename P::E* S, int j) const {
+    float x[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      x[i] = LOG1P ? log1pf(v[j][i]) : v[j][i];
+      if (SCALED) x[i] *= mul;
+    }
+    P::store(&S[tr() * P::kLd + 2 * (tp() + 4 * j)], x);
   }
 };
 

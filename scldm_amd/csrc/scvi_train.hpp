@@ -1,6 +1,7 @@
 // Training kernels of the scVI-style baseline VAE (ScviVAE; the reference trains it with VAEScvi.training_step, models.py:942-1113):
 // BatchNorm1d in training mode forward and backward, the dropout mask, the two heads' backward and the products a backward needs.
-// Exact fp32 (scvi::F32Operands).  The training forward takes its raw products from scvi::gemm_kernel (MODE_PARTIAL, launched by
+// The products run on exact fp32 operands (scvi::F32Operands) or on fp16 operands (scvi::F16Operands, the reference's TF32 class);
+// everything else is fp32 in both.  The training forward takes its raw products from scvi::gemm_kernel (MODE_PARTIAL, launched by
 // scvi_api.hip).  Philox4x32-10 is the project's, from fm_step_common.hpp.
 //
 // prod_kernel is the tile product of scvi_tile.hpp with the loaders a backward needs:
@@ -9,6 +10,14 @@
 // log1p is applied to the B operand while staging (dW_0 = da_0^T log1p(X)).  K above kScviSplit is cut into blockIdx.z splits of that
 // many k-values - a function of K alone - written as slots of a partial buffer which sum_slots_kernel adds in slot order.  No float
 // atomics anywhere: every sum below has one fixed order.
+//
+// fp16 operands: a gradient tensor that is an operand (always A: dlogit, the theta logits' gradient, every layer's da, dloc_t,
+// dlog_scale) carries one power of two per TENSOR - K is the batch in a weight gradient, so a per-cell scale would not factor out of
+// the sum.  The kernel that produces the tensor (template parameter F16 of lik_backward_kernel, bn_backward_kernel and
+// post_backward_kernel) leaves the maximum of its magnitude bits in a slot of the workspace (unsigned integer maximum: exact in any
+// order); prod_kernel<F16Operands, ...> reads the slot, multiplies A by 2^e while staging (scvi::scale_exponent) and its result by
+// 2^-e, both exact.  The host never reads a slot.  The same instantiations raise the caller's overflow flag (found_inf) on a
+// non-finite maximum or result.  The F16 = false instantiations are the fp32 kernels, instruction for instruction.
 #pragma once
 #include <type_traits>
 
@@ -28,32 +37,68 @@ struct ProdArgs {
   int k_per_split;       // k-values per blockIdx.z (multiple of kBK)
   float* out;            // (slots, M, N); this launch writes slots slot0 + blockIdx.z
   int slot0;
+  const uint32_t* a_max; // F16Operands: the magnitude-bit maximum of A (a gradient tensor)
+  float* found_inf;      // F16Operands: set to 1 on a non-finite maximum or result; may be NULL
 };
 
-template <bool AT, bool LOG1P_B>
+template <class P, bool AT, bool LOG1P_B>
 __global__ __launch_bounds__(256) void prod_kernel(const ProdArgs a) {
-  using P = scvi::F32Operands;
-  using LA = std::conditional_t<AT, scvi::StridedLoader<P, false>, scvi::RowLoader<P, false>>;
   __shared__ __attribute__((aligned(16))) unsigned char smem[scvi::kStageBytes<P>];
-  LA la(a.A, blockIdx.y * scvi::kBM, a.M, a.lda);
-  scvi::StridedLoader<P, LOG1P_B> lb(a.Bm, blockIdx.x * scvi::kBN, a.N, a.ldb);
-  const int k_lo = blockIdx.z * a.k_per_split;
-  const int k_hi = min(a.K, k_lo + a.k_per_split);
-  const f32x16 acc = scvi::tile_product<P>(la, lb, smem, k_lo, k_hi);
-  scvi::GemmArgs g = {};
-  g.M = a.M;
-  g.N0 = a.N;
-  g.out0 = a.out;
-  scvi::tile_epilogue<scvi::MODE_PARTIAL>(g, acc, nullptr, a.slot0 + blockIdx.z);
+  if constexpr (std::is_same_v<P, scvi::F32Operands>) {      // statement for statement the fp32 kernel as it was (its code generation follows the order)
+    using LA = std::conditional_t<AT, scvi::StridedLoader<P, false>, scvi::RowLoader<P, false>>;
+    LA la(a.A, blockIdx.y * scvi::kBM, a.M, a.lda);
+    scvi::StridedLoader<P, LOG1P_B> lb(a.Bm, blockIdx.x * scvi::kBN, a.N, a.ldb);
+    const int k_lo = blockIdx.z * a.k_per_split;
+    const int k_hi = min(a.K, k_lo + a.k_per_split);
+    const f32x16 acc = scvi::tile_product<P>(la, lb, smem, k_lo, k_hi);
+    scvi::GemmArgs g = {};
+    g.M = a.M;
+    g.N0 = a.N;
+    g.out0 = a.out;
+    scvi::tile_epilogue<scvi::MODE_PARTIAL>(g, acc, nullptr, a.slot0 + blockIdx.z);
+  } else {
+    using LA = std::conditional_t<AT, scvi::StridedPairLoader<P, false, true>, scvi::ScaledRowLoader<P>>;
+    const uint32_t mx = *a.a_max;
+    const int e = scvi::scale_exponent(mx);
+    LA la(a.A, blockIdx.y * scvi::kBM, a.M, a.lda, scvi::pow2_f(e));
+    scvi::StridedPairLoader<P, LOG1P_B, false> lb(a.Bm, blockIdx.x * scvi::kBN, a.N, a.ldb);
+    const int k_lo = blockIdx.z * a.k_per_split;
+    const int k_hi = min(a.K, k_lo + a.k_per_split);
+    f32x16 acc = scvi::tile_product<P>(la, lb, smem, k_lo, k_hi);
+    scvi::GemmArgs g = {};
+    g.M = a.M;
+    g.N0 = a.N;
+    g.out0 = a.out;
+    const float inv = scvi::pow2_f(-e);
+    bool bad = !scvi::scale_max_finite(mx);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[r] *= inv;
+      bad |= !scvi::scale_max_finite(scvi::magnitude_bits(acc[r]));
+    }
+    if (bad && a.found_inf) *a.found_inf = 1.0f;
+    scvi::tile_epilogue<scvi::MODE_PARTIAL>(g, acc, nullptr, a.slot0 + blockIdx.z);
+  }
 }
 
+// the block's maximum of `m` (every thread of the block calls it) into *slot
+__device__ __forceinline__ void block_max_to_slot(uint32_t m, uint32_t* slot) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+  if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
+}
+__device__ __forceinline__ bool finite_f(float x) { return scvi::scale_max_finite(scvi::magnitude_bits(x)); }
+
 // out = slot 0 + slot 1 + ... in slot order
-__global__ __launch_bounds__(256) void sum_slots_kernel(const float* __restrict__ part, int slots, size_t plane, float* __restrict__ out) {
+template <bool F16>
+__global__ __launch_bounds__(256) void sum_slots_kernel(const float* __restrict__ part, int slots, size_t plane, float* __restrict__ out,
+                                                        float* found_inf) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= plane) return;
   float v = part[i];
   for (int z = 1; z < slots; ++z) v += part[z * plane + i];
   out[i] = v;
+  if (F16 && found_inf && !finite_f(v)) *found_inf = 1.0f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -153,10 +198,13 @@ struct BnBwdArgs {
   float p;
   int B, H;
   float *dgamma, *dbeta, *dbias;
+  uint32_t* da_max;      // F16: slot of da's magnitude-bit maximum
+  float* found_inf;      // F16: set to 1 on a non-finite dgamma / dbeta; may be NULL
 };
 
 // dy = dh keep / (1 - p) SiLU'(gamma xhat + beta);  dbeta = sum dy, dgamma = sum dy xhat;  da = gamma rstd (dy - mean(dy) - xhat
 // mean(dy xhat));  the Linear bias in front of a training-mode BatchNorm has the gradient zero, written as such.
+template <bool F16>
 __global__ __launch_bounds__(256) void bn_backward_kernel(const BnBwdArgs a) {
   __shared__ float red[kRowGroups][kColTile];
   const int c = blockIdx.x * kColTile + threadIdx.x % kColTile, rg = threadIdx.x / kColTile;
@@ -177,21 +225,42 @@ __global__ __launch_bounds__(256) void bn_backward_kernel(const BnBwdArgs a) {
   }
   s1 = col_total(red, s1);
   s2 = col_total(red, s2);
-  if (!ok) return;
-  if (rg == 0) {
-    a.dbeta[c] = s1;
-    a.dgamma[c] = s2;
-    a.dbias[c] = 0.f;
-  }
-  const float m1 = s1 / (float)a.B, m2 = s2 / (float)a.B, gr = g * a.rstd[c];
-  for (int r = rg; r < a.B; r += kRowGroups) {
-    const size_t i = (size_t)r * a.H + c;
-    a.d[i] = gr * (a.d[i] - m1 - a.xhat[i] * m2);
+  if constexpr (!F16) {
+    if (!ok) return;
+    if (rg == 0) {
+      a.dbeta[c] = s1;
+      a.dgamma[c] = s2;
+      a.dbias[c] = 0.f;
+    }
+    const float m1 = s1 / (float)a.B, m2 = s2 / (float)a.B, gr = g * a.rstd[c];
+    for (int r = rg; r < a.B; r += kRowGroups) {
+      const size_t i = (size_t)r * a.H + c;
+      a.d[i] = gr * (a.d[i] - m1 - a.xhat[i] * m2);
+    }
+  } else {      // the same, every thread staying for the block's maximum of |da|
+    uint32_t mx = 0u;
+    if (ok) {
+      if (rg == 0) {
+        a.dbeta[c] = s1;
+        a.dgamma[c] = s2;
+        a.dbias[c] = 0.f;
+        if (a.found_inf && !(finite_f(s1) && finite_f(s2))) *a.found_inf = 1.0f;
+      }
+      const float m1 = s1 / (float)a.B, m2 = s2 / (float)a.B, gr = g * a.rstd[c];
+      for (int r = rg; r < a.B; r += kRowGroups) {
+        const size_t i = (size_t)r * a.H + c;
+        const float da = gr * (a.d[i] - m1 - a.xhat[i] * m2);
+        a.d[i] = da;
+        mx = max(mx, scvi::magnitude_bits(da));
+      }
+    }
+    block_max_to_slot(mx, a.da_max);
   }
 }
 
 // out[c] = sum over the B rows of X[., c]
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, int B, int N, float* __restrict__ out) {
+template <bool F16>
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, int B, int N, float* __restrict__ out, float* found_inf) {
   __shared__ float red[kRowGroups][kColTile];
   const int c = blockIdx.x * kColTile + threadIdx.x % kColTile, rg = threadIdx.x / kColTile;
   float s = 0.f;
@@ -199,6 +268,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
     for (int r = rg; r < B; r += kRowGroups) s += X[(size_t)r * N + c];
   s = col_total(red, s);
   if (c < N && rg == 0) out[c] = s;
+  if (F16 && c < N && rg == 0 && found_inf && !finite_f(s)) *found_inf = 1.0f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -227,20 +297,41 @@ __global__ __launch_bounds__(256) void post_forward_kernel(const float* __restri
   z[i] = lo + eps[i] * sc;
 }
 
+template <bool F16>
 __global__ __launch_bounds__(256) void post_backward_kernel(const float* __restrict__ dz, const float* __restrict__ dz_dec,
                                                             const float* __restrict__ dloc, const float* __restrict__ dscale,
                                                             const float* __restrict__ eps, const float* __restrict__ scale,
                                                             const float* __restrict__ ls_pre, int n, float* __restrict__ dloc_t,
-                                                            float* __restrict__ dls) {
+                                                            float* __restrict__ dls, uint32_t* dloc_max, uint32_t* dls_max,
+                                                            float* found_inf) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float g = dz ? dz[i] : 0.f;
-  if (dz_dec) g += dz_dec[i];
-  const float dl = (dloc ? dloc[i] : 0.f) + g;
-  const float ds = (dscale ? dscale[i] : 0.f) + g * eps[i];
-  const float ls = ls_pre[i];
-  dloc_t[i] = dl;
-  dls[i] = (ls > -7.f && ls < 5.f) ? ds * scale[i] : 0.f;
+  if constexpr (!F16) {
+    if (i >= n) return;
+    float g = dz ? dz[i] : 0.f;
+    if (dz_dec) g += dz_dec[i];
+    const float dl = (dloc ? dloc[i] : 0.f) + g;
+    const float ds = (dscale ? dscale[i] : 0.f) + g * eps[i];
+    const float ls = ls_pre[i];
+    dloc_t[i] = dl;
+    dls[i] = (ls > -7.f && ls < 5.f) ? ds * scale[i] : 0.f;
+  } else {      // the same, every thread staying for the two maxima; an upstream gradient behind a closed hardtanh gate is checked too
+    uint32_t m_dl = 0u, m_ds = 0u;
+    if (i < n) {
+      float g = dz ? dz[i] : 0.f;
+      if (dz_dec) g += dz_dec[i];
+      const float dl = (dloc ? dloc[i] : 0.f) + g;
+      const float ds = (dscale ? dscale[i] : 0.f) + g * eps[i];
+      const float ls = ls_pre[i];
+      const float dv = (ls > -7.f && ls < 5.f) ? ds * scale[i] : 0.f;
+      dloc_t[i] = dl;
+      dls[i] = dv;
+      m_dl = scvi::magnitude_bits(dl);
+      m_ds = scvi::magnitude_bits(dv);
+      if (found_inf && !finite_f(ds)) *found_inf = 1.0f;
+    }
+    block_max_to_slot(m_dl, dloc_max);
+    block_max_to_slot(m_ds, dls_max);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -249,11 +340,13 @@ __global__ __launch_bounds__(256) void post_backward_kernel(const float* __restr
 // dtheta_logit = dtheta softplus'(.) with softplus'(x) = 1 - exp(-theta) (= sigmoid(x); 1 above torch's threshold 20).  Workgroup 0
 // also forms the shared theta's dtheta_param = dtheta softplus'(theta_param).
 // ------------------------------------------------------------------------------------------------
+template <bool F16>
 __global__ __launch_bounds__(256) void lik_backward_kernel(const float* __restrict__ mu, const float* __restrict__ theta,
                                                            const float* __restrict__ dmu, const float* __restrict__ dtheta,
                                                            const float* __restrict__ library, int G, int shared_theta,
                                                            const float* __restrict__ theta_param, float* __restrict__ dlogit,
-                                                           float* __restrict__ dtlogit, float* __restrict__ dtheta_param) {
+                                                           float* __restrict__ dtlogit, float* __restrict__ dtheta_param,
+                                                           uint32_t* dlogit_max, uint32_t* dtlogit_max, float* found_inf) {
   __shared__ float red[4];
   const int row = blockIdx.x, tid = threadIdx.x;
   const size_t o = (size_t)row * G;
@@ -266,19 +359,30 @@ __global__ __launch_bounds__(256) void lik_backward_kernel(const float* __restri
   __syncthreads();
   s = ((red[0] + red[1]) + red[2]) + red[3];
   const float lib = library[row];
+  uint32_t m_dl = 0u, m_dt = 0u;      // (F16 only)
   for (int g = tid; g < G; g += 256) {
     const float m = mu[o + g];
-    dlogit[o + g] = (dmu && lib != 0.f) ? m * dmu[o + g] - (m / lib) * s : 0.f;
+    const float dl = (dmu && lib != 0.f) ? m * dmu[o + g] - (m / lib) * s : 0.f;
+    dlogit[o + g] = dl;
+    if (F16) m_dl = max(m_dl, scvi::magnitude_bits(dl));
     if (!shared_theta) {
       const float t = theta[o + g];
-      dtlogit[o + g] = dtheta ? dtheta[o + g] * (t > 20.f ? 1.f : -expm1f(-t)) : 0.f;
+      const float dt = dtheta ? dtheta[o + g] * (t > 20.f ? 1.f : -expm1f(-t)) : 0.f;
+      dtlogit[o + g] = dt;
+      if (F16) m_dt = max(m_dt, scvi::magnitude_bits(dt));
     }
   }
   if (shared_theta && row == 0)
     for (int g = tid; g < G; g += 256) {
       const float x = theta_param[g];
-      dtheta_param[g] = dtheta ? dtheta[g] * (x > 20.f ? 1.f : sigmoid_f(x)) : 0.f;
+      const float dp = dtheta ? dtheta[g] * (x > 20.f ? 1.f : sigmoid_f(x)) : 0.f;
+      dtheta_param[g] = dp;
+      if (F16 && found_inf && !finite_f(dp)) *found_inf = 1.0f;
     }
+  if constexpr (F16) {
+    block_max_to_slot(m_dl, dlogit_max);
+    if (!shared_theta) block_max_to_slot(m_dt, dtlogit_max);
+  }
 }
 
 }  // namespace scvi_train

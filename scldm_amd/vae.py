@@ -528,10 +528,17 @@ class ScviVAE(nn.Module):
 
     fp16 operands are opt-in as well: with `fp16_enabled = True`, `precision = "fp16"` runs every product of the eval-mode calls on
     the same kernel on csrc/scvi_tile.hpp's F16Operands (operands rounded to fp16, fp32 accumulate and epilogues: the reference's TF32 class).  With the
-    default the setter refuses everything but "fp32" as before; training is fp32 whatever the switch says."""
+    default the setter refuses everything but "fp32" as before; training is fp32 whatever that switch says.
+
+    Training on fp16 operands is a third opt-in: with `train_enabled`, `fp16_enabled` and `train_fp16_enabled = True`,
+    `precision = "fp16"` runs the training forward and backward through scldm_scvi_train_forward_ex / _backward_ex on fp16 operands
+    (the class the reference trains in).  Gradient operands carry one power of two per tensor, formed on the device, so callers pass
+    unscaled gradients and use no loss scale; `found_inf_flag()` is the overflow flag.  With the default, training at
+    `precision = "fp16"` is refused as before."""
 
     train_enabled = False
     fp16_enabled = False
+    train_fp16_enabled = False
 
     def __init__(self, encoder: EncoderScvi, encoder_head: GaussianLinearLayer, decoder: DecoderScvi,
                  decoder_head: NegativeBinomialLinearLayer, prior: nn.Module):
@@ -635,7 +642,25 @@ class ScviVAE(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _ws=None, _keep=None, _train_ws=None, last_dropout_masks=None)
+        for k in ("_found_inf", "_found_inf_handle"):      # (the flag is registered with the handle that does not travel)
+            state.pop(k, None)
         return state
+
+    def found_inf_flag(self) -> torch.Tensor:
+        """Device float the fp16 training backward sets to 1.0 when an upstream gradient, an intermediate gradient tensor or a
+        parameter gradient it produced is non-finite (reset to 0.0 at the start of every fp16 backward): hand it to an optimizer that
+        understands GradScaler's `found_inf` (`scldm_amd.optim.AdamW`: `optimizer.found_inf = vae.found_inf_flag()`), which then
+        skips the step on device, no host read.  The contract of TransformerVAE.found_inf_flag()."""
+        L, h = (_lib.lib(), self._handle) if self._handle is not None else self._native()
+        dev = self.decoder_head.mu.weight.device
+        flag = self.__dict__.get("_found_inf")
+        if flag is None or flag.device != dev:
+            flag = self.__dict__["_found_inf"] = torch.zeros((), dtype=torch.float32, device=dev)
+            self.__dict__["_found_inf_handle"] = None
+        if self.__dict__.get("_found_inf_handle") != h.value:     # (re-)register with THIS handle (a copy starts with none)
+            _lib.check(L.scldm_scvi_train_set_found_inf(h, flag.data_ptr()), "scldm_scvi_train_set_found_inf")
+            self.__dict__["_found_inf_handle"] = h.value
+        return flag
 
     def __del__(self):
         try:
@@ -767,7 +792,7 @@ class ScviVAE(nn.Module):
         return self._train_ws.data_ptr()
 
     def _train_forward(self, counts, library_size, eps, seed, dropout_masks):
-        if self._precision != "fp32":
+        if self._precision != "fp32" and not (self.train_fp16_enabled and self.fp16_enabled and self._precision == "fp16"):
             raise NotImplementedError(f"ScviVAE trains in exact fp32 only (precision={self._precision!r})")
         for name, t in (("counts", counts), ("library_size", library_size), ("eps", eps)):
             if isinstance(t, torch.Tensor) and t.requires_grad:
@@ -835,7 +860,8 @@ class ScviVAE(nn.Module):
 
 
 class _ScviTrainFn(torch.autograd.Function):
-    """ScviVAE's training forward and backward: scldm_scvi_train_forward / scldm_scvi_train_backward (include/scldm_hip.h)."""
+    """ScviVAE's training forward and backward: scldm_scvi_train_forward_ex / scldm_scvi_train_backward_ex (include/scldm_hip.h), the
+    backward in the precision its forward ran in."""
 
     @staticmethod
     def forward(ctx, module, counts, lib, eps, seed, masks, masks_given, *params):
@@ -851,12 +877,13 @@ class _ScviTrainFn(torch.autograd.Function):
         p_enc, p_dec = float(module.encoder.dropout), float(module.decoder.dropout)
         momentum = float(module.encoder.encoder_mlp[1].momentum)
         ws = module._train_workspace(L, B)
+        prec = _lib.PRECISIONS[module._precision]
         with torch.cuda.device(dev):
-            _lib.check(L.scldm_scvi_train_forward(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), p_enc, p_dec,
-                                                  C.c_uint64(seed), mask_ptrs, int(masks_given), momentum, record.data_ptr(),
-                                                  loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(), ws,
-                                                  _stream_ptr()), "scldm_scvi_train_forward")
-        ctx.module, ctx.masks, ctx.rates = module, masks, (p_enc, p_dec)
+            _lib.check(L.scldm_scvi_train_forward_ex(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), p_enc, p_dec,
+                                                     C.c_uint64(seed), mask_ptrs, int(masks_given), momentum, record.data_ptr(),
+                                                     loc.data_ptr(), scale.data_ptr(), z.data_ptr(), mu.data_ptr(), theta.data_ptr(),
+                                                     prec, ws, _stream_ptr()), "scldm_scvi_train_forward_ex")
+        ctx.module, ctx.masks, ctx.rates, ctx.prec = module, masks, (p_enc, p_dec), prec
         # the parameters too: the backward reads the weights through the handle's pointers, so an in-place update between forward
         # and backward (an optimizer step before a second backward with retain_graph) must raise autograd's version error
         ctx.save_for_backward(counts, lib, eps, record, scale, z, mu, theta, *params)
@@ -887,8 +914,8 @@ class _ScviTrainFn(torch.autograd.Function):
         ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         ws = module._train_workspace(L, B)
         with torch.cuda.device(counts.device):
-            _lib.check(L.scldm_scvi_train_backward(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), ctx.rates[0],
-                                                   ctx.rates[1], mask_ptrs, record.data_ptr(), scale.data_ptr(), z.data_ptr(),
-                                                   mu.data_ptr(), theta.data_ptr(), *[ptr(t) for t in ups], C.byref(g), ws,
-                                                   _stream_ptr()), "scldm_scvi_train_backward")
+            _lib.check(L.scldm_scvi_train_backward_ex(h, counts.data_ptr(), lib.data_ptr(), lib.shape[0], B, eps.data_ptr(), ctx.rates[0],
+                                                      ctx.rates[1], mask_ptrs, record.data_ptr(), scale.data_ptr(), z.data_ptr(),
+                                                      mu.data_ptr(), theta.data_ptr(), *[ptr(t) for t in ups], C.byref(g), ctx.prec, ws,
+                                                      _stream_ptr()), "scldm_scvi_train_backward_ex")
         return (None,) * 7 + tuple(g_ if p.requires_grad else None for g_, p in zip(grads, params))

@@ -41,6 +41,12 @@ for tu in tus:
                 cur = syms.setdefault(m[1], [])
             elif cur is not None and line.startswith("\t"):
                 cur.append(" ".join(line.split("//")[0].split()))
+        # a symbol ends at its last s_endpgm: what follows is the padding of its section (s_code_end / s_nop / elided zeros), which
+        # depends on where the linker put the symbol (last of .text, or a template instantiation in a section of its own)
+        for body in syms.values():
+            ends = [i for i, ins in enumerate(body) if ins.startswith("s_endpgm")]
+            if ends:
+                del body[ends[-1] + 1:]
     print(f"# {tu}: {len(syms)} symbols, {sum(map(len, syms.values()))} instructions")
     for name in sorted(syms):
         print(f"{tu} | {name} | {len(syms[name])} insts | isa {digest(chr(10).join(syms[name]).encode())} | kd {kd.get(name, '-')}")
