@@ -22,13 +22,18 @@ namespace scldm {
 // m16 (FT=2, 16-bit policies; dit_forward.hpp: gemm_pass_tile16): the W12 units of a chunk (and of the trailing half chunk) are
 // 16-row x 32-k fragments instead - unit vv = k-step (vv & 7) of 32 of tile vv >> 3, fragment 0 = w1[hid], fragment 1 = w2[hid],
 // hid = c*128 + (w*2 + tile)*16 + (l&15), k = 32*(vv & 7) + (l>>4)*8 + j.  Same units, same bytes.
-// m16 also moves whole 64-row passes to 16x16 tiles (dit_forward.hpp: gemm_pass16; one switch per pass, kM16Proj / kM16Down):
+// m16 also moves whole 64-row passes to 16x16 tiles (dit_forward.hpp: gemm_pass16; one switch per pass, kM16Proj / kM16Down /
+// kM16QK / kM16V):
 // a 32-k step of such a pass is two consecutive units; pass-local unit v holds k-step v >> 1 and row pair
 // v & 1, its fragment ft the row tile R4 = 2 (v & 1) + ft: lane l, element j = row 16 R4 + (l&15) of the wave's 64 rows,
 // k = 32 (v >> 1) + (l>>4)*8 + j.
 //   c_proj (units 48-63): wave rows w*64 + 16 R4 + (l&15)
 //   mlp.c_proj (chunk units 16-23, half-chunk units 8-11): k is the hidden index c*128 + 32 (v >> 1) + (l>>4)*8 + j, exact
 //   zeros for hid >= H
+//   Q / K of head h (units 16 h .. 16 h + 15, kM16QK): row tiles 0, 1 = the head's Q rows, 2, 3 = its K rows; row r16 of tile
+//   T = R4 & 1 is head dim 8 T + 16 (r16 >> 3) + 4 ((r16 >> 2) & 1) + (r16 & 3), Q and K alike - a lane's pack8 of its two Q (K)
+//   tiles' registers is then k-group l >> 4 of the score product, in the k slots of the 32x32 form (dit_forward.hpp: scores16)
+//   V (units 32-47, kM16V): c_attn rows 512 + w*64 + 16 R4 + (l&15), natural order (consumed with swapped operands)
 // Every other unit is unchanged.
 // ------------------------------------------------------------------------------------------------
 // One element of a layer's packed stream (index documented above); FT = 32-row tiles per wave.
@@ -51,6 +56,15 @@ __device__ __forceinline__ float pack_layer_val(const float* __restrict__ Wqkv, 
   if (u >= 48 && u < 64 && m16 && kM16Proj) {
     const int v = u - 48;
     val = Wproj[(size_t)(w * 64 + row64(v)) * 256 + (v >> 1) * 32 + k16];
+  } else if (u < 32 && m16 && kM16QK) {
+    // Q and K of ONE head per pass on 16x16 tiles: row tiles 0, 1 = the head's Q rows, 2, 3 = its K rows, head dims permuted
+    // (Q and K alike: scores unchanged): tile T = R4 & 1, row r16 = head dim 8 T + 16 (r16 >> 3) + 4 ((r16 >> 2) & 1) + (r16 & 3)
+    const int head = u >> 4, v = u & 15, R4 = 2 * (v & 1) + ft;
+    const int dim = 8 * (R4 & 1) + 16 * (r16 >> 3) + 4 * ((r16 >> 2) & 1) + (r16 & 3);
+    val = Wqkv[(size_t)((R4 >> 1) * 256 + (w * 2 + head) * 32 + dim) * 256 + (v >> 1) * 32 + k16];
+  } else if (u >= 32 && u < 48 && m16 && kM16V) {
+    const int v = u - 32;
+    val = Wqkv[(size_t)(2 * 256 + w * 64 + row64(v)) * 256 + (v >> 1) * 32 + k16];
   } else if (u < 32 && FT == 2) {
     // Q and K of ONE head per pass: units 0-15 = head 0, 16-31 = head 1; inside a unit fragment 0 is the head's Q tile and
     // fragment 1 its K tile of the same k-step (an ordinary two-tile gemm_pass whose "feature tiles" are Q_h and K_h)

@@ -66,10 +66,14 @@ constexpr int kDbgStamps = 32;
 constexpr int kGemmPassPrio = 1;
 // Which GEMM passes of the M16 instantiations (16-bit policies, FT = 2) run on 16x16x32 MFMA tiles besides the SwiGLU
 // up-projection; the weight packer (dit_aux.hpp: pack_layer_val, m16) reads the same constants, so a pass is moved or left
-// behind by its switch alone.  A moved pass hands its result back in the 32x32 accumulator layout (relayout16), so nothing
-// downstream of it changes.  Measurements, and the Q/K and V passes left on 32x32 tiles (they spill): DESIGN section 4.1 / 8.
+// behind by its switch alone.  c_proj and W3 hand their result back in the 32x32 accumulator layout (relayout16), so nothing
+// downstream of them changes.  Q/K and V are not handed back (that relayout spills): with their switches the attention core
+// itself runs on 16x16 tiles, one cell (16 tokens, head_dim 32 = the M/N and the K of 16x16x32) per tile - the pass outputs are
+// already MFMA operands and the P V output is already in the layout of the AO store.  Measurements: DESIGN section 4.1 / 8.
 constexpr bool kM16Proj = true;    // attention c_proj
 constexpr bool kM16Down = true;    // SwiGLU down-projection (W3)
+constexpr bool kM16QK = true;      // Q / K passes, scores and softmax (head dims packed permuted: pack_layer_val)
+constexpr bool kM16V = true;       // V pass, P V and the AO store
 // layer slots instantiated in the fused kernel (code size grows with it: ~30 KB of ISA per slot): EIGHT for the inference
 // kernels - the whole reference network in one launch, no residual hand-off through HBM at all (same-box interleaved A/B,
 // profiles/r4a_ab_lpl8_l2warm.txt: +0.8 % at 4 096 cells, +2.0 % at 1 024, +1.9 % at 512 over four); four for the recording
@@ -402,7 +406,8 @@ __device__ __forceinline__ void gemm_pass_tile16(f32x4 (&a1)[2 * NTT], f32x4 (&b
 // accumulator chain over k in natural order, 8-element groups, the bias as the initial C operand: the bits of gemm_pass.
 // ZERO: tile (R4, *) starts from init[R4] (a per-row bias tile: rows 4 (l >> 4)..+3 of the row tile) or from zero.  The pass's
 // first 32-k step spans TWO units, and `first` holds for both: unit 0 initialises row tiles 0 and 1, unit 1 row tiles 2 and 3.
-template <typename OP, int NTT, int KSTEPS32, bool ZERO, int PF>
+// SWAP: the transposed tiles (mma16(b, w): rows = the 16 tokens of j, cols = the 16 features of R4) - the V pass.
+template <typename OP, int NTT, int KSTEPS32, bool ZERO, int PF, bool SWAP = false>
 __device__ __forceinline__ void gemm_pass16(f32x4 (&t)[4][2 * NTT], WStream<OP, PF, 2>& ws, const typename OP::E* __restrict__ bsm,
                                             int ldb, int lane, const f32x4* init = nullptr) {
   using Frag = typename OP::Frag;
@@ -415,19 +420,20 @@ __device__ __forceinline__ void gemm_pass16(f32x4 (&t)[4][2 * NTT], WStream<OP, 
   Frag b[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) b[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb);
+  auto mm = [&](const Frag& w, const Frag& x, const f32x4& c) { return SWAP ? OP::mma16(x, w, c) : OP::mma16(w, x, c); };
   auto kstep = [&](int k, int s, bool first) {   // s = ring slot of unit 2 k
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      t[0][j] = OP::mma16(ws.ring[s][0], b[j], first ? (init ? init[0] : zero) : t[0][j]);
-      t[1][j] = OP::mma16(ws.ring[s][1], b[j], first ? (init ? init[1] : zero) : t[1][j]);
+      t[0][j] = mm(ws.ring[s][0], b[j], first ? (init ? init[0] : zero) : t[0][j]);
+      t[1][j] = mm(ws.ring[s][1], b[j], first ? (init ? init[1] : zero) : t[1][j]);
     }
     ws.ring[s][0] = ws.fetch(0);
     ws.ring[s][1] = ws.fetch(1);
     ws.advance(2);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      t[2][j] = OP::mma16(ws.ring[s + 1][0], b[j], first ? (init ? init[2] : zero) : t[2][j]);
-      t[3][j] = OP::mma16(ws.ring[s + 1][1], b[j], first ? (init ? init[3] : zero) : t[3][j]);
+      t[2][j] = mm(ws.ring[s + 1][0], b[j], first ? (init ? init[2] : zero) : t[2][j]);
+      t[3][j] = mm(ws.ring[s + 1][1], b[j], first ? (init ? init[3] : zero) : t[3][j]);
       // after the last k-step: k-step 0 again, never used (the read stays inside the row)
       b[j] = *reinterpret_cast<const Frag*>(bbase + j * 16 * ldb + ((k + 1) & (KSTEPS32 - 1)) * 32);
     }
@@ -481,8 +487,19 @@ __device__ __forceinline__ void relayout16_all(const f32x4 (&t)[4][2 * NTT], f32
       for (int R = 0; R < 2; ++R) relayout16(t[2 * ft + R][2 * tt], t[2 * ft + R][2 * tt + 1], acc[ft][tt], R);
 }
 
+// Reductions across the two 16-lane groups of each 32-lane half (lane ^ 16) with v_permlane16_swap: swap(v, v) yields the even
+// group's v and the odd group's v in every lane of the pair - the operand order of xor32_sum / xor32_max (common.hpp).
+__device__ __forceinline__ float xor16_sum(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float xor16_max(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
 #ifdef SCLDM_PHASE_TIMING
-#define SCLDM_LN_STAMP(i)                                                                              \
+#define SCLDM_LN_STAMP(i)                                                                             \
   do {                                                                                                 \
     if (SB >= 0 && dbg && lane == 0) dbg[((size_t)blockIdx.x * 8 + wave) * kDbgStamps + SB + (i)] = __builtin_readcyclecounter(); \
   } while (0)
@@ -623,8 +640,9 @@ __device__ __forceinline__ void ln_modulate_store(const float (&v)[FT][NTT][16],
 }
 
 // M16 (16-bit policies, FT = 2): the SwiGLU up-projection (gemm_pass_tile16) and the passes switched on by kM16Proj / kM16Down
-// (gemm_pass16 + relayout16) run on 16x16 tiles from a stream packed for them (pack_layer_val, m16); the other passes, the
-// attention core, the residual and the record stay on 32x32 tiles.  SCLDM_FWD_MFMA=32 selects M16 = false.
+// (gemm_pass16 + relayout16) run on 16x16 tiles from a stream packed for them (pack_layer_val, m16); with kM16QK / kM16V the
+// Q / K / V passes and the attention core do too, one cell per tile and without a relayout.  The residual and the record stay in
+// the 32x32 accumulator layout.  SCLDM_FWD_MFMA=32 selects M16 = false.
 template <typename OP, int NTT, int FT, bool REC = false, bool M16 = false>
 __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 1) ? 2 : 1) void dit_forward_kernel(const FwdArgs a) {
   static_assert(!M16 || (FT == 2 && sizeof(typename OP::E) == 2 && sizeof(typename OP::Frag) == 16), "M16: 16-bit policies, FT = 2");
@@ -886,8 +904,74 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
   // ---- attention for this wave's FT heads, entirely in registers ----
   //   Q pass, K pass -> S^T = K Q^T -> softmax -> P  (Q, K fragments die here: keeps the live MFMA
   //   operand set inside the architectural VGPRs) -> V pass -> O^T = V^T P^T (kept in acc).
+  // The 16x16 form (M16; kM16QK / kM16V): one cell per tile.  Its softmax and P live in the lane order (sample of the pair
+  // sp = lane >> 5, key half hh = (lane >> 4) & 1, query lane & 15) - the 32x32 form's (hh = lane >> 5, sp = (lane >> 4) & 1)
+  // with lane bits 4 and 5 exchanged, same registers, same arithmetic.  tests/test_attn16_lanes_cpu.py restates the lane algebra.
+  constexpr bool kQK16 = M16 && kM16QK, kV16 = M16 && kM16V;
+  Quad po[kV16 ? 4 : 1][kV16 ? 2 * NTT : 1];   // kV16: the attention output, packed: po[R4][cell], lane l = dims 16 R4 + 4 (l >> 4)..+3 of query l & 15
   {
     Frag Pf[FT][NTT][2];
+    // kQK16: scores + softmax of one head from the Q/K pass's tiles t[R4][cell] (R4 = 0, 1: Q rows, 2, 3: K rows, head dims
+    // permuted by the packer so that pack8(tile 0, tile 1) of lane group g is k-group g of the 32x32 form's two chained operands).
+    // S^T of a cell is ONE mma16; per register one permlane32_swap of the pair's two tiles gives the 32x32 form's sv[8]
+    // (lanes 0-31: the even cell's keys 4 hh..+3 | 8 + 4 hh..+3 of their query, lanes 32-63: the odd cell's).
+    auto scores16 = [&](const f32x4 (&t)[4][2 * NTT], Frag (&Ph)[NTT][2]) {
+      if constexpr (kQK16) {   // (the other policies have no mma16)
+        const int sp16 = lane >> 5;
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+          f32x4 S[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int c = 2 * tt + e;
+            float qv[8], kv[8];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              qv[i] = t[0][c][i]; qv[4 + i] = t[1][c][i];
+              kv[i] = t[2][c][i]; kv[4 + i] = t[3][c][i];
+            }
+            S[e] = OP::mma16(OP::pack8(kv), OP::pack8(qv), zero4);  // S^T[key][query] of cell c
+          }
+          float sv[8];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(S[0][i]), __float_as_uint(S[1][i]), false, false);
+            sv[i] = __uint_as_float(r[0]);
+            sv[4 + i] = __uint_as_float(r[1]);
+          }
+          float m = sv[0];
+#pragma unroll
+          for (int i = 1; i < 8; ++i) m = fmaxf(m, sv[i]);
+          m = xor16_max(m);
+          float sum = 0.f;
+          const float nms = -m * a.attn_scale_log2e;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            sv[i] = __builtin_amdgcn_exp2f(fmaf(sv[i], a.attn_scale_log2e, nms));
+            sum += sv[i];
+          }
+          sum = xor16_sum(sum);
+          const float inv = __builtin_amdgcn_rcpf(sum);
+          float p[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) p[i] = sv[i] * inv;
+          // own fragment or zero by sp, as in the 32x32 form: Ph[.][0] is the B operand of the even cell's P V product, Ph[.][1] of the odd
+          // kV16: P is held packed ONCE across the next passes (pinned here: hipcc otherwise sinks the normalisation behind the V
+          // pass and carries the eight exponentials instead) and selected where the operands are used
+          union FragBits { Frag f; unsigned u[sizeof(Frag) / 4]; } own, lo_half, hi_half;
+          own.f = OP::pack8(p);
+#pragma unroll
+          for (int i = 0; i < (int)(sizeof(Frag) / 4); ++i) {
+            if (kV16) asm volatile("" : "+v"(own.u[i]));
+            lo_half.u[i] = (sp16 && !kV16) ? 0u : own.u[i];
+            hi_half.u[i] = (sp16 || kV16) ? own.u[i] : 0u;
+          }
+          Ph[tt][0] = lo_half.f;
+          Ph[tt][1] = hi_half.f;
+        }
+      }
+    };
     // scores + softmax of one head: S^T = K Q^T (k = head dims), masked to the query's own sample, P packed as the next operand
     auto scores = [&](const Frag (&QFh)[NTT][2], const Frag (&KFh)[NTT][2], Frag (&Ph)[NTT][2]) {
 #pragma unroll
@@ -970,7 +1054,22 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
         F[tt][1] = OP::pack8(t + 8);
       }
     };
-    if constexpr (FT == 2) {
+    if constexpr (kQK16) {
+      // one head at a time, as below: units 16 ft..+15 of the stream, row tiles 0, 1 = the head's Q rows, 2, 3 = its K rows
+#pragma unroll
+      for (int ft = 0; ft < FT; ++ft) {
+        f32x4 t[4][2 * NTT];
+        f32x4 qkb[4];
+        // the bias follows the packer's row map: row tile R4, lane group g = head dims 8 (R4 & 1) + 16 (g >> 1) + 4 (g & 1)..+3
+#pragma unroll
+        for (int R4 = 0; R4 < 4; ++R4)
+          qkb[R4] = *reinterpret_cast<const f32x4*>(bq + (R4 >> 1) * kD + fbase + ft * 32 + 8 * (R4 & 1) + 16 * (lane >> 5) + 4 * ((lane >> 4) & 1));
+        gemm_pass16<OP, NTT, 8, true, PF>(t, ws, XA, L::XA_LD, lane, qkb);
+        if (ft == 0) SCLDM_STAMP(2);
+        if (ft == 0) SCLDM_STAMP(3);
+        scores16(t, Pf[ft]);
+      }
+    } else if constexpr (FT == 2) {
       // one head at a time: a two-tile pass whose tiles are the head's Q and K (the activation fragments are read from
       // LDS once for both), then its scores.  Only one head's Q/K fragments are live next to the residual - with both
       // heads' (the natural Q pass, K pass order) the allocator parked the residual in scratch, and scratch traffic shares
@@ -1000,39 +1099,106 @@ __global__ __launch_bounds__(64 * (8 / FT), ((OP::kTwoWG && NTT <= 2) || NTT == 
       for (int ft = 0; ft < FT; ++ft) scores(QF[ft], KF[ft], Pf[ft]);
     }
     SCLDM_STAMP(4);
-    // V (swapped operands: lane = feature, registers = tokens), then O^T = V^T P^T
-    gemm_pass<OP, NTT, FT, 16, true, true, PF>(acc, ws, XA, L::XA_LD, lane);
+    if constexpr (kQK16 != kV16) {
+      // one form's P into the other's lane order: lane bits 4 and 5 exchanged (an involution; own-or-zero moves with its lane)
+      const int src = (lane & 15) | (((lane >> 4) & 1) << 5) | (((lane >> 5) & 1) << 4);
 #pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-      // the V bias is added AFTER the P V product, as the initial accumulator: every query's probabilities sum to one over its
-      // sample's keys (the cross-sample blocks of P are exact zeros), so P (V + 1 b^T) = P V + b per output row d
-      const float* vb_row = bq + 2 * kD + fbase + ft * 32;
+      for (int ft = 0; ft < FT; ++ft)
 #pragma unroll
-      for (int tt = 0; tt < NTT; ++tt) {
-        float t[16];
+        for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) t[r] = acc[ft][tt][r];
-        const Frag v0 = OP::pack8(t), v1 = OP::pack8(t + 8);
-        const float* vb = vb_row;
-        asm volatile("" : "+v"(vb));        // re-read per token tile: holding the bias tile across both costs 16 registers where pressure peaks
-        f32x16 ot = bias_tile(vb);
-        ot = OP::mma(v0, Pf[ft][tt][0], ot);  // O^T[d][query], k = keys
-        ot = OP::mma(v1, Pf[ft][tt][1], ot);
-        acc[ft][tt] = ot;
+          for (int h = 0; h < 2; ++h) {
+            union { Frag f; int u[sizeof(Frag) / 4]; } x;
+            x.f = Pf[ft][tt][h];
+#pragma unroll
+            for (int i = 0; i < (int)(sizeof(Frag) / 4); ++i) x.u[i] = __shfl(x.u[i], src);
+            Pf[ft][tt][h] = x.f;
+          }
+    }
+    if constexpr (kV16) {
+      // V on 16x16 tiles with swapped operands: t[R4][cell], rows = the cell's 16 keys, cols = features 16 R4..+15.  Per row tile
+      // and cell pair the two packed registers of the even and the odd cell's tile are swapped across the wave halves: ONE A
+      // operand Vop whose k-groups 0, 1 are the even cell's keys 0-3 | 8-11, 4-7 | 12-15 and k-groups 2, 3 the odd cell's - the k
+      // slots of the 32x32 form's two chained operands.  Both cells' products use it; the other cell's keys meet the exact zeros
+      // of Ph.  The V bias is the initial C (see below).  The output tile is already in the layout of the AO store: packed here.
+      f32x4 t[4][2 * NTT];
+      gemm_pass16<OP, NTT, 8, true, PF, true>(t, ws, XA, L::XA_LD, lane);
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt)
+#pragma unroll
+        for (int R4 = 0; R4 < 4; ++R4) {
+          union { Quad q; unsigned u[2]; } ve, vo;
+          ve.q = OP::pack4(t[R4][2 * tt][0], t[R4][2 * tt][1], t[R4][2 * tt][2], t[R4][2 * tt][3]);
+          vo.q = OP::pack4(t[R4][2 * tt + 1][0], t[R4][2 * tt + 1][1], t[R4][2 * tt + 1][2], t[R4][2 * tt + 1][3]);
+          const auto s0 = __builtin_amdgcn_permlane32_swap(ve.u[0], vo.u[0], false, false);
+          const auto s1 = __builtin_amdgcn_permlane32_swap(ve.u[1], vo.u[1], false, false);
+          union { Frag f; unsigned u[4]; } vop;
+          vop.u[0] = s0[0]; vop.u[1] = s1[0]; vop.u[2] = s0[1]; vop.u[3] = s1[1];
+          const float* vbp = bq + 2 * kD + fbase + R4 * 16 + (lane >> 4) * 4;
+          asm volatile("" : "+v"(vbp));     // re-read per tile: not held across the loop
+          const f32x4 vb = *reinterpret_cast<const f32x4*>(vbp);
+          // own fragment or zero by sp, as in the 32x32 form (selected here, not held: idempotent on an already selected pair)
+          union { Frag f; unsigned u[4]; } pe, podd;
+          pe.f = Pf[R4 >> 1][tt][0];
+          podd.f = Pf[R4 >> 1][tt][1];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (kQK16) {   // one held copy; the opaque copy keeps the selects behind the pass
+              asm volatile("" : "+v"(pe.u[i]));
+              podd.u[i] = pe.u[i];
+            }
+            pe.u[i] = (lane >> 5) ? 0u : pe.u[i];
+            podd.u[i] = (lane >> 5) ? podd.u[i] : 0u;
+          }
+          const f32x4 oe = OP::mma16(vop.f, pe.f, vb);     // O^T[d][query] of the even cell, k = keys
+          const f32x4 oo = OP::mma16(vop.f, podd.f, vb);   // ... of the odd cell
+          po[R4][2 * tt] = OP::pack4(oe[0], oe[1], oe[2], oe[3]);
+          po[R4][2 * tt + 1] = OP::pack4(oo[0], oo[1], oo[2], oo[3]);
+        }
+    } else {
+      // V (swapped operands: lane = feature, registers = tokens), then O^T = V^T P^T
+      gemm_pass<OP, NTT, FT, 16, true, true, PF>(acc, ws, XA, L::XA_LD, lane);
+#pragma unroll
+      for (int ft = 0; ft < FT; ++ft) {
+        // the V bias is added AFTER the P V product, as the initial accumulator: every query's probabilities sum to one over its
+        // sample's keys (the cross-sample blocks of P are exact zeros), so P (V + 1 b^T) = P V + b per output row d
+        const float* vb_row = bq + 2 * kD + fbase + ft * 32;
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+          float t[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) t[r] = acc[ft][tt][r];
+          const Frag v0 = OP::pack8(t), v1 = OP::pack8(t + 8);
+          const float* vb = vb_row;
+          asm volatile("" : "+v"(vb));        // re-read per token tile: holding the bias tile across both costs 16 registers where pressure peaks
+          f32x16 ot = bias_tile(vb);
+          ot = OP::mma(v0, Pf[ft][tt][0], ot);  // O^T[d][query], k = keys
+          ot = OP::mma(v1, Pf[ft][tt][1], ot);
+          acc[ft][tt] = ot;
+        }
       }
     }
   }
   SCLDM_STAMP(5);
   lds_barrier();  // every wave is done reading XA (Q/K/V passes): it may now be overwritten by the attention output
+  if constexpr (kV16) {
+    // lane l: token 16 cell + (l & 15), features fbase + 16 R4 + 4 (l >> 4)..+3 - one 8-byte store, the bank pattern of the M16
+    // hidden-chunk store (row stride 132 dwords = 4 banks mod 64)
 #pragma unroll
-  for (int ft = 0; ft < FT; ++ft)
+    for (int R4 = 0; R4 < 4; ++R4)
 #pragma unroll
-    for (int tt = 0; tt < NTT; ++tt)
+      for (int c = 0; c < 2 * NTT; ++c) OP::store_quad(AO + (c * 16 + (lane & 15)) * L::XA_LD, fbase + R4 * 16 + (lane >> 4) * 4, po[R4][c]);
+  } else {
 #pragma unroll
-      for (int q = 0; q < 4; q += 2)
-        OP::store_quad_pair(AO + (tt * 32 + c32) * L::XA_LD, fbase + ft * 32 + q * 8, hh,
-                            OP::pack4(acc[ft][tt][q * 4 + 0], acc[ft][tt][q * 4 + 1], acc[ft][tt][q * 4 + 2], acc[ft][tt][q * 4 + 3]),
-                            OP::pack4(acc[ft][tt][q * 4 + 4], acc[ft][tt][q * 4 + 5], acc[ft][tt][q * 4 + 6], acc[ft][tt][q * 4 + 7]));
+    for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt)
+#pragma unroll
+        for (int q = 0; q < 4; q += 2)
+          OP::store_quad_pair(AO + (tt * 32 + c32) * L::XA_LD, fbase + ft * 32 + q * 8, hh,
+                              OP::pack4(acc[ft][tt][q * 4 + 0], acc[ft][tt][q * 4 + 1], acc[ft][tt][q * 4 + 2], acc[ft][tt][q * 4 + 3]),
+                              OP::pack4(acc[ft][tt][q * 4 + 4], acc[ft][tt][q * 4 + 5], acc[ft][tt][q * 4 + 6], acc[ft][tt][q * 4 + 7]));
+  }
   lds_barrier();  // AO complete
   SCLDM_STAMP(6);
 

@@ -14,8 +14,9 @@ struct scldm_dit {
   bool fused;   // shape served by the fused inference kernels (otherwise only the scldm_dit_train_* path)
   void* stream[4][2];  // [precision][FT-1] packed weight streams, [layer][wave][unit][tile] (+ ring over-read slack); NULL = shape unused
   bool fwd_m16 = true;  // SCLDM_FWD_MFMA (read once at create; 32: off): the bf16 / fp16 FT=2 streams and kernels run the SwiGLU
-                        // up-projection, the SwiGLU down-projection and the attention c_proj on 16x16 MFMA tiles
-                        // (dit_forward.hpp: M16, kM16Proj, kM16Down; the streams are packed for it)
+                        // up-projection, the SwiGLU down-projection, the attention c_proj and the attention phase (Q / K / V passes
+                        // and core) on 16x16 MFMA tiles (dit_forward.hpp: M16, kM16Proj, kM16Down, kM16QK, kM16V; the streams are
+                        // packed for it)
   void* wfinal[4];   // [precision] packed final_layer.linear
   float *b_qkv, *b_proj;  // (n_layer,768), (n_layer,256)
   float *w0t, *b0, *w2t, *b2;      // timestep MLP (transposed weights)
