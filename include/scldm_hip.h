@@ -282,7 +282,7 @@ int scldm_sample_ode(scldm_dit* h, float* z, const int64_t* const* ulabels, int 
 #define SCLDM_SDE_FORM_CONSTANT 2
 #define SCLDM_SDE_FORM_DECREASING 3
 #define SCLDM_SDE_FORM_INC_DEC 4   /* the reference spells it "inccreasing-decreasing" */
-#define SCLDM_SDE_FORM_SBDM 5      /* the reference's default; rejected (see above) */
+#define SCLDM_SDE_FORM_SBDM 5      /* the reference's default; rejected here (see above), served by scldm_sample_sde_transport */
 #define SCLDM_SDE_LAST_NONE 0
 #define SCLDM_SDE_LAST_MEAN 1
 #define SCLDM_SDE_LAST_TWEEDIE 2
@@ -640,6 +640,47 @@ int scldm_transport_coef_at(const scldm_transport* tr, double t, scldm_transport
 int scldm_sample_ode_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
                                const uint32_t* pass_mask, const float* pass_scale, int n_steps, int method, const scldm_transport* tr,
                                int precision, void* ws, void* stream);
+/* The SDE sampler and the likelihood under any transport above (scldm_sample_sde / scldm_logp_ode serve the default one: Linear path,
+ * velocity model).  With m the CFG-blended model output at state x and model time t, rr = alpha / alpha' (0 at t = 0):
+ *   drift      f_ode = a x + b m                                  (a, b) as scldm_transport_coef_at returns them
+ *   score      s = s_x x + s_m m,  (s_x, s_m) = (-1/var, rr/var) velocity, var = sigma^2 - rr sigma' sigma | (0, 1) score | (0, -1/sigma) noise
+ *   diffusion  D(t): SBDM norm Dv | SIGMA norm sigma (path-dependent) | LINEAR, CONSTANT, DECREASING, INC_DEC as scldm_sample_sde
+ *   SDE drift  f = f_ode + D s = c_x x + c_m m
+ * so every update of a solve is one affine map x' = a_x x + a_m m + a_w w: an Euler-Maruyama step (1 + dt c_x, dt c_m, sqrt(2 D dt)),
+ * Heun's K1 / K2 (c_x, c_m, 0) and the last step at t1 - MEAN (1 + lss c_x, lss c_m), EULER (1 + lss a, lss b), TWEEDIE
+ * (1/alpha + sigma^2/alpha s_x, sigma^2/alpha s_m).  All scalars are formed on the host in double from the fp32 time the model sees and
+ * rounded to fp32 once, where they enter a kernel argument.
+ * Grid: linspace(t0, t1, num_steps) in fp32, dt = t[1] - t[0], Heun's second evaluation at fp32 t + dt; a velocity model gets
+ * (t0, t1) = (0, 1 - lss), a noise / score model (sample_eps, lss == 0 ? 1 - sample_eps : 1 - lss)  (lss = last_step_size).
+ * Refusal rule: before the first launch every scalar of every update of the solve is formed; if one is not finite (as a double or once
+ * rounded to fp32) the call returns SCLDM_ERR_SHAPE and the message names the evaluation index and its time.  This refuses SBDM for a
+ * velocity model (Dv(0) is infinite on both paths), MEAN / TWEEDIE at t1 = 1 for a velocity model and a noise / score transport with
+ * sample_eps == 0; it admits Heun with last_step NONE for a noise / score model with sample_eps > 0.
+ *   scldm_sample_sde_transport: the arguments of scldm_sample_sde, then the transport.  The launches per evaluation are those of
+ *       scldm_sample_sde.  The default transport is handed to scldm_sample_sde, with that entry's own refusals; GVP + velocity is not the
+ *       default (its score conversion differs).
+ *   scldm_logp_ode_transport / scldm_logp_transport_workspace_bytes: the arguments of scldm_logp_ode / scldm_logp_workspace_bytes, then
+ *       the transport.  Solver time s runs over the fp32 linspace(t0, t1, n_steps + 1), (t0, t1) = (0, 1) for a velocity model and
+ *       (sample_eps, 1 - sample_eps) otherwise; the model sees t = fp32(1 - s); the state moves by -(a x + b m) with (a, b) at t and
+ *       logp_grad = a e + b (eps . (dm/dx)^T eps), formed as (float)(a e) + b * dot (e = S Din; eps . eps = e exactly for a Rademacher
+ *       probe).  Probes, shards, Heun's form and the prior as scldm_logp_ode; the default transport is handed to scldm_logp_ode.
+ *       Refused: a noise / score transport with sample_eps == 0 (as scldm_sample_ode_transport), and a solve with a non-finite (a, b, a e).
+ *   scldm_sde_coef_at: out[4] = {D, c_x, c_m, sqrt(2 D dt)} at t;  scldm_sde_last_coef_at: out[2] = {a_x, a_m} of the last step at t1
+ *       (last_step MEAN | TWEEDIE | EULER).  Host only, in double: no handle, no device; non-finite values are returned as they come.
+ * SCLDM_ERR_SHAPE with nothing launched also for a bad transport, an unknown form / last step / method and a null pointer. */
+int scldm_sde_coef_at(const scldm_transport* tr, int diffusion_form, double diffusion_norm, double t, double dt, double* out);
+int scldm_sde_last_coef_at(const scldm_transport* tr, int diffusion_form, double diffusion_norm, int last_step, double last_step_size, double t1,
+                           double* out);
+int scldm_sample_sde_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B, int n_pass,
+                               const uint32_t* pass_mask, const float* pass_scale, int num_steps, int method, int diffusion_form,
+                               float diffusion_norm, int last_step, float last_step_size, const float* noise, unsigned long long seed,
+                               long long cell_offset, long long cells_total, float* traj, int precision, void* ws, void* stream,
+                               const scldm_transport* tr);
+size_t scldm_logp_transport_workspace_bytes(const scldm_dit* h, int B, int n_pass, int precision, const scldm_transport* tr);
+int scldm_logp_ode_transport(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                             const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps,
+                             int method, const float* probe, unsigned long long seed, long long cell_offset, long long cells_total,
+                             float* logp, float* dlogp_traj, int precision, void* saved, void* ws, void* stream, const scldm_transport* tr);
 /* Training around the model call, unfused (the generalisation of scldm_fm_mix / scldm_fm_loss / scldm_fm_loss_bwd):
  *   scldm_fm_plan:      one launch writes xt, the loss target tgt (ut | x0 | -x0) and rowc[b] = {c, w} (n, 2); each product is rounded
  *                       on its own, then the sum, like the eager form.  x1, x0, xt, tgt are (n, e) fp32, t is (n).

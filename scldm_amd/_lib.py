@@ -261,6 +261,12 @@ def lib() -> C.CDLL:
     L.scldm_transport_coef_at.argtypes = [C.POINTER(TransportC), C.c_double, C.POINTER(TransportCoef)]
     a = L.scldm_sample_ode.argtypes
     L.scldm_sample_ode_transport.argtypes = a[:11] + [C.POINTER(TransportC)] + a[11:]
+    L.scldm_sample_sde_transport.argtypes = L.scldm_sample_sde.argtypes + [C.POINTER(TransportC)]
+    L.scldm_logp_transport_workspace_bytes.argtypes = L.scldm_logp_workspace_bytes.argtypes + [C.POINTER(TransportC)]
+    L.scldm_logp_transport_workspace_bytes.restype = C.c_size_t
+    L.scldm_logp_ode_transport.argtypes = L.scldm_logp_ode.argtypes + [C.POINTER(TransportC)]
+    L.scldm_sde_coef_at.argtypes = [C.POINTER(TransportC), C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    L.scldm_sde_last_coef_at.argtypes = [C.POINTER(TransportC), C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.scldm_fm_plan.argtypes = [C.POINTER(TransportC)] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_wloss.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.scldm_fm_wloss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -380,6 +386,7 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_logp_ode_dopri5_workspace_bytes", "scldm_logp_ode_dopri5",
            "scldm_transport_coef_at", "scldm_sample_ode_transport", "scldm_fm_plan", "scldm_fm_wloss", "scldm_fm_wloss_bwd", "scldm_fm_prepare_transport", "scldm_fm_wloss_grad",
            "scldm_dit_train_step_transport",
+           "scldm_sample_sde_transport", "scldm_logp_transport_workspace_bytes", "scldm_logp_ode_transport", "scldm_sde_coef_at", "scldm_sde_last_coef_at",
            "scldm_scvi_create", "scldm_scvi_destroy", "scldm_scvi_pack", "scldm_scvi_workspace_bytes", "scldm_scvi_encode", "scldm_scvi_decode",
            "scldm_scvi_forward",
            "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward",

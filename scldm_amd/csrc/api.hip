@@ -17,6 +17,7 @@
 #include "ode_rk.hpp"
 #include "sde.hpp"
 #include "transport_path.hpp"
+#include "sde_transport.hpp"
 #include "dopri5_ctl.hpp"
 #include "dopri5_fused.hpp"
 #include "fixed_grid.hpp"
@@ -1191,6 +1192,148 @@ extern "C" int scldm_sample_sde(scldm_dit* h, float* z, const int64_t* const* ul
     } else if (last_step == SCLDM_SDE_LAST_TWEEDIE) a_v = (float)(1.0 - (double)t1);   // x / t1 + (1 - t1)^2 / t1 score = x + (1 - t1) v
     if ((rc = eval(z, z, a_x, a_v, 0.f, n_steps, tr))) return rc;
   } else if (tr) HIP_TRY(hipMemcpyAsync(tr, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // the reference appends the unchanged state
+  return SCLDM_OK;
+}
+
+// ---- SDE sampling under any transport (sde_transport.hpp) -------------------------------------------------------------------------------
+// The same launches as scldm_sample_sde - the trunk, then cfg_blend_sde_kernel with three scalars (sde_perturb_kernel, axpy and heun
+// kernels for Heun) - with the scalars of sdet::eval_at over linspace(t0, t1, num_steps), (t0, t1) = sdet::sde_interval.  Every scalar
+// of every update is formed before the first launch; one that is not finite refuses the solve.
+extern "C" int scldm_sde_coef_at(const scldm_transport* tr, int diffusion_form, double diffusion_norm, double t, double dt, double* out) {
+  if (!out || !tpath::transport_valid(tr) || !sdet::form_valid(diffusion_form))
+    return fail(SCLDM_ERR_SHAPE, "scldm_sde_coef_at: bad argument (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5, a known diffusion form)");
+  const sdet::Eval ev = sdet::eval_at(tr, diffusion_form, diffusion_norm, t);
+  out[0] = ev.D;
+  out[1] = ev.c_x;
+  out[2] = ev.c_m;
+  out[3] = sdet::noise_scale(ev, dt);
+  return SCLDM_OK;
+}
+extern "C" int scldm_sde_last_coef_at(const scldm_transport* tr, int diffusion_form, double diffusion_norm, int last_step, double last_step_size,
+                                      double t1, double* out) {
+  if (!out || !tpath::transport_valid(tr) || !sdet::form_valid(diffusion_form) || last_step < SCLDM_SDE_LAST_MEAN || last_step > SCLDM_SDE_LAST_EULER)
+    return fail(SCLDM_ERR_SHAPE, "scldm_sde_last_coef_at: bad argument (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5, a known diffusion "
+                "form, last step Mean | Tweedie | Euler)");
+  const sdet::Eval ev = sdet::eval_at(tr, diffusion_form, diffusion_norm, t1);
+  sdet::last_coef(ev, last_step, last_step_size, &out[0], &out[1]);
+  return SCLDM_OK;
+}
+
+extern "C" int scldm_sample_sde_transport(scldm_dit* h, float* z, const int64_t* const* ulabels, int n_urows, const int32_t* cell_row, int B,
+                                          int n_pass, const uint32_t* pass_mask, const float* pass_scale, int num_steps, int method,
+                                          int diffusion_form, float diffusion_norm, int last_step, float last_step_size, const float* noise,
+                                          unsigned long long seed, long long cell_offset, long long cells_total, float* traj, int precision,
+                                          void* ws_, void* stream_, const scldm_transport* tr) {
+  if (!tpath::transport_valid(tr))
+    return fail(SCLDM_ERR_SHAPE, "scldm_sample_sde_transport: bad transport (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5)");
+  if (tr->path == SCLDM_PATH_LINEAR && tr->model == SCLDM_MODEL_VELOCITY)   // the default transport: the existing solve, its refusals included
+    return scldm_sample_sde(h, z, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, num_steps, method, diffusion_form, diffusion_norm,
+                            last_step, last_step_size, noise, seed, cell_offset, cells_total, traj, precision, ws_, stream_);
+  int rc = check_ready(h, precision);
+  if (rc) return rc;
+  if (!z || !ws_) return fail(SCLDM_ERR_SHAPE, "null pointer argument");
+  if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
+  if (!sdet::form_valid(diffusion_form)) return fail(SCLDM_ERR_SHAPE, "unknown diffusion form %d", diffusion_form);
+  if (last_step < SCLDM_SDE_LAST_NONE || last_step > SCLDM_SDE_LAST_EULER) return fail(SCLDM_ERR_SHAPE, "unknown last step %d", last_step);
+  if (num_steps < 2) return fail(SCLDM_ERR_SHAPE, "num_steps must be >= 2 (grid points)");
+  if (last_step == SCLDM_SDE_LAST_NONE) last_step_size = 0.f;   // transport.py:290-291
+  if (!(last_step_size >= 0.f && last_step_size < 1.f)) return fail(SCLDM_ERR_SHAPE, "last_step_size must be in [0, 1) (got %g)", (double)last_step_size);
+  if (cell_offset < 0 || cells_total < cell_offset + B) return fail(SCLDM_ERR_SHAPE, "cells_total (%lld) < cell_offset (%lld) + B (%d)", cells_total, cell_offset, B);
+  if (((uintptr_t)z & 15) || ((uintptr_t)noise & 15) || ((uintptr_t)traj & 15)) return fail(SCLDM_ERR_SHAPE, "z, noise and traj must be 16-byte aligned");
+  const bool heun = method == SCLDM_METHOD_HEUN, has_last = last_step != SCLDM_SDE_LAST_NONE;
+  const int n_steps = num_steps - 1;
+  // the fp32 grid of integrators.py:23-24, every evaluation's time and every update's scalars
+  float t0, t1;
+  sdet::sde_interval(tr, last_step_size, &t0, &t1);
+  if (!(t0 < t1)) return fail(SCLDM_ERR_SHAPE, "the solve's interval [%g, %g] is empty (sample_eps against 1 - last_step_size)", (double)t0, (double)t1);
+  const float dt = grid::linspace(1, num_steps, t0, t1) - grid::linspace(0, num_steps, t0, t1);
+  const std::vector<float> tl = grid::eval_times(n_steps, t0, t1, heun ? grid::kPlusDt : grid::kNone, has_last ? &t1 : nullptr);
+  struct Upd { float a_x, a_m, a_w; };
+  std::vector<Upd> up;   // one per evaluation, in tl's order: a step's noise scale rides with its first evaluation
+  up.reserve(tl.size());
+  for (int i = 0; i < n_steps; ++i) {
+    const float t = grid::linspace(i, num_steps, t0, t1);
+    const sdet::Eval ev = sdet::eval_at(tr, diffusion_form, diffusion_norm, (double)t);
+    const double a_w = sdet::noise_scale(ev, (double)dt);
+    const double a_x = heun ? ev.c_x : 1.0 + (double)dt * ev.c_x, a_m = heun ? ev.c_m : (double)dt * ev.c_m;
+    if (!sdet::all_finite({ev.D, a_x, a_m, a_w}))
+      return fail(SCLDM_ERR_SHAPE, "scldm_sample_sde_transport: %s", sdet::refusal((int)up.size(), (double)t, "D, c_x, c_m or sqrt(2 D dt)").c_str());
+    up.push_back(Upd{(float)a_x, (float)a_m, (float)a_w});
+    if (heun) {
+      const float t2 = t + dt;
+      const sdet::Eval e2 = sdet::eval_at(tr, diffusion_form, diffusion_norm, (double)t2);
+      if (!sdet::all_finite({e2.D, e2.c_x, e2.c_m}))
+        return fail(SCLDM_ERR_SHAPE, "scldm_sample_sde_transport: %s", sdet::refusal((int)up.size(), (double)t2, "D, c_x or c_m of Heun's K2").c_str());
+      up.push_back(Upd{(float)e2.c_x, (float)e2.c_m, 0.f});
+    }
+  }
+  if (has_last) {
+    const sdet::Eval ev = sdet::eval_at(tr, diffusion_form, diffusion_norm, (double)t1);
+    double a_x, a_m;
+    sdet::last_coef(ev, last_step, (double)last_step_size, &a_x, &a_m);
+    if (!sdet::all_finite({a_x, a_m}))
+      return fail(SCLDM_ERR_SHAPE, "scldm_sample_sde_transport: %s", sdet::refusal((int)up.size(), (double)t1, "a_x or a_m of the last step").c_str());
+    up.push_back(Upd{(float)a_x, (float)a_m, 0.f});
+  }
+  FusedSolve s;
+  if ((rc = s.plan(h, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, precision, ws_, stream_))) return rc;
+  const CfgPlan& pl = s.pl;
+  const Ws& w = s.w;
+  hipStream_t st = s.st;
+  const int e_row = 16 * h->cfg.n_embed_input;
+  const size_t n = s.n;
+  if (e_row % 4 || n / 4 > 0x7fffffffull) return fail(SCLDM_ERR_SHAPE, "state rows must be a multiple of 4 elements, at most 2^33 elements in all");
+  if ((rc = s.prepare(tl))) return rc;
+  sde::BlendArgs ba{};
+  ba.v = w.v;
+  ba.B = B;
+  ba.e = e_row;
+  ba.P = pl.P;
+  ba.direct = pl.direct ? 1 : 0;
+  fill_pass_scale(ba.scale, pl.P, pl.scale);
+  ba.g = sde::NoiseGeom{seed, cell_offset, cells_total, 0u};
+  int e_idx = 0;
+  // evaluation e_idx at zin, then out = a_x zin + a_m m (+ a_w w of step `step` when with_noise)
+  auto eval = [&](const float* zin, float* out, bool with_noise, int step, float* traj_out) -> int {
+    const Upd& u = up[e_idx];
+    int rc2 = s.eval(e_idx++, zin, w.v);
+    if (rc2) return rc2;
+    ba.x = zin;
+    ba.out = out;
+    ba.traj = traj_out;
+    ba.a_x = u.a_x;
+    ba.a_v = u.a_m;
+    ba.a_w = with_noise ? u.a_w : 0.f;
+    ba.noise_mode = (!with_noise || u.a_w == 0.f) ? sde::kNoiseNone : noise ? sde::kNoiseArray : sde::kNoisePhilox;
+    ba.noise = noise ? noise + (size_t)step * n : nullptr;
+    ba.g.step = (uint32_t)step;
+    sde::cfg_blend_sde_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(ba);
+    LAUNCH_CHECK();
+    return SCLDM_OK;
+  };
+  for (int i = 0; i < n_steps; ++i) {
+    float* trj = traj ? traj + (size_t)i * n : nullptr;
+    if (!heun) {   // x <- x + dt f(x, t) + sqrt(2 D dt) w
+      if ((rc = eval(z, z, true, i, trj))) return rc;
+    } else {
+      const float a_w = up[e_idx].a_w;
+      if (a_w != 0.f) {   // xhat = x + sqrt(2 D(t) dt) w
+        sde::PerturbArgs pa{z, noise ? noise + (size_t)i * n : nullptr, B, e_row, noise ? sde::kNoiseArray : sde::kNoisePhilox, a_w, ba.g};
+        pa.g.step = (uint32_t)i;
+        sde::sde_perturb_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(pa);
+      }
+      if ((rc = eval(z, w.dz, false, i, nullptr))) return rc;                                 // K1 = f(xhat, t)
+      axpy_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.ztmp, dt, n);                      // xp = xhat + dt K1
+      if ((rc = eval(w.ztmp, w.k2, false, i, nullptr))) return rc;                            // K2 = f(xp, t + dt)
+      heun_kernel<<<cdiv(n, 256), 256, 0, st>>>(z, w.dz, w.k2, 0.5f * dt, n);                 // x = xhat + dt / 2 (K1 + K2)
+      if (trj) HIP_TRY(hipMemcpyAsync(trj, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    LAUNCH_CHECK();
+  }
+  float* trj = traj ? traj + (size_t)n_steps * n : nullptr;
+  if (has_last) {
+    if ((rc = eval(z, z, false, n_steps, trj))) return rc;
+  } else if (trj) HIP_TRY(hipMemcpyAsync(trj, z, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // the reference appends the unchanged state
   return SCLDM_OK;
 }
 

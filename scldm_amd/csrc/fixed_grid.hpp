@@ -1,4 +1,4 @@
-// Host side of the fixed-grid solves (scldm_sample_ode, scldm_sample_sde, scldm_sample_ode_transport, scldm_logp_ode,
+// Host side of the fixed-grid solves (scldm_sample_ode, scldm_sample_sde / _transport, scldm_sample_ode_transport, scldm_logp_ode / _transport,
 // scldm_dit_infer_sample_ode): plain C++, no HIP, no handle - the fp32 time grid, the list of a solve's evaluation times and the
 // Euler / Heun step loop over caller-supplied launches.  tests/fixed_grid_shim.cpp gives it a C face, so all of it is tested on a
 // machine without a GPU (a sibling of dopri5_ctl.hpp).

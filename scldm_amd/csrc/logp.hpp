@@ -212,6 +212,63 @@ __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ z,
   if (lane == 0) logp[r] = (c0 - ss * 0.5f) - dl[r];
 }
 
+// The blend under a transport other than the default (transport_path.hpp: Linear | GVP x velocity | noise | score): the probability-flow
+// drift is f = a x + b m with m the CFG-blended model output and x the state the evaluation was made at - rows [0, 2B) of the forward's
+// input xin, which seed_kernel filled from z (Euler, Heun's first evaluation) or from ztmp (Heun's second).  The state moves by -f and
+//   logp_grad = eps . (d f / d x)^T eps = a e + b (eps . (d m / d x)^T eps)          (eps in {-1, +1}: eps . eps = e exactly)
+// formed as lg = ae + b * dot: ae = the host's (float)(a * e), dot = the unscaled wave sum of blend_kernel, two roundings.  a, b and ae
+// are evaluated in double at the fp32 model time and rounded once on the host.  One wave per row, the fixed butterfly order, plain
+// vector stores, as blend_kernel; modes as there.
+struct BlendTransportArgs {
+  BlendArgs k;          // blend_kernel's arguments
+  const float* xin;     // (N, e) the forward's input: rows [0, 2B) = the state of this evaluation
+  float a, b, ae;
+};
+__global__ __launch_bounds__(256) void blend_transport_kernel(const BlendTransportArgs t) {
+  const BlendArgs& a = t.k;
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= 2 * a.B) return;   // (whole waves leave: the shuffles below see full waves)
+  const int e4 = a.e >> 2;
+  const size_t half4 = (size_t)a.B * e4, row4 = (size_t)r * e4;
+  const f32x4* out = reinterpret_cast<const f32x4*>(a.out);
+  const f32x4* dx = reinterpret_cast<const f32x4*>(a.dx);
+  float acc = 0.f;
+  for (int c4 = lane; c4 < e4; c4 += 64) {
+    f32x4 v = out[row4 + c4], d = dx[row4 + c4];
+    if (r >= a.B) {
+      const f32x4 u = v;
+      for (int p = 0; p < a.P; ++p) {
+        v = cfg_blend_pass(v, out[row4 + half4 + (size_t)p * half4 + c4], u, a.scale[p]);   // (cfg_blend_kernel's statement)
+        d = d + dx[row4 + half4 + (size_t)p * half4 + c4];
+      }
+    }
+    const f32x4 ep = reinterpret_cast<const f32x4*>(a.eps)[row4 + c4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc = acc + ep[i] * d[i];
+    const f32x4 x = reinterpret_cast<const f32x4*>(t.xin)[row4 + c4];
+    const f32x4 px = x * t.a, pm = v * t.b;
+    const f32x4 nv = -(px + pm);
+    f32x4* zp = reinterpret_cast<f32x4*>(a.z) + row4 + c4;
+    if (a.mode == kEuler) {
+      *zp = *zp + nv * a.hs;
+    } else if (a.mode == kHeun1) {
+      reinterpret_cast<f32x4*>(a.k1v)[row4 + c4] = nv;
+      reinterpret_cast<f32x4*>(a.ztmp)[row4 + c4] = *zp + nv * a.hs;
+    } else {
+      *zp = *zp + (reinterpret_cast<const f32x4*>(a.k1v)[row4 + c4] + nv) * a.hs;
+    }
+  }
+  const float dot = wave_sum_fixed(acc);
+  if (lane == 0) {
+    const float bd = t.b * dot;
+    const float lg = t.ae + bd;
+    if (a.traj) a.traj[r] = lg;
+    if (a.mode == kEuler) a.dl[r] = a.dl[r] + lg * a.hs;
+    else if (a.mode == kHeun1) a.k1l[r] = lg;
+    else a.dl[r] = a.dl[r] + (a.k1l[r] + lg) * a.hs;
+  }
+}
+
 #pragma clang fp contract(fast)   // back to the compiler's default for whatever the including translation unit defines after this header
 
 }  // namespace logp

@@ -4,12 +4,14 @@
 
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "api_common.hpp"
 #include "cfg_plan.hpp"
 #include "dit_handle.hpp"
 #include "fixed_grid.hpp"
 #include "logp.hpp"
+#include "sde_transport.hpp"
 
 using namespace scldm;
 
@@ -67,10 +69,13 @@ extern "C" int scldm_logp_probe(float* out, long long n_rows_local, int e, unsig
   return SCLDM_OK;
 }
 
-extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
-                              const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps,
-                              int method, const float* probe, unsigned long long seed, long long cell_offset, long long cells_total,
-                              float* logp_out, float* dlogp_traj, int precision, void* saved, void* ws_, void* stream_) {
+// The fixed-grid likelihood solve.  tr == NULL: the default transport (Linear path, velocity model) over s in [0, 1] with blend_kernel;
+// otherwise solver time runs over linspace(t0, t1, n_steps + 1), (t0, t1) = check_interval(sde=False, eval=True), and every
+// evaluation ends in blend_transport_kernel with (a, b) of tpath::transport_coef at its model time t = fp32(1 - s).
+static int logp_solve(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                      const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps,
+                      int method, const float* probe, unsigned long long seed, long long cell_offset, long long cells_total,
+                      float* logp_out, float* dlogp_traj, int precision, void* saved, void* ws_, void* stream_, const scldm_transport* tr) {
   if (!h || !w || !z || !logp_out || !saved || !ws_) return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode: null pointer argument");
   if (n_steps < 1) return fail(SCLDM_ERR_SHAPE, "n_steps must be >= 1");
   if (method != SCLDM_METHOD_EULER && method != SCLDM_METHOD_HEUN) return fail(SCLDM_ERR_SHAPE, "unknown method %d", method);
@@ -83,6 +88,31 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
   const int e = 16 * c.n_embed_input;
   const long long N = (long long)(2 + n_pass) * B;
   if (c.seq_len != 16 || e % 4 || N * (e / 4) > 0x7fffffffll || N > 0x7fffffffll) return fail(SCLDM_ERR_SHAPE, "state too large or unsupported shape");
+  // the solver-time grid and, under a transport, every evaluation's (a, b, a e): formed and checked before anything is launched
+  const int steps = n_steps + 1;
+  float sa0 = 0.f, sb0 = 1.f;
+  struct TCoef { float a, b, ae; };
+  std::vector<TCoef> tc;
+  if (tr) {
+    if (tr->model != SCLDM_MODEL_VELOCITY && !(tr->sample_eps > 0.f))   // (as scldm_sample_ode_transport)
+      return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_transport: a noise / score model needs sample_eps > 0: its drift is singular at t = 0 (alpha'/alpha) "
+                  "and at t = 1 (noise: 1 / sigma)");
+    double td0, td1;
+    tpath::transport_interval(tr, true, &td0, &td1);
+    sa0 = (float)td0;
+    sb0 = (float)td1;
+    const bool heun = method == SCLDM_METHOD_HEUN;
+    for (int i = 0; i < n_steps; ++i)
+      for (int j = 0; j < (heun ? 2 : 1); ++j) {
+        const float t = 1.0f - grid::linspace(i + j, steps, sa0, sb0);
+        scldm_transport_coef kc;
+        tpath::transport_coef(tr->path, tr->model, tr->weight, (double)t, &kc);
+        const double ae = kc.a * (double)e;
+        if (!sdet::all_finite({kc.a, kc.b, ae}))
+          return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_transport: %s", sdet::refusal((int)tc.size(), (double)t, "a, b of the probability-flow drift").c_str());
+        tc.push_back(TCoef{(float)kc.a, (float)kc.b, (float)ae});
+      }
+  }
   hipStream_t st = (hipStream_t)stream_;
   const LogpWs k = carve_logp(h, B, n_pass, precision, ws_);
   const size_t row_e = (size_t)2 * B * e;
@@ -138,13 +168,17 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
     ba.mode = mode;
     ba.hs = hs;
     ba.traj = dlogp_traj ? dlogp_traj + (size_t)ev * 2 * B : nullptr;
-    logp::blend_kernel<<<cdiv(2 * B, 4), 256, 0, st>>>(ba);
+    if (tr) {
+      const logp::BlendTransportArgs bt{ba, k.xin, tc[ev].a, tc[ev].b, tc[ev].ae};
+      logp::blend_transport_kernel<<<cdiv(2 * B, 4), 256, 0, st>>>(bt);
+    } else {
+      logp::blend_kernel<<<cdiv(2 * B, 4), 256, 0, st>>>(ba);
+    }
     LAUNCH_CHECK();
     return SCLDM_OK;
   };
-  const int steps = n_steps + 1;
   for (int i = 0; i < n_steps; ++i) {
-    const float s0 = grid::linspace(i, steps, 0.f, 1.f), s1 = grid::linspace(i + 1, steps, 0.f, 1.f);
+    const float s0 = grid::linspace(i, steps, sa0, sb0), s1 = grid::linspace(i + 1, steps, sa0, sb0);
     const float hs = s1 - s0;
     if (method == SCLDM_METHOD_EULER) {
       if ((rc = eval(z, s0, logp::kEuler, hs))) return rc;
@@ -157,6 +191,33 @@ extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z
   logp::final_kernel<<<cdiv(2 * B, 4), 256, 0, st>>>(z, k.dl, 2 * B, e, c0, logp_out);
   LAUNCH_CHECK();
   return SCLDM_OK;
+}
+
+extern "C" int scldm_logp_ode(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                              const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale, int n_steps,
+                              int method, const float* probe, unsigned long long seed, long long cell_offset, long long cells_total,
+                              float* logp_out, float* dlogp_traj, int precision, void* saved, void* ws_, void* stream_) {
+  return logp_solve(h, w, z, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, n_steps, method, probe, seed, cell_offset, cells_total,
+                    logp_out, dlogp_traj, precision, saved, ws_, stream_, nullptr);
+}
+
+// ---- the same solve under any transport (sde_transport.hpp, transport_path.hpp) ---------------------------------------------------------
+static bool is_default_transport(const scldm_transport* tr) { return tr->path == SCLDM_PATH_LINEAR && tr->model == SCLDM_MODEL_VELOCITY; }
+
+extern "C" size_t scldm_logp_transport_workspace_bytes(const scldm_dit* h, int B, int n_pass, int precision, const scldm_transport* tr) {
+  if (!tpath::transport_valid(tr)) return 0;
+  return scldm_logp_workspace_bytes(h, B, n_pass, precision);   // the transport blend reads the forward's own input: no further buffer
+}
+
+extern "C" int scldm_logp_ode_transport(scldm_dit* h, const scldm_dit_weights* w, float* z, const int64_t* const* ulabels, int n_urows,
+                                        const int32_t* cell_row, int B, int n_pass, const uint32_t* pass_mask, const float* pass_scale,
+                                        int n_steps, int method, const float* probe, unsigned long long seed, long long cell_offset,
+                                        long long cells_total, float* logp_out, float* dlogp_traj, int precision, void* saved, void* ws_,
+                                        void* stream_, const scldm_transport* tr) {
+  if (!tpath::transport_valid(tr))
+    return fail(SCLDM_ERR_SHAPE, "scldm_logp_ode_transport: bad transport (Linear | GVP, velocity | noise | score, 0 <= eps < 0.5)");
+  return logp_solve(h, w, z, ulabels, n_urows, cell_row, B, n_pass, pass_mask, pass_scale, n_steps, method, probe, seed, cell_offset, cells_total,
+                    logp_out, dlogp_traj, precision, saved, ws_, stream_, is_default_transport(tr) ? nullptr : tr);
 }
 
 #include "logp_dopri5_api.inc"   // scldm_logp_ode_dopri5: the adaptive solve over the same evaluation

@@ -25,10 +25,15 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _default_transport_only(transport, what: str) -> None:
-    if transport is not None and not transport.is_default:
-        raise NotImplementedError(f"{what} serves the Linear path with a velocity model only (its drift, score and last steps are written for "
-                                  "that transport); a GVP path or a noise / score model samples through sample_ode_cfg(..., transport=)")
+def _default_transport_only(transport, what: str) -> bool:
+    """True: the default transport's code path (None included).  False: another transport that opted in with `samplers_enabled`."""
+    if transport is None or transport.is_default:
+        return True
+    if getattr(transport, "samplers_enabled", False):
+        return False
+    raise NotImplementedError(f"{what} serves the Linear path with a velocity model only (its drift, score and last steps are written for "
+                              "that transport); a GVP path or a noise / score model samples through sample_ode_cfg(..., transport=), or "
+                              "opts in with create_transport(..., samplers_enabled=True)")
 
 
 def _require_cuda_f32(name: str, t: torch.Tensor) -> torch.Tensor:
@@ -1241,8 +1246,15 @@ class DiT(nn.Module):
         draws it in registers (`seed=None`: one drawn from torch's host generator).  A value depends on (seed, step, global row, column)
         only: with `cell_offset` / `cells_total` a shard of a larger solve draws exactly the noise the whole solve would have drawn for
         its cells.  Under graph capture the seed is baked into the captured launches, so a replay repeats its noise.
-        `diffusion_form="SBDM"` and "heun" with `last_step=None` raise ValueError (NaN in the reference under this transport)."""
-        _default_transport_only(transport, "sample_sde_cfg")
+        `diffusion_form="SBDM"` and "heun" with `last_step=None` raise ValueError (NaN in the reference under this transport).
+
+        `transport`: None or the default (Linear, velocity) transport is the solve above.  Another transport created with
+        `samplers_enabled=True` (without it: NotImplementedError) runs the same launches with its own scalars (scldm_sample_sde_transport:
+        score per model type, D(t) per path, "SBDM" = norm Dv included) over linspace(t0, t1, num_steps), (t0, t1) = (0, 1 -
+        last_step_size) for a velocity model and (sample_eps, 1 - last_step_size or 1 - sample_eps) for a noise / score model; a solve one
+        of whose scalars is not finite raises ValueError before anything is launched, naming the evaluation and its time.  Training mode and
+        shapes outside the fused family take the generic `Sampler(transport).sample_sde` over forward_with_cfg."""
+        default = _default_transport_only(transport, "sample_sde_cfg")
         method = str(sampling_method).lower()
         if method not in _lib.METHODS:
             raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'euler' and 'heun' are")
@@ -1273,8 +1285,9 @@ class DiT(nn.Module):
             fwd = self._generic_forward_with_cfg if not self.fused_shape else self.forward_with_cfg
             draws = iter(range(num_steps - 1))
             draw = lambda x: noise[next(draws)] if noise is not None else self.sde_noise(seed, next(draws), B, cell_offset, total)
-            fn = Sampler(create_transport()).sample_sde(sampling_method=method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm,
-                                                        last_step=last_step, last_step_size=last_step_size, num_steps=num_steps)
+            fn = Sampler(create_transport() if default else transport).sample_sde(
+                sampling_method=method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm, last_step=last_step,
+                last_step_size=last_step_size, num_steps=num_steps)
             xs = fn(z, lambda x, t: fwd(x, t.contiguous() if not self.fused_shape else t, condition, cfg_scale), _draw=draw)
             return torch.stack(xs) if return_trajectory else xs[-1]
         self._need_null_row("CFG sampling (the unconditional pass)")
@@ -1282,14 +1295,19 @@ class DiT(nn.Module):
         ul, n_u, cell_row, n_pass, masks, scales, keep = self._cfg_plan(condition, cfg_scale, B, dedup=True)
         ws = self._workspace(L, 2 * B + n_pass * B, 1 + n_pass * n_u, 2 * B)
         traj = torch.empty(num_steps, *z.shape, device=z.device, dtype=torch.float32) if return_trajectory and num_steps >= 2 else None
+        args = (h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass, masks,
+                scales, num_steps, _lib.METHODS[method], _lib.SDE_FORMS[diffusion_form], float(diffusion_norm),
+                _lib.SDE_LAST_STEPS[last_step], float(last_step_size), noise.data_ptr() if noise is not None else None,
+                seed, cell_offset, total, traj.data_ptr() if traj is not None else None, self._prec(), ws, _stream_ptr())
         with torch.cuda.device(z.device):
-            rc = L.scldm_sample_sde(h, z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass, masks,
-                                    scales, num_steps, _lib.METHODS[method], _lib.SDE_FORMS[diffusion_form], float(diffusion_norm),
-                                    _lib.SDE_LAST_STEPS[last_step], float(last_step_size), noise.data_ptr() if noise is not None else None,
-                                    seed, cell_offset, total, traj.data_ptr() if traj is not None else None, self._prec(), ws, _stream_ptr())
+            if default:
+                rc = L.scldm_sample_sde(*args)
+            else:
+                tr = transport.c_struct()
+                rc = L.scldm_sample_sde_transport(*args, C.byref(tr))
         if rc == -1:    # SCLDM_ERR_SHAPE: the rejected combinations and ranges, with the library's message
             raise ValueError(L.scldm_last_error().decode())
-        _lib.check(rc, "scldm_sample_sde")
+        _lib.check(rc, "scldm_sample_sde" if default else "scldm_sample_sde_transport")
         del keep
         return traj if return_trajectory else z
 
@@ -1310,7 +1328,7 @@ class DiT(nn.Module):
         return out
 
     def log_likelihood_cfg(self, z: torch.Tensor, condition: dict[str, torch.Tensor] | None, cfg_scale: dict[str, float] | None,
-                           num_steps: int = 50, sampling_method: str = "euler", *, atol: float = 1e-6, rtol: float = 1e-3,
+                           num_steps: int = 50, sampling_method: str = "euler", *, transport=None, atol: float = 1e-6, rtol: float = 1e-3,
                            first_step: float | None = None, probe_per: str = "evaluation", seed: int | None = None,
                            probe: torch.Tensor | None = None, cell_offset: int = 0, cells_total: int | None = None, return_trace: bool = False):
         """The reference's `Sampler.sample_ode_likelihood` over `forward_with_cfg` on the fixed grid linspace(0, 1, num_steps)
@@ -1344,11 +1362,19 @@ class DiT(nn.Module):
         noise to the step controller.  `probe_per="solve"` ("dopri5" only; the usual FFJORD form) holds one probe for the whole solve:
         evaluation 0 of the generator, or `probe` (1, 2B, S, C) / (2B, S, C).
         The step size is shared by the whole batch: a shard of a dopri5 solve does NOT reproduce the whole solve's rows, unlike the fixed
-        grid, even though its probes are the whole solve's.  `return_trace` is not available with "dopri5"."""
+        grid, even though its probes are the whole solve's.  `return_trace` is not available with "dopri5".
+
+        `transport`: None or the default (Linear, velocity) transport is everything above.  Another transport created with
+        `samplers_enabled=True` (without it: NotImplementedError): solver time runs over linspace(t0, t1, num_steps), (t0, t1) = (0, 1) for
+        a velocity model and (sample_eps, 1 - sample_eps) for a noise / score model, the state moves by -(a x + b m) and logp_grad =
+        a e + b eps . (dm/dx)^T eps; "euler" / "heun" are one C call on a fused shape in eval mode (scldm_logp_ode_transport), and a solve
+        with a non-finite scalar raises ValueError before anything is launched.  "dopri5" under such a transport is HOST-DRIVEN: the generic
+        `Sampler(transport).sample_ode_likelihood("dopri5")` over differentiable `forward` calls, one host read per attempted step."""
+        default = _default_transport_only(transport, "log_likelihood_cfg")
         method = str(sampling_method).lower()
         if method == "dopri5":
             return self._log_likelihood_dopri5(z, condition, cfg_scale, num_steps, atol, rtol, first_step, probe_per, seed, probe, cell_offset,
-                                               cells_total, return_trace)
+                                               cells_total, return_trace, None if default else transport)
         if method not in _lib.METHODS:
             raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are")
         if probe_per != "evaluation":
@@ -1377,7 +1403,7 @@ class DiT(nn.Module):
             from .transport import Sampler, create_transport
             draws = iter(range(n_evals))
             draw = lambda x: probe[next(draws)] if probe is not None else self.logp_probe(seed, next(draws), B, cell_offset, total)
-            fn = Sampler(create_transport()).sample_ode_likelihood(sampling_method=method, num_steps=num_steps)
+            fn = Sampler(create_transport() if default else transport).sample_ode_likelihood(sampling_method=method, num_steps=num_steps)
             logp, z_end = fn(z, lambda x, t: self._composed_forward_with_cfg(x, t.contiguous(), condition, cfg_scale), _probe=draw)
             return (logp, z_end, torch.stack(fn.last_trace["logp_grad"])) if return_trace else (logp, z_end)
         L, h = self._native_handle()
@@ -1394,19 +1420,24 @@ class DiT(nn.Module):
         ws = torch.empty(L.scldm_logp_workspace_bytes(h, B, n_pass, prec), dtype=torch.uint8, device=z.device)
         logp = torch.empty(n, dtype=torch.float32, device=z.device)
         trace = torch.empty(n_evals, n, dtype=torch.float32, device=z.device) if return_trace else None
+        args = (h, C.byref(w), z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass,
+                masks, scales, num_steps - 1, _lib.METHODS[method], probe.data_ptr() if probe is not None else None, seed,
+                cell_offset, total, logp.data_ptr(), trace.data_ptr() if trace is not None else None, prec,
+                saved.data_ptr(), ws.data_ptr(), _stream_ptr())
         with torch.cuda.device(z.device):
-            rc = L.scldm_logp_ode(h, C.byref(w), z.data_ptr(), C.cast(ul, _lib.c_void_pp) if ul is not None else None, n_u, cell_row, B, n_pass,
-                                  masks, scales, num_steps - 1, _lib.METHODS[method], probe.data_ptr() if probe is not None else None, seed,
-                                  cell_offset, total, logp.data_ptr(), trace.data_ptr() if trace is not None else None, prec,
-                                  saved.data_ptr(), ws.data_ptr(), _stream_ptr())
+            if default:
+                rc = L.scldm_logp_ode(*args)
+            else:
+                tr = transport.c_struct()
+                rc = L.scldm_logp_ode_transport(*args, C.byref(tr))
         if rc == -1:    # SCLDM_ERR_SHAPE: rejected arguments, with the library's message
             raise ValueError(L.scldm_last_error().decode())
-        _lib.check(rc, "scldm_logp_ode")
+        _lib.check(rc, "scldm_logp_ode" if default else "scldm_logp_ode_transport")
         del keep
         return (logp, z, trace) if return_trace else (logp, z)
 
     def _log_likelihood_dopri5(self, z, condition, cfg_scale, num_steps, atol, rtol, first_step, probe_per, seed, probe, cell_offset,
-                               cells_total, return_trace):
+                               cells_total, return_trace, transport=None):
         """log_likelihood_cfg(..., "dopri5"): scldm_logp_ode_dopri5, or the generic sampler for training mode / other shapes."""
         if return_trace:
             raise ValueError("return_trace is not available with 'dopri5' (the evaluation count of an adaptive solve is not known ahead)")
@@ -1440,7 +1471,8 @@ class DiT(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         seed = int(seed) & (2 ** 64 - 1)
         self._need_null_row("the likelihood of a CFG field (the unconditional pass)")
-        if self.training or not self.fused_shape:
+        if self.training or not self.fused_shape or transport is not None:
+            # (`transport`: a non-default one that opted in - no one-call dopri5 exists for it)
             from .transport import Sampler, create_transport
             count = iter(range(1 << 62))
             if probe is not None:
@@ -1450,8 +1482,8 @@ class DiT(nn.Module):
                 draw = lambda x: held
             else:
                 draw = lambda x: self.logp_probe(seed, next(count), B, cell_offset, total)
-            fn = Sampler(create_transport()).sample_ode_likelihood(sampling_method="dopri5", num_steps=num_steps, atol=atol, rtol=rtol,
-                                                                   first_step=first_step)
+            fn = Sampler(transport or create_transport()).sample_ode_likelihood(sampling_method="dopri5", num_steps=num_steps, atol=atol,
+                                                                                rtol=rtol, first_step=first_step)
             logp, z_end = fn(z, lambda x, t: self._composed_forward_with_cfg(x, t.contiguous(), condition, cfg_scale), _probe=draw)
             st = fn.last_stats
             steps = sorted(st["accepted_steps"] + st["rejected_steps"])

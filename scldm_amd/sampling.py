@@ -23,8 +23,8 @@ def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | N
                    rtol: float = 1e-5, transport=None) -> torch.Tensor:
     """z0 (B,S,C) noise -> final latents (2B,S,C): rows [0,B) unconditional, rows [B,2B) guided (models.py:801-812).
     `atol` / `rtol`: the tolerances of sampling_method="dopri5" (the reference's default sampler and its defaults; a fixed grid ignores them).
-    `transport`: what the model predicts (`DiT.sample_ode_cfg`); None or a velocity transport is the plain solve, the SDE sampler takes
-    the default transport only.
+    `transport`: what the model predicts (`DiT.sample_ode_cfg`); None or a velocity transport is the plain solve; the SDE sampler takes
+    the default transport, or any other created with `samplers_enabled=True` (`DiT.sample_sde_cfg(..., transport=)`).
 
     `sde`: None integrates the ODE (`DiT.sample_ode_cfg`); a dict selects the stochastic sampler instead and holds the keyword arguments
     of `DiT.sample_sde_cfg` beyond the grid and the method (diffusion_form, diffusion_norm, last_step, last_step_size, seed, noise, and
@@ -42,7 +42,10 @@ def sample_latents(dit, z0: torch.Tensor, condition: dict[str, torch.Tensor] | N
     cond2 = None if condition is None else {k: torch.cat([v, v], dim=0) for k, v in condition.items()}
     if sde is not None:
         if transport is not None and not transport.is_default:
-            raise NotImplementedError("the SDE sampler serves the Linear path with a velocity model only")
+            if not getattr(transport, "samplers_enabled", False):
+                raise NotImplementedError("the SDE sampler serves the Linear path with a velocity model only (create_transport(..., "
+                                          "samplers_enabled=True) opts into the other transports)")
+            return dit.sample_sde_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, transport=transport, **sde)
         return dit.sample_sde_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, **sde)
     if transport is not None and transport.model_type.name != "VELOCITY":
         return dit.sample_ode_cfg(z2, cond2, guidance_weight, num_steps, sampling_method, atol=atol, rtol=rtol, transport=transport)

@@ -4,7 +4,15 @@
 reference signatures (transport/__init__.py:6-12, transport.py:110,269-332).  Differences, by design:
   * path_type "Linear" | "GVP" x prediction "velocity" | "noise" | "score" x loss_weight None | "velocity" | "likelihood" exist;
     (Linear, velocity) is the combination every reference config uses (ldm_base.yaml:30-35) and keeps its own kernels.  The VP
-    path raises NotImplementedError.  `sample_sde` and `sample_ode_likelihood` serve the default (Linear, velocity) transport only;
+    path raises NotImplementedError.  `sample_sde` and `sample_ode_likelihood` serve the default (Linear, velocity) transport, and every
+    other one created with `create_transport(..., samplers_enabled=True)` (off by default: without it they raise NotImplementedError
+    there).  Under such a transport every update of the SDE solve is one affine map x' = a_x x + a_m m + a_w w of the state, the model
+    output and the step's normals (score = s_x x + s_m m per model type, D(t) per form - "SBDM" = norm Dv included -, SDE drift
+    = probability-flow drift + D score), over linspace(t0, t1, num_steps) with (t0, t1) = check_interval(sde=True, eval=True); the
+    likelihood integrates -(a x + b m) over solver time linspace(t0, t1) with the model at t = 1 - s.  A solve one of whose scalars is not
+    finite (SBDM for a velocity model, a score at t = 1, sample_eps = 0 for a noise / score model) raises ValueError before any model call,
+    naming the evaluation and its time.  A scldm_amd DiT of the fused family runs both as one C call (`DiT.sample_sde_cfg(...,
+    transport=)` -> scldm_sample_sde_transport, `DiT.log_likelihood_cfg(..., transport=)` -> scldm_logp_ode_transport);
   * the reference hands stepping to third-party torchdiffeq (integrators.py:111, default dopri5); here the
     fixed-grid "euler" / "heun" schemes are built in (definition + KAT: oracle/transport.py), and when the
     model is a scldm_amd DiT bound through `forward_with_cfg` the whole loop runs inside one C call
@@ -208,7 +216,9 @@ _C_WEIGHT = {WeightType.NONE: 0, WeightType.VELOCITY: 1, WeightType.LIKELIHOOD: 
 
 
 class Transport:
-    def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps):
+    samplers_enabled = False   # opt-in: sample_sde / sample_ode_likelihood under a transport other than (Linear, velocity)
+
+    def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps, samplers_enabled=False):
         if path_type not in _C_PATH:
             raise NotImplementedError("the VP path is not provided: path_type 'Linear' and 'GVP' are (its fp32 arithmetic forms 1 - exp(...) "
                                       "next to t = 1 and needs a design of its own)")
@@ -220,6 +230,7 @@ class Transport:
         self.model_type, self.path_type, self.loss_type = model_type, path_type, loss_type
         self.train_eps, self.sample_eps = train_eps, sample_eps
         self.path_sampler = LinearPath() if path_type is PathType.LINEAR else GVPPath()
+        self.samplers_enabled = bool(samplers_enabled)
 
     @property
     def is_default(self) -> bool:
@@ -371,12 +382,15 @@ class Transport:
         return lambda x, t, model, **kw: path.get_score_from_velocity(model(x, t, **kw), x, t)
 
 
-def create_transport(path_type="Linear", prediction="velocity", loss_weight=None, train_eps=None, sample_eps=None):
+def create_transport(path_type="Linear", prediction="velocity", loss_weight=None, train_eps=None, sample_eps=None, *, samplers_enabled=False):
     """Same call as scldm.transport.create_transport.  A velocity model on the Linear or GVP path: both eps forced to 0
     (transport/__init__.py:55-57).  A noise / score model: train_eps and sample_eps default to 1e-3 each.  (The reference's line
     `sample_eps = 1e-3 if train_eps is None else sample_eps` runs after train_eps was reassigned, so it leaves sample_eps = None
     unless the caller passes one and then fails with TypeError in check_interval(eval=True); None becomes 1e-3 here, the value that
-    line evidently intends.)  path_type="VP" raises NotImplementedError."""
+    line evidently intends.)  path_type="VP" raises NotImplementedError.
+    `samplers_enabled=True` (not in the reference's call) opts into `Sampler.sample_sde` / `.sample_ode_likelihood`, `DiT.sample_sde_cfg` and
+    `DiT.log_likelihood_cfg` under a transport other than (Linear, velocity); without it they raise NotImplementedError there, and the
+    default transport behaves the same either way."""
     model_type = {"noise": ModelType.NOISE, "score": ModelType.SCORE}.get(prediction, ModelType.VELOCITY)
     loss_type = {"velocity": WeightType.VELOCITY, "likelihood": WeightType.LIKELIHOOD}.get(loss_weight, WeightType.NONE)
     ptype = {"Linear": PathType.LINEAR, "GVP": PathType.GVP, "VP": PathType.VP}[path_type]
@@ -385,7 +399,8 @@ def create_transport(path_type="Linear", prediction="velocity", loss_weight=None
     else:
         train_eps = 1e-3 if train_eps is None else train_eps
         sample_eps = 1e-3 if sample_eps is None else sample_eps
-    return Transport(model_type=model_type, path_type=ptype, loss_type=loss_type, train_eps=train_eps, sample_eps=sample_eps)
+    return Transport(model_type=model_type, path_type=ptype, loss_type=loss_type, train_eps=train_eps, sample_eps=sample_eps,
+                     samplers_enabled=samplers_enabled)
 
 
 # Dormand-Prince 5(4) tableau (Dormand & Prince 1980) and the mid-point weights of the quartic dense output used by
@@ -415,9 +430,168 @@ class Sampler:
         t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, sde=False, eval=True, reverse=False)
         return float(t0), float(t1)
 
-    def _default_only(self, what: str) -> None:
-        if not self.transport.is_default:
+    def _default_only(self, what: str) -> bool:
+        """True: the default transport's code path.  False: another transport that opted in (`samplers_enabled`).  Otherwise raises."""
+        if self.transport.is_default:
+            return True
+        if not self.transport.samplers_enabled:
             raise NotImplementedError(f"{what} serves the Linear path with a velocity model only; under another transport use sample_ode")
+        return False
+
+    # ---- the SDE sampler and the likelihood under the other transports (opt-in: Transport.samplers_enabled) ----
+    def sde_plan(self, *, sampling_method, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps):
+        """The grid and the refusal scan of an SDE solve under this transport: (ts fp32 tensor, dt, t1, evaluation times).  (t0, t1) =
+        check_interval(sde=True, eval=True, last_step_size) - (0, 1 - last_step_size) for a velocity model.  Every scalar of every update
+        x' = a_x x + a_m m + a_w w is formed (scldm_sde_coef_at / scldm_sde_last_coef_at: double, from the fp32 time); one that is not
+        finite raises ValueError naming the evaluation and its time, before any model call."""
+        import ctypes as C
+        import math
+        from .. import _lib
+        tr = self.transport
+        method = str(sampling_method).lower()
+        if method not in ("euler", "heun"):
+            raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'Euler' and 'Heun' are")
+        if diffusion_form not in _lib.SDE_FORMS:
+            raise NotImplementedError(f"Diffusion form {diffusion_form} not implemented")
+        if last_step not in SDE_LAST_STEPS:
+            raise NotImplementedError(f"last_step={last_step!r}: one of {SDE_LAST_STEPS}")
+        if last_step is None:
+            last_step_size = 0.0
+        if num_steps < 2:
+            raise ValueError("num_steps must be >= 2 (grid points)")
+        if not 0.0 <= last_step_size < 1.0:
+            raise ValueError(f"last_step_size must be in [0, 1), got {last_step_size}")
+        t0, t1 = tr.check_interval(tr.train_eps, tr.sample_eps, diffusion_form=diffusion_form, sde=True, eval=True, last_step_size=last_step_size)
+        if tr.model_type == ModelType.VELOCITY:
+            t1 = 1 - last_step_size
+        if not t0 < t1:
+            raise ValueError(f"the solve's interval [{t0}, {t1}] is empty (sample_eps against 1 - last_step_size)")
+        ts = torch.linspace(t0, t1, num_steps)
+        dt = ts[1] - ts[0]
+        L, trc, form = _lib.lib(), tr.c_struct(), _lib.SDE_FORMS[diffusion_form]
+        out4, out2 = (C.c_double * 4)(), (C.c_double * 2)()
+        f32ok = lambda v: math.isfinite(v) and abs(v) <= 3.4028234663852886e38
+        times = []
+
+        def refuse(tv, what):
+            raise ValueError(f"evaluation {len(times)} of the solve, at t = {tv:.9g}, has a non-finite coefficient ({what}): the transport "
+                             "is singular there")
+
+        for i in range(num_steps - 1):
+            tv = float(ts[i])
+            _lib.check(L.scldm_sde_coef_at(C.byref(trc), form, float(diffusion_norm), tv, float(dt), out4), "scldm_sde_coef_at")
+            D, c_x, c_m, a_w = out4
+            step = (c_x, c_m) if method == "heun" else (1.0 + float(dt) * c_x, float(dt) * c_m)
+            if not all(map(f32ok, (D, a_w, *step))):
+                refuse(tv, "D, c_x, c_m or sqrt(2 D dt)")
+            times.append(tv)
+            if method == "heun":
+                t2 = float(ts[i] + dt)
+                _lib.check(L.scldm_sde_coef_at(C.byref(trc), form, float(diffusion_norm), t2, float(dt), out4), "scldm_sde_coef_at")
+                if not all(map(f32ok, out4[:3])):
+                    refuse(t2, "D, c_x or c_m of Heun's K2")
+                times.append(t2)
+        t1f = float(torch.tensor(t1, dtype=torch.float32))
+        if last_step is not None:
+            _lib.check(L.scldm_sde_last_coef_at(C.byref(trc), form, float(diffusion_norm), _lib.SDE_LAST_STEPS[last_step], float(last_step_size), t1f,
+                                                out2), "scldm_sde_last_coef_at")
+            if not all(map(f32ok, out2)):
+                refuse(t1f, "a_x or a_m of the last step")
+            times.append(t1f)
+        return ts, dt, t1, times
+
+    def _sample_sde_transport(self, sampling_method, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps):
+        """sample_sde under a transport other than (Linear, velocity): the reference's expressions (transport.py:222-322, integrators.py:7-75)
+        on one model call per evaluation.  SBDM's D = norm Dv is formed here (the paths' compute_diffusion does not offer it)."""
+        ts, dt, t1, _ = self.sde_plan(sampling_method=sampling_method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm,
+                                      last_step=last_step, last_step_size=last_step_size, num_steps=num_steps)
+        method = str(sampling_method).lower()
+        if last_step is None:
+            last_step_size = 0.0
+        path, model_type = self.transport.path_sampler, self.transport.model_type
+
+        def diffusion(x, tv):
+            if diffusion_form == "SBDM":
+                return diffusion_norm * path.compute_drift(x, tv)[1]
+            return path.compute_diffusion(x, tv, form=diffusion_form, norm=diffusion_norm)
+
+        def evaluate(x, tval, model, model_kwargs):
+            """(probability-flow drift, score, SDE drift) at one time, from ONE model call."""
+            tv = torch.as_tensor(tval, dtype=torch.float32).to(x.device).reshape(()).expand(x.shape[0])
+            m = model(x, tv, **model_kwargs)
+            assert m.shape == x.shape, "Output shape from SDE solver must match input shape"
+            if model_type == ModelType.VELOCITY:
+                f_ode, score = m, path.get_score_from_velocity(m, x, tv)
+            else:
+                drift_mean, drift_var = path.compute_drift(x, tv)
+                score = m / -path.compute_sigma_t(_expand_like(tv, x))[0] if model_type == ModelType.NOISE else m
+                f_ode = -drift_mean + drift_var * score
+            return f_ode, score, f_ode + diffusion(x, tv) * score, tv
+
+        @torch.no_grad()
+        def _sample(init, model, _draw=None, **model_kwargs):
+            import contextlib
+            from ..nnets import weights_unchanged
+            x, xs = init, []
+            with contextlib.ExitStack() as stack:
+                for i in range(num_steps - 1):
+                    ti = ts[i]
+                    w = torch.randn(x.size()).to(x) if _draw is None else _draw(x)
+                    dw = w * torch.sqrt(dt)
+                    tv = ti.to(x.device).expand(x.shape[0])
+                    D = diffusion(x, tv)
+                    if method == "euler":
+                        _, _, f, _ = evaluate(x, ti, model, model_kwargs)
+                        x = x + f * dt.to(x.device) + torch.sqrt(2 * D) * dw
+                    else:
+                        xhat = x + torch.sqrt(2 * D) * dw
+                        _, _, k1, _ = evaluate(xhat, ti, model, model_kwargs)
+                        _, _, k2, _ = evaluate(xhat + dt.to(x.device) * k1, ti + dt, model, model_kwargs)
+                        x = xhat + 0.5 * dt.to(x.device) * (k1 + k2)
+                    if i == 0:
+                        stack.enter_context(weights_unchanged())
+                    xs.append(x)
+                if last_step is not None:
+                    f_ode, score, f, tv = evaluate(x, torch.tensor(t1, dtype=torch.float32), model, model_kwargs)
+                    if last_step == "Mean":
+                        x = x + f * last_step_size
+                    elif last_step == "Tweedie":
+                        alpha, sigma = path.compute_alpha_t(tv)[0][0], path.compute_sigma_t(tv)[0][0]
+                        x = x / alpha + (sigma ** 2) / alpha * score
+                    else:
+                        x = x + f_ode * last_step_size
+                xs.append(x)
+            assert len(xs) == num_steps, "Samples does not match the number of steps"
+            return xs
+
+        return _sample
+
+    def logp_plan(self, *, sampling_method, num_steps, row_elems=None):
+        """The refusal scan of a likelihood solve under this transport: a noise / score model needs sample_eps > 0 (as sample_ode's one-call
+        form refuses it), and on the fixed grids
+        (a, b) of every evaluation's model time t = fp32(1 - s) must be finite (ValueError naming the evaluation and its time)."""
+        import ctypes as C
+        import math
+        from .. import _lib
+        tr = self.transport
+        t_lo, t_hi = self._ode_interval()
+        if tr.model_type != ModelType.VELOCITY and not tr.sample_eps > 0:
+            raise ValueError("a noise / score model needs sample_eps > 0: its drift is singular at t = 0 (alpha'/alpha) and at t = 1 (noise: 1 / sigma)")
+        method = str(sampling_method).lower()
+        if method == "dopri5":
+            return t_lo, t_hi
+        ss = torch.linspace(t_lo, t_hi, num_steps)
+        L, trc, k = _lib.lib(), tr.c_struct(), _lib.TransportCoef()
+        n = 0
+        for i in range(num_steps - 1):
+            for j in range(2 if method == "heun" else 1):
+                tv = float(1 - ss[i + j])
+                _lib.check(L.scldm_transport_coef_at(C.byref(trc), tv, C.byref(k)), "scldm_transport_coef_at")
+                if not (math.isfinite(k.a) and math.isfinite(k.b) and math.isfinite(k.a * (row_elems or 1))):
+                    raise ValueError(f"evaluation {n} of the solve, at t = {tv:.9g}, has a non-finite coefficient (a, b of the probability-flow "
+                                     "drift): the transport is singular there")
+                n += 1
+        return t_lo, t_hi
 
     def _sample_dopri5(self, num_steps: int, atol: float, rtol: float, first_step: float | None = None):
         """Adaptive Dormand-Prince 5(4) - what `torchdiffeq.odeint(method="dopri5")` computes for the reference's default
@@ -589,7 +763,8 @@ class Sampler:
         Three corners of the reference return NaN under this transport and raise here: diffusion_form="SBDM" - the DEFAULT - is
         (1 - t) / t at the t0 = 0 the solve starts from; "Heun" with last_step=None and "Mean" / "Tweedie" with last_step_size=0
         evaluate the score at t = 1."""
-        self._default_only("sample_sde")
+        if not self._default_only("sample_sde"):
+            return self._sample_sde_transport(sampling_method, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps)
         method = str(sampling_method).lower()
         if method not in ("euler", "heun"):
             raise NotImplementedError(f"Sampler type {sampling_method!r} not implemented: 'Euler' and 'Heun' are")
@@ -681,12 +856,14 @@ class Sampler:
         None: the automatic initial step) is the first attempted step size, as for `_sample_dopri5`.
         A scldm_amd DiT runs these solves on device through `DiT.log_likelihood_cfg` (fixed grid: scldm_logp_ode; "dopri5":
         scldm_logp_ode_dopri5)."""
-        self._default_only("sample_ode_likelihood")
+        default = self._default_only("sample_ode_likelihood")
         method = str(sampling_method).lower()
         if method not in ("euler", "heun", "dopri5"):
             raise NotImplementedError(f"sampling_method={sampling_method!r}: 'euler', 'heun' (fixed grid) and 'dopri5' (adaptive) are provided")
         if num_steps < 2:
             raise ValueError("num_steps must be >= 2 (grid points)")
+        # solver time runs over [t0, t1] = check_interval(sde=False, eval=True): (0, 1) under the default transport
+        s_lo, s_hi = (0.0, 1.0) if default else self.logp_plan(sampling_method=method, num_steps=num_steps)
         drift, transport = self.drift, self.transport
 
         def _sample_fn(x, model, _probe=None, **model_kwargs):
@@ -722,7 +899,7 @@ class Sampler:
                 _sample_fn.last_stats = solve.last_stats
                 x, dl = y[:, :-1].reshape(shape), y[:, -1]
             else:
-                ts = torch.linspace(0.0, 1.0, num_steps)
+                ts = torch.linspace(s_lo, s_hi, num_steps)
                 with torch.no_grad():
                     for i in range(num_steps - 1):
                         h = float(ts[i + 1] - ts[i])
