@@ -1162,6 +1162,44 @@ int scldm_scvi_train_backward_ex(scldm_scvi* h, const float* counts, const float
                                  void* ws, void* stream);
 int scldm_scvi_train_set_found_inf(scldm_scvi* h, float* found_inf /* device, caller-owned, may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------
+ * TransformerVAE inference beyond the 32-wide shape: a handle family of its own (scldm_vaew_*), config and weight structs shared with
+ * scldm_vae_*.  The shape family, checked by scldm_vaew_create before any HIP call (SCLDM_ERR_SHAPE, the message names the violated
+ * condition): n_embed % 32 == 0 and 64 <= n_embed <= 1024; n_embed % n_head == 0 and n_embed % n_head_cross == 0 with both head dims
+ * multiples of 8 in [8, 256]; 1 <= n_inducing <= 64; 1 <= n_embed_latent <= n_embed; n_layer >= 0; any hidden_dim >= 1; positional
+ * encoding on or off; bias=False, shared gene embedding, no adaLN; the negative-binomial head with a theta table or (theta = NULL)
+ * with the two-logit params.  The Gaussian head (head_ln_w / head_ln_b given) is refused by scldm_vaew_load_weights.
+ *
+ * Inference only: encode and decode (the draw is scldm_nb_sample on decode's output).  `precision`: SCLDM_PREC_FP32 (every product on
+ * v_mfma_f32_32x32x2_f32, <= 1e-4 against the reference) or SCLDM_PREC_FP16 (v_mfma_f32_32x32x16_f16, operands rounded while they are
+ * staged: the reference's TF32 class; LayerNorm, attention, softmax and the head stay fp32); anything else: SCLDM_ERR_SHAPE.
+ *
+ * Nothing derived from the weights is kept: scldm_vaew_load_weights only remembers the pointers (no HIP call, `stream` unused), every
+ * call reads the parameters where they live, so an in-place update is seen by the next call.  No allocation in encode / decode: the
+ * caller passes scldm_vaew_workspace_bytes(h, B, S, G) bytes (S or G may be 0 when only the other call follows; 0 is returned when a
+ * single cell does not fit the cap).  The cells of a call are processed in chunks whose workspace stays under a cap: 1024 MiB, or
+ * SCLDM_VAEW_WS_MB (MiB, read at scldm_vaew_create).  Results are bit-equal run to run and do not depend on the chunking or on the
+ * other cells of the batch.
+ *
+ * scldm_vaew_plan is host arithmetic: how B cells of `tokens` tokens (decode == 0: S encoder tokens, else G decoded genes) are cut
+ * under `cap_bytes` (0 = the handle's cap): chunk i holds cells [i * cells_per_chunk, min(B, (i + 1) * cells_per_chunk)), ws_bytes is
+ * the workspace of one chunk.  One cell above the cap: SCLDM_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct scldm_vaew scldm_vaew;
+int scldm_vaew_create(const scldm_vae_config* cfg, scldm_vaew** out);
+void scldm_vaew_destroy(scldm_vaew* h);
+int scldm_vaew_load_weights(scldm_vaew* h, const scldm_vae_weights* w, void* stream);
+int scldm_vaew_plan(const scldm_vaew* h, int decode, int B, int tokens, size_t cap_bytes, int* cells_per_chunk, int* n_chunks,
+                    size_t* ws_bytes);
+size_t scldm_vaew_workspace_bytes(const scldm_vaew* h, int B, int S, int G);
+/* counts (B,S) fp32, genes (B,S) int64 -> z (B, n_inducing, n_embed_latent) */
+int scldm_vaew_encode(scldm_vaew* h, const float* counts, const int64_t* genes, int B, int S, float* z, int precision, void* ws,
+                      void* stream);
+/* z (B, n_inducing, n_embed_latent), genes (B,G) int64, library_size (B) -> mu (B,G) = softmax_G(logit / t) * library_size,
+ * theta (B,G) = exp(theta table row) or exp(second logit) */
+int scldm_vaew_decode(scldm_vaew* h, const float* z, const int64_t* genes, const float* library_size, int B, int G, float* mu,
+                      float* theta, int precision, void* ws, void* stream);
+
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the
  * production library returns SCLDM_ERR_STATE. */

@@ -363,6 +363,16 @@ def lib() -> C.CDLL:
     L.scldm_scvi_train_forward_ex.argtypes = L.scldm_scvi_train_forward.argtypes[:-2] + [C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_scvi_train_backward_ex.argtypes = L.scldm_scvi_train_backward.argtypes[:-2] + [C.c_int, C.c_void_p, C.c_void_p]
     L.scldm_scvi_train_set_found_inf.argtypes = [C.c_void_p, C.c_void_p]
+    # TransformerVAE inference beyond the 32-wide shape (config and weight structs of scldm_vae_*)
+    L.scldm_vaew_create.argtypes = [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]
+    L.scldm_vaew_destroy.argtypes = [C.c_void_p]
+    L.scldm_vaew_destroy.restype = None
+    L.scldm_vaew_load_weights.argtypes = [C.c_void_p, C.POINTER(VaeWeights), C.c_void_p]
+    L.scldm_vaew_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    L.scldm_vaew_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.scldm_vaew_workspace_bytes.restype = C.c_size_t
+    L.scldm_vaew_encode.argtypes = L.scldm_vae_encode.argtypes
+    L.scldm_vaew_decode.argtypes = L.scldm_vae_decode.argtypes
     _lib = L
     return L
 
@@ -391,7 +401,9 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_scvi_forward",
            "scldm_scvi_train_record_bytes", "scldm_scvi_train_workspace_bytes", "scldm_scvi_train_forward", "scldm_scvi_train_backward",
            "scldm_scvi_encode_ex", "scldm_scvi_decode_ex", "scldm_scvi_forward_ex",
-           "scldm_scvi_train_forward_ex", "scldm_scvi_train_backward_ex", "scldm_scvi_train_set_found_inf"]
+           "scldm_scvi_train_forward_ex", "scldm_scvi_train_backward_ex", "scldm_scvi_train_set_found_inf",
+           "scldm_vaew_create", "scldm_vaew_destroy", "scldm_vaew_load_weights", "scldm_vaew_plan", "scldm_vaew_workspace_bytes",
+           "scldm_vaew_encode", "scldm_vaew_decode"]
 
 
 def check(rc: int, what: str) -> None:

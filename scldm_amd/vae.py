@@ -256,6 +256,60 @@ class TransformerVAE(nn.Module):
         """The head kind, told as the reference tells it: by the class name (vae.py:46-47,82-83)."""
         return self.decoder_head.__class__.__name__ == "GaussianTransformerLayer"
 
+    # ------------------------------------------------------------------ the shape-generic inference route (scldm_vaew_*)
+    @property
+    def wide(self) -> bool:
+        """False: the vae_base shape (n_embed 32, 16 inducing points, heads 8 / 4), which runs on the MCAB kernels (scldm_vae_*).
+        True: any other shape; inference (encode / decode / decode_sample / forward under no_grad) runs on the shape-generic route
+        (scldm_vaew_*: every product a tile GEMM on the matrix pipe, csrc/vae_wide.hpp), `precision` "fp32" or "fp16", NB head only."""
+        enc = self.encoder
+        return not (enc.n_embed == 32 and enc.latent_dim == 16 and enc.n_head == 8 and enc.n_head_cross == 4)
+
+    def _native_wide(self):
+        if self.gaussian_head:
+            raise NotImplementedError("the wide TransformerVAE route (n_embed != 32) decodes the negative-binomial head only: the Gaussian "
+                                      "head (GaussianTransformerLayer) is not built for it")
+        if self.precision not in ("fp32", "fp16"):
+            raise NotImplementedError(f"the wide TransformerVAE route (n_embed != 32) runs in fp32 or fp16 (precision={self.precision!r}); "
+                                      "bf16 operands are not built for it")
+        L = _lib.lib()
+        emb = self.input_layer.gene_embedding.weight
+        enc = self.encoder
+        if self.__dict__.get("_whandle") is None:
+            cfg = _lib.VaeConfig(n_genes=emb.shape[0] - 1, n_embed=emb.shape[1], n_inducing=enc.latent_dim,
+                                 n_embed_latent=enc.latent_embedding, n_layer=enc.n_layer, n_head=enc.n_head,
+                                 n_head_cross=enc.n_head_cross, hidden_dim=swiglu_hidden(enc.n_embed, enc.multiple_of),
+                                 layernorm_eps=enc.layernorm_eps, positional_encoding=int(enc.pos_embed is not None),
+                                 nb_temperature=float(self.decoder_head.t))
+            h = C.c_void_p()
+            rc = L.scldm_vaew_create(C.byref(cfg), C.byref(h))      # host arithmetic: the shape family and the workspace cap
+            if rc == -1:                                            # SCLDM_ERR_SHAPE: the message names the violated condition
+                raise NotImplementedError(L.scldm_last_error().decode())
+            _lib.check(rc, "scldm_vaew_create")
+            self.__dict__["_whandle"] = h
+            self.__dict__["_wkey"] = None
+        if emb.device.type != "cuda":
+            raise RuntimeError("TransformerVAE parameters must live on a CUDA (ROCm) device; there is no CPU path")
+        h = self.__dict__["_whandle"]
+        key = tuple(p.data_ptr() for p in self.parameters())
+        if key != self.__dict__.get("_wkey"):       # new storages.  The kernels read the parameters where they live and keep nothing
+            for p in self.parameters():             # derived from them, so an in-place update needs no refresh
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError("TransformerVAE parameters must be contiguous fp32")
+            w, keep = self._weights_struct(lambda t: t.data_ptr())
+            _lib.check(L.scldm_vaew_load_weights(h, C.byref(w), None), "scldm_vaew_load_weights")
+            self.__dict__["_wkey"] = key
+        return L, h
+
+    def _wide_workspace(self, L, h, B: int, S: int, G: int) -> int:
+        need = L.scldm_vaew_workspace_bytes(h, B, S, G)
+        if need == 0:
+            raise _lib.ScldmError(f"scldm_vaew_workspace_bytes failed: {L.scldm_last_error().decode()}")
+        dev = self.input_layer.gene_embedding.weight.device
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._ws.data_ptr()
+
     # ------------------------------------------------------------------ native handle
     def _native(self):
         L = _lib.lib()
@@ -298,7 +352,7 @@ class TransformerVAE(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _weights_fp=None, _ws=None, _keep=None)
-        for k in ("_train_cache", "_found_inf", "_found_inf_handle", "_env_deterministic"):    # (the flag is registered with the handle that does not travel)
+        for k in ("_train_cache", "_found_inf", "_found_inf_handle", "_env_deterministic", "_whandle", "_wkey"):    # (the flag is registered with the handle that does not travel)
             state.pop(k, None)
         return state
 
@@ -390,6 +444,8 @@ class TransformerVAE(nn.Module):
         try:
             if self._handle is not None:
                 _lib.lib().scldm_vae_destroy(self._handle)
+            if self.__dict__.get("_whandle") is not None:
+                _lib.lib().scldm_vaew_destroy(self.__dict__["_whandle"])
         except Exception:
             pass
 
@@ -399,7 +455,8 @@ class TransformerVAE(nn.Module):
                genes_subset: torch.Tensor | None = None) -> torch.Tensor:
         c = counts_subset if counts_subset is not None else counts
         g = genes_subset if genes_subset is not None else genes
-        L, h = self._native()
+        wide = self.wide
+        L, h = self._native_wide() if wide else self._native()
         c = _require_cuda_f32("counts", c)
         if not g.is_cuda:
             raise RuntimeError("genes must be a CUDA (ROCm) tensor")
@@ -408,6 +465,12 @@ class TransformerVAE(nn.Module):
             raise ValueError(f"counts and genes must both be (B,S); got {tuple(c.shape)} and {tuple(g.shape)}")
         B, S = c.shape
         z = torch.empty(B, self.encoder.latent_dim, self.encoder.latent_embedding, device=c.device, dtype=torch.float32)
+        if wide:
+            ws = self._wide_workspace(L, h, B, S, 0)
+            with torch.cuda.device(c.device):
+                _lib.check(L.scldm_vaew_encode(h, c.data_ptr(), g.data_ptr(), B, S, z.data_ptr(), _lib.PRECISIONS[self.precision], ws,
+                                               _stream_ptr()), "scldm_vaew_encode")
+            return z
         ws = self._workspace(L, B, 1)
         with torch.cuda.device(c.device):
             _lib.check(L.scldm_vae_encode(h, c.data_ptr(), g.data_ptr(), B, S, z.data_ptr(), _lib.PRECISIONS[self.precision], ws,
@@ -417,7 +480,8 @@ class TransformerVAE(nn.Module):
     @torch.no_grad()
     def decode(self, z: torch.Tensor, genes: torch.Tensor, library_size: torch.Tensor,
                condition: dict[str, torch.Tensor] | None = None) -> torch.distributions.Distribution:
-        L, h = self._native()
+        wide = self.wide
+        L, h = self._native_wide() if wide else self._native()
         z = _require_cuda_f32("z", z)
         if not genes.is_cuda:
             raise RuntimeError("genes must be a CUDA (ROCm) tensor")
@@ -428,6 +492,13 @@ class TransformerVAE(nn.Module):
             raise ValueError(f"expected z (B,{self.encoder.latent_dim},{self.encoder.latent_embedding}) and library_size (B,1); got "
                              f"{tuple(z.shape)}, {tuple(library_size.shape)} for genes {tuple(g.shape)}")
         mu = torch.empty(B, G, device=z.device, dtype=torch.float32)
+        if wide:
+            theta = torch.empty(B, G, device=z.device, dtype=torch.float32)
+            ws = self._wide_workspace(L, h, B, 0, G)
+            with torch.cuda.device(z.device):
+                _lib.check(L.scldm_vaew_decode(h, z.data_ptr(), g.data_ptr(), lib.data_ptr(), B, G, mu.data_ptr(), theta.data_ptr(),
+                                               _lib.PRECISIONS[self.precision], ws, _stream_ptr()), "scldm_vaew_decode")
+            return NegativeBinomial(mu=mu, theta=theta)
         ws = self._workspace(L, B, G)
         if self.gaussian_head:      # Normal(mu, 1) (vae.py:83-85); library_size is accepted and unused, as in the reference
             with torch.cuda.device(z.device):
@@ -444,7 +515,12 @@ class TransformerVAE(nn.Module):
     def decode_sample(self, z: torch.Tensor, genes: torch.Tensor, library_size: torch.Tensor, seed: int | None = None) -> torch.Tensor:
         """`decode(z, genes, library_size).sample()` in one call (models.py:819 after vae.py:71-87): the negative-binomial draw is
         fused into the decoder's normalisation pass, mu / theta never reach HBM.  Returns counts (B, G) fp32.  Gaussian head: mu + n
-        from the per-gene kernel's epilogue, bit for bit `decode(...).sample(seed=seed)`."""
+        from the per-gene kernel's epilogue, bit for bit `decode(...).sample(seed=seed)`.  The wide route (`wide`) has no fused
+        draw: it is decode followed by scldm_nb_sample."""
+        if self.wide:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
+            return self.decode(z, genes, library_size).sample(seed=seed)
         L, h = self._native()
         z = _require_cuda_f32("z", z)
         if not genes.is_cuda:
@@ -478,6 +554,9 @@ class TransformerVAE(nn.Module):
         (`_VAETrainFn`: theta is then the per-element (B, G) dispersion).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.wide:
+                raise NotImplementedError("the wide TransformerVAE route (n_embed != 32) is inference only: there is no HIP backward for "
+                                          "it; call forward under torch.no_grad()")
             if self.gaussian_head and not self.train_gaussian_head:
                 raise NotImplementedError("training the Gaussian head (GaussianTransformerLayer) is switched off: set "
                                           "`train_gaussian_head = True` on the module (fp32), or call forward under torch.no_grad()")
