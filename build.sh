@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libscldm_hip.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.  The fifteen translation units are
+# Build libscldm_hip.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.  The sixteen translation units are
 # compiled in parallel (objects under build/, git-ignored) and linked into one shared library.
 set -euo pipefail
 cd "$(dirname "$0")"
@@ -30,7 +30,7 @@ stale() {  # $1 = tu
   return 1
 }
 pids=()
-TUS="api vae_api vae_train_api train_api train_fused train_dx logp_api optim train_step train_step_transport eval_api infer_wide scvi_api scvi_train_api vae_wide_api"
+TUS="api vae_api vae_train_api train_api train_fused train_dx logp_api optim train_step train_step_transport eval_api infer_wide scvi_api scvi_train_api vae_wide_api vae_wide_train_api"
 for tu in $TUS; do
   if stale "$tu"; then
     hipcc $FLAGS -MD -MF "$OBJ/$tu.d" -c "scldm_amd/csrc/$tu.hip" -o "$OBJ/$tu.o" &

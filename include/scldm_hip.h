@@ -1200,6 +1200,32 @@ int scldm_vaew_encode(scldm_vaew* h, const float* counts, const int64_t* genes, 
 int scldm_vaew_decode(scldm_vaew* h, const float* z, const int64_t* genes, const float* library_size, int B, int G, float* mu,
                       float* theta, int precision, void* ws, void* stream);
 
+/* Training of the wide shapes: the backward of TransformerVAE.forward = scldm_vaew_encode on the subset + scldm_vaew_decode on all genes,
+ * exact fp32 (both NB heads).  There is no recording forward: the caller keeps the inputs and (mu, theta, z) of the two inference calls,
+ * and scldm_vaew_train_backward rebuilds what it needs.  For each chunk of cells, in ascending order: the decoder chain is re-run from the
+ * saved z with the inference kernels, every stage into a buffer of its own (the two SwiGLU pre-activations by two plain products), and
+ * walked back; dz = the upstream dz + the decoder's; the encoder chain is re-run from the inputs and walked back.  The chunk size comes
+ * from scldm_vaew_train_plan under the handle's cap (SCLDM_VAEW_WS_MB, as for inference); one cell whose record exceeds the cap is
+ * SCLDM_ERR_SHAPE, the message names the bytes needed.
+ *
+ * `g` is a scldm_vae_weights of gradient pointers (writable, zero-initialised by the caller; enc_pos_embed is frozen in the reference and
+ * is not written; theta is NULL for the unshared head).  dmu, dtheta (B,G) and dz (B, n_inducing, n_embed_latent) may each be NULL.
+ * (order, seg, n_order) is the index of scldm_amd.vae.table_order over n_genes + 1 table rows: entry cell * G + slot is a decoder slot,
+ * entry B * G + cell * S + tok an encoder token; `rows` holds scldm_vaew_train_rows_bytes bytes (the per-entry rows of the gene table and
+ * of the theta table, written completely by the call), `ws` scldm_vaew_train_workspace_bytes (0: one cell does not fit the cap).
+ *
+ * No float atomics: every product accumulates in ascending k with k-splits that depend on the row count alone and are added in split
+ * order, LayerNorm / head column sums go through per-workgroup partials merged in workgroup order, attention splits in split order, the
+ * tables in the index's order, and weight gradients accumulate over the chunks in chunk order.  Every gradient is bit-equal run to run
+ * on one build, one GPU model and one cap; under another cap (another chunking) the weight gradients may differ in the last bits. */
+int scldm_vaew_train_plan(const scldm_vaew* h, int B, int S, int G, size_t cap_bytes, int* cells_per_chunk, int* n_chunks, size_t* ws_bytes);
+size_t scldm_vaew_train_workspace_bytes(const scldm_vaew* h, int B, int S, int G);
+size_t scldm_vaew_train_rows_bytes(const scldm_vaew* h, int B, int S, int G);
+int scldm_vaew_train_backward(scldm_vaew* h, const scldm_vae_weights* g, const float* counts_subset, const int64_t* genes_subset, int B, int S,
+                              const int64_t* genes, const float* library_size, int G, const float* mu, const float* theta, const float* z,
+                              const float* dmu, const float* dtheta, const float* dz, const int32_t* order, const int32_t* seg, int n_order,
+                              void* rows, void* ws, void* stream);
+
 /* Debug hook (tools/phase_timing.py): device buffer receiving 16 x u64 s_memtime phase stamps per
  * (workgroup, wave) of each fused-block launch.  Only builds with -DSCLDM_PHASE_TIMING record; the
  * production library returns SCLDM_ERR_STATE. */

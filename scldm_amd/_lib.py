@@ -373,6 +373,15 @@ def lib() -> C.CDLL:
     L.scldm_vaew_workspace_bytes.restype = C.c_size_t
     L.scldm_vaew_encode.argtypes = L.scldm_vae_encode.argtypes
     L.scldm_vaew_decode.argtypes = L.scldm_vae_decode.argtypes
+    # ... and its training backward (h, gradient struct, counts_subset, genes_subset, B, S, genes, library_size, G, mu, theta, z, dmu,
+    # dtheta, dz, order, seg, n_order, rows, ws, stream)
+    L.scldm_vaew_train_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_size_t)]
+    for f in (L.scldm_vaew_train_workspace_bytes, L.scldm_vaew_train_rows_bytes):
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        f.restype = C.c_size_t
+    L.scldm_vaew_train_backward.argtypes = ([C.c_void_p, C.POINTER(VaeWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 
@@ -403,7 +412,8 @@ EXPORTS = ["scldm_last_error", "scldm_version", "scldm_dit_create", "scldm_dit_d
            "scldm_scvi_encode_ex", "scldm_scvi_decode_ex", "scldm_scvi_forward_ex",
            "scldm_scvi_train_forward_ex", "scldm_scvi_train_backward_ex", "scldm_scvi_train_set_found_inf",
            "scldm_vaew_create", "scldm_vaew_destroy", "scldm_vaew_load_weights", "scldm_vaew_plan", "scldm_vaew_workspace_bytes",
-           "scldm_vaew_encode", "scldm_vaew_decode"]
+           "scldm_vaew_encode", "scldm_vaew_decode",
+           "scldm_vaew_train_plan", "scldm_vaew_train_workspace_bytes", "scldm_vaew_train_rows_bytes", "scldm_vaew_train_backward"]
 
 
 def check(rc: int, what: str) -> None:

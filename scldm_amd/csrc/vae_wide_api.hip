@@ -5,18 +5,11 @@
 
 #include "api_common.hpp"
 #include "vae_wide.hpp"
+#include "vae_wide_host.hpp"
 
 using namespace scldm;
 using namespace scldm::vaew;
-
-struct scldm_vaew {
-  scldm_vae_config cfg;
-  size_t cap_bytes;                     // workspace cap of a cell chunk (SCLDM_VAEW_WS_MB at creation)
-  bool loaded;
-  bool unshared_theta;
-  scldm_vae_weights w;                  // the parameters, read where they live
-  std::vector<scldm_vae_block> enc_blocks, dec_blocks;
-};
+using namespace scldm::vaew_host;
 
 static const size_t kDefaultCapMb = 1024;
 static const long long kMaxChunkRows = 1ll << 30;   // rows of one chunk (cells x tokens): row indices stay ints
@@ -172,13 +165,8 @@ extern "C" size_t scldm_vaew_workspace_bytes(const scldm_vaew* h, int B, int S, 
   return need;
 }
 
-// ---- launch helpers
+// ---- launch helpers (declared in vae_wide_host.hpp: the training backward rebuilds its record with them)
 namespace {
-struct Ctx {
-  const scldm_vaew* h;
-  int prec;
-  hipStream_t st;
-};
 template <int EPI>
 void gemm(const Ctx& c, const GemmArgs& a) {
   const dim3 grid(cdiv(a.M, kBM), cdiv(a.N, EPI == EPI_SWIGLU ? 32 : 64));
@@ -191,9 +179,14 @@ GemmArgs gemm_args(const float* X, const float* W, float* out, long long M, int 
   a.X = X; a.W0 = W; a.W1 = W; a.out = out; a.M = (int)M; a.N = N; a.K = K;
   return a;
 }
+}  // namespace
+namespace scldm {
+namespace vaew_host {
+static_assert(kWideMaxEmbed == kMaxEmbed, "one width limit");
+int wide_attn_keys_per_split(int hd) { return attn_keys_per_split(hd); }
 void store(const Ctx& c, const float* X, const float* W, float* out, long long M, int N, int K) { gemm<EPI_STORE>(c, gemm_args(X, W, out, M, N, K)); }
-void resid(const Ctx& c, const float* X, const float* W, float* out, long long M, int N, int K, const float* R, int rmod = 0,
-           const float* R2 = nullptr, int r2mod = 1, const int64_t* ridx = nullptr, int ridx_max = 0) {
+void resid(const Ctx& c, const float* X, const float* W, float* out, long long M, int N, int K, const float* R, int rmod,
+           const float* R2, int r2mod, const int64_t* ridx, int ridx_max) {
   GemmArgs a = gemm_args(X, W, out, M, N, K);
   a.R = R; a.rmod = rmod; a.R2 = R2; a.r2mod = r2mod; a.ridx = ridx; a.ridx_max = ridx_max;
   gemm<EPI_RESID>(c, a);
@@ -203,15 +196,15 @@ void swiglu(const Ctx& c, const float* X, const float* w1, const float* w2, floa
   a.W1 = w2;
   gemm<EPI_SWIGLU>(c, a);
 }
-void ln(const Ctx& c, const float* src, float* out, long long rows, int n, const float* w, const float* b, const int64_t* gidx = nullptr,
-        const float* counts = nullptr) {
+void ln(const Ctx& c, const float* src, float* out, long long rows, int n, const float* w, const float* b, const int64_t* gidx,
+        const float* counts) {
   LnArgs a;
   a.src = src; a.gidx = gidx; a.idx_max = c.h->cfg.n_genes; a.counts = counts; a.w = w; a.b = b; a.out = out; a.rows = rows; a.n = n;
   a.eps = c.h->cfg.layernorm_eps;
   ln_rows_kernel<<<cdiv(rows, 4), 256, 0, c.st>>>(a);
 }
 void attn(const Ctx& c, const float* Q, size_t q_bs, int q_ld, const float* K, const float* V, size_t kv_bs, int kv_ld, float* O, int cells,
-          int M, int S, int heads, float* part = nullptr) {
+          int M, int S, int heads, float* part) {
   AttnArgs a;
   const int n = c.h->cfg.n_embed;
   a.Q = Q; a.q_bs = q_bs; a.q_ld = q_ld; a.K = K; a.V = V; a.kv_bs = kv_bs; a.kv_ld = kv_ld; a.O = O; a.o_ld = n; a.M = M; a.S = S;
@@ -226,6 +219,9 @@ void attn(const Ctx& c, const float* Q, size_t q_bs, int q_ld, const float* K, c
     attn_merge_kernel<<<cdiv(rows, 4), 256, 0, c.st>>>(part, O, n, rows, heads, M, a.hd, a.splits);
   }
 }
+}  // namespace vaew_host
+}  // namespace scldm
+namespace {
 // the plain Blocks on the cells' inducing-point rows h (rows, n), in place (layers.py:222-226)
 void trunk(const Ctx& c, const std::vector<scldm_vae_block>& blocks, const Layout& L, char* ws, int cells) {
   const scldm_vae_config& f = c.h->cfg;

@@ -212,6 +212,66 @@ class _VAEGaussTrainFn(torch.autograd.Function):
         return (None, None, None, None, *out)
 
 
+class _VAEWideTrainFn(torch.autograd.Function):
+    """`_VAETrainFn` for the wide shapes (TransformerVAE.train_wide).  The forward IS the inference route - scldm_vaew_encode on the
+    subset, scldm_vaew_decode on all genes, launched as under no_grad, so the outputs are bit-equal to the no_grad forward - and keeps
+    only the inputs and (mu, theta, z).  The backward (scldm_vaew_train_backward, exact fp32) rebuilds the record per chunk of cells
+    under the workspace cap (SCLDM_VAEW_WS_MB) and walks it back; the two embedding tables' gradients are fixed-order segmented sums
+    over `table_order`'s index, so every gradient is bit-equal run to run on one build, one GPU model and one cap (another cap is
+    another chunking: the weight gradients may then differ in the last bits).  The step cannot be captured into a graph: building the
+    index allocates."""
+
+    @staticmethod
+    def forward(ctx, module, counts_subset, genes_subset, genes, lib, *params):
+        z = module.encode(counts_subset, genes_subset)
+        nb = module.decode(z, genes, lib)
+        ctx.module = module
+        ctx.inputs = (counts_subset, genes_subset, genes, lib)
+        ctx.outs = (nb.mu, nb.theta, z)
+        ctx.params = params
+        ctx.param_versions = [p._version for p in params]
+        return nb.mu, nb.theta, z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmu, dtheta, dz):
+        module, params = ctx.module, ctx.params
+        if [p._version for p in params] != ctx.param_versions:
+            raise RuntimeError("TransformerVAE parameters were modified between forward and backward (the HIP backward reads them live)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the wide TransformerVAE training backward cannot be captured into a graph: building the table index "
+                               "allocates; run this step eagerly")
+        L, h = module._native_wide()
+        counts_subset, genes_subset, genes, lib = ctx.inputs
+        mu, theta, z = ctx.outs
+        B, S = counts_subset.shape
+        G = genes.shape[1]
+        dev = mu.device
+        prep = lambda t: None if t is None else t.contiguous().float()
+        dmu, dtheta, dz = prep(dmu), prep(dtheta), prep(dz)
+        flat, _, g = _grad_structs(module, params, dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        need = L.scldm_vaew_train_workspace_bytes(h, B, S, G)
+        if need == 0:
+            raise _lib.ScldmError(f"scldm_vaew_train_workspace_bytes failed: {L.scldm_last_error().decode()}")
+        ws = module.__dict__.get("_wtrain_ws")
+        if ws is None or ws.numel() < need or ws.device != dev:
+            module.__dict__["_wtrain_ws"] = None
+            ws = module.__dict__["_wtrain_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            order, seg = table_order(genes, genes_subset, counts_subset, module.input_layer.gene_embedding.weight.shape[0])
+            rows = torch.empty(L.scldm_vaew_train_rows_bytes(h, B, S, G), dtype=torch.uint8, device=dev)
+            _lib.check(L.scldm_vaew_train_backward(h, C.byref(g), counts_subset.data_ptr(), genes_subset.data_ptr(), B, S, genes.data_ptr(),
+                                                   lib.data_ptr(), G, mu.data_ptr(), theta.data_ptr(), z.data_ptr(), ptr(dmu), ptr(dtheta),
+                                                   ptr(dz), order.data_ptr(), seg.data_ptr(), order.numel(), rows.data_ptr(), ws.data_ptr(),
+                                                   _stream_ptr()),
+                       "scldm_vaew_train_backward")
+        module.last_table_gradient_mode = "ordered"
+        views = _unflatten_dense_tensors(flat, params)
+        out = [v if ctx.needs_input_grad[5 + i] else None for i, v in enumerate(views)]
+        return (None, None, None, None, None, *out)
+
+
 class TransformerVAE(nn.Module):
     # Gradients of the two embedding tables (gene_embedding, theta) in training: False = float atomics (torch's own embedding
     # backward does the same), True = a fixed-order segmented sum (scldm_vae_train_backward_ordered): with it EVERY gradient is
@@ -228,6 +288,11 @@ class TransformerVAE(nn.Module):
     # backward; True = forward returns differentiable {"mu", "theta"}, z through `_VAETrainFn` (the C entries route on the handle:
     # wide::dec_gene_bwd_nb2_kernel), `precision` "fp32" or "fp16", `deterministic` as for the shared head.
     train_unshared_theta: bool = False
+    # Training of the wide shapes (`wide`: n_embed 64..1024, the route of scldm_vaew_*): False = forward under autograd raises
+    # NotImplementedError ("inference only"), as it did before that route had a backward; True = forward returns differentiable
+    # {"mu", "theta"}, z through `_VAEWideTrainFn` (scldm_vaew_train_backward): both NB heads, `precision` "fp32" only, the table
+    # gradients always in the ordered mode (every gradient bit-equal run to run), so a step cannot be captured into a graph.
+    train_wide: bool = False
     last_table_gradient_mode: str | None = None      # "ordered" / "atomic": the mode of the last backward
 
     def __init__(self, encoder: Encoder, decoder: Decoder, decoder_head: NegativeBinomialTransformerLayer | GaussianTransformerLayer,
@@ -352,7 +417,7 @@ class TransformerVAE(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.update(_handle=None, _weights_key=None, _weights_fp=None, _ws=None, _keep=None)
-        for k in ("_train_cache", "_found_inf", "_found_inf_handle", "_env_deterministic", "_whandle", "_wkey"):    # (the flag is registered with the handle that does not travel)
+        for k in ("_train_cache", "_found_inf", "_found_inf_handle", "_env_deterministic", "_whandle", "_wkey", "_wtrain_ws"):    # (the flag is registered with the handle that does not travel)
             state.pop(k, None)
         return state
 
@@ -548,15 +613,21 @@ class TransformerVAE(nn.Module):
 
     def forward(self, counts, genes, library_size, counts_subset=None, genes_subset=None):
         """(params, z) with params = {"mu", "theta"}, or {"mu"} for the Gaussian head (vae.py:29-56).  With gradients enabled and trainable parameters the outputs
-        are differentiable: forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
+        are differentiable.  A wide shape: with `train_wide = True`, in exact fp32, through `_VAEWideTrainFn`.  The 32-wide shape:
+        forward on the inference kernels + a hand-derived HIP backward (`_VAETrainFn`), in `precision` "fp32"
         (exact) or "fp16" (the reference's TF32 class; overflow flag: found_inf_flag()); the Gaussian head with
         `train_gaussian_head = True`, in fp32 (`_VAEGaussTrainFn`); the unshared-theta NB head with `train_unshared_theta = True`
         (`_VAETrainFn`: theta is then the per-element (B, G) dispersion).  As in the
         reference, the encoder reads counts_subset / genes_subset (vae.py:37-40: no fallback to the full vectors in forward)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.wide:
+            wide = self.wide
+            if wide and not self.train_wide:
                 raise NotImplementedError("the wide TransformerVAE route (n_embed != 32) is inference only: there is no HIP backward for "
                                           "it; call forward under torch.no_grad()")
+            if wide:        # `train_wide`: the NB heads in exact fp32 (scldm_vaew_train_backward)
+                if not self.gaussian_head and self.precision != "fp32":
+                    raise NotImplementedError(f"the wide TransformerVAE route trains in exact fp32 only (precision={self.precision!r})")
+                self._native_wide()     # refuses the Gaussian head, a shape outside the family and a CPU module
             if self.gaussian_head and not self.train_gaussian_head:
                 raise NotImplementedError("training the Gaussian head (GaussianTransformerLayer) is switched off: set "
                                           "`train_gaussian_head = True` on the module (fp32), or call forward under torch.no_grad()")
@@ -573,6 +644,9 @@ class TransformerVAE(nn.Module):
             if cs.dim() != 2 or gs.shape != cs.shape or g.dim() != 2 or g.shape[0] != cs.shape[0] or lib.shape[0] != cs.shape[0]:
                 raise ValueError(f"expected counts_subset / genes_subset (B,S), genes (B,G), library_size (B,1); got {tuple(cs.shape)}, "
                                  f"{tuple(gs.shape)}, {tuple(g.shape)}, {tuple(library_size.shape)}")
+            if wide:
+                mu, theta, z = _VAEWideTrainFn.apply(self, cs, gs, g, lib, *tuple(self.parameters()))
+                return {"mu": mu, "theta": theta}, z
             if self.gaussian_head:
                 mu, z = _VAEGaussTrainFn.apply(self, cs, gs, g, *tuple(self.parameters()))
                 return {"mu": mu}, z
